@@ -2,13 +2,19 @@
 """bench.py -- parcel moment-RHS evaluations per second of the MI355X coalescence kernel.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--parcels P] [--workload cfg3a|cfg3b|cfg2]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (cloudy_coal_rhs: normalise -> closure inversion -> moments ->
 finite 2-D integrals -> Q/R/S -> de-normalise) over one device-resident batch of synthetic parcels.
 Headline workload (BASELINE.json configs[2], SURVEY.md 8(d) "cfg3a"): 1e7 parcels per GPU, two Gamma modes,
 order-2 polynomial CoalescenceTensors (the exact pieces of Long's kernel), 6 prognostic moments, fp64,
-thresholds (Inf, Inf).  The same batch with the reference example's finite threshold (5e-10 kg, Inf)
-("cfg3b", the Simpson / incomplete-gamma path) is measured in the same run and reported under "variants".
+thresholds (Inf, Inf).
+
+A plain run sets up, warms up, times exactly K steps and prints the line: value = parcels x K / wall, ms_per_step =
+wall / K.  --dump-outputs DIR then writes what the last timed step computed (see _dump_outputs).  --full adds everything
+else: HIP-event kernel times and rooflines, the conservation diagnostic through the RCCL communicator, the variants (the
+same batch with the reference example's finite threshold (5e-10 kg, Inf), "cfg3b", the Simpson / incomplete-gamma path;
+other precisions, configurations and integrators) and the CPU baselines.
 
 Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL); parcels shard with no data-path
 collective (weak scaling: every rank owns --parcels parcels).  The only collective is the all-reduce of the
@@ -508,7 +514,25 @@ def _gather(x, dist, torch):
     return [float(t.item()) for t in parts]
 
 
-def _run_workload(pkg, name, n_parcels, steps, warmup, rank, dist, torch):
+DUMP_MAX_BYTES = 48 << 20   # --dump-outputs: what one run writes at most (the cap is 64 MB)
+
+
+def _dump_outputs(out_dir, dm, name="dm"):
+    """--dump-outputs: the tendencies dM/dt of the last timed step -- what the caller of cloudy_coal_rhs receives -- as
+    <out_dir>/<name>.npy, (planes, parcels) in the batch's own precision.  A batch larger than DUMP_MAX_BYTES is sampled: a
+    fixed set of parcel columns (seeded, sorted; the same for every run with the same --workload / --parcels)."""
+    os.makedirs(out_dir, exist_ok=True)
+    planes, n = dm.shape
+    a = dm.to_numpy()
+    cap = DUMP_MAX_BYTES // (planes * a.dtype.itemsize)
+    if n > cap:
+        idx = np.sort(np.random.Generator(np.random.Philox(key=SEED + 1)).choice(n, cap, replace=False))
+        a = a[:, idx]
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def _run_workload(pkg, name, n_parcels, steps, warmup, rank, dist, torch, full=True, dump_dir=None):
+    """Warm-up + exactly `steps` timed launches; with `full`, the HIP-event kernel time and the conservation diagnostic"""
     wl = make_workload(name, n_parcels, seed=SEED + 1000 * rank)
     plan = wl["coal_data"].plan(wl["dist_types"])
     m = pkg.DeviceArray.from_numpy(wl["mom"])
@@ -525,6 +549,10 @@ def _run_workload(pkg, name, n_parcels, steps, warmup, rank, dist, torch):
         pkg._lib.check(pkg.lib().cloudy_stream_synchronize(None))
         done += 8
     wall = _time_steps(pkg, plan, m, dm, steps, dist, torch)
+    if dump_dir:
+        _dump_outputs(dump_dir, dm)
+    if not full:
+        return dict(wl=wl, plan=plan, wall=wall, nmom=plan.nmom)
     ev_ms = _event_ms(pkg, plan, m, dm, steps)
     # conservation diagnostic: sum over parcels and modes of dM1 must vanish (mass is conserved)
     if _COMM["comm"] is not None:     # local plane sums + ncclAllReduce on the launch stream, inside the library
@@ -1118,9 +1146,10 @@ def emit(full, json_out, side_file=True):
             f.write("\n")
     except OSError as e:   # a read-only checkout: the line still goes out
         print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
-    print("bench.py full result (also in " + VARIANTS_FILE + "):\n" + json.dumps(full, allow_nan=False), file=sys.stderr)
+    print("bench.py full result" + (" (also in " + VARIANTS_FILE + ")" if side_file else "") + ":\n"
+          + json.dumps(full, allow_nan=False), file=sys.stderr)
     sys.stderr.flush()
-    json_out.write(compact_line(full) + "\n")
+    json_out.write(compact_line(full, VARIANTS_FILE if side_file else None) + "\n")
     json_out.flush()
 
 
@@ -1201,6 +1230,9 @@ def _one_process(args):
                       "launch": "ONE process driving all GPUs (cloudy_comm_create_all + cloudy_comm_group_start/_end)"},
            "collective": f"ncclAllReduce(sum, f64, {nmom}) per device inside one group, RCCL {v // 10000}.{v // 100 % 100}.{v % 100}, {N} device(s)",
            "mass_rate_residual": abs(mass) / max(gross, 1e-300), "np_modes": np_modes}
+    if args.dump_outputs:   # device 0's tendencies of the last timed step (the all-reduce above only reads them)
+        pkg._lib.check(L.cloudy_set_device(0))
+        _dump_outputs(args.dump_outputs, devs[0]["dm"])
     emit(out, json_out)
     return 0
 
@@ -1212,16 +1244,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--parcels", type=int, default=0, help="parcels per GPU (default: the workload's size)")
     ap.add_argument("--workload", default="cfg3a")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tendencies of the last timed step to DIR/dm.npy (a fixed sample of large batches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: HIP-event kernel times and rooflines, the "
+                         "conservation diagnostic through the RCCL communicator, the variants and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baselines")
+    ap.add_argument("--no-variants", action="store_true", help="(with --full) skip the variants")
     ap.add_argument("--all-cpu-baselines", action="store_true",
-                    help="also time the cfg3b and cfg4q (10-point rule) oracles and one parcel of the reference's own nested "
-                         "quadgk algorithm (the default run times the headline + the converged-mode baseline: ~30 s of CPU)")
+                    help="(with --full) also time the cfg3b and cfg4q (10-point rule) oracles and one parcel of the reference's "
+                         "own nested quadgk algorithm (--full alone times the headline + the converged-mode baseline: ~30 s of CPU)")
     ap.add_argument("--one-process", action="store_true",
                     help="one process drives all --gpus devices (cloudy_comm_create_all) instead of one rank per GPU")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.one_process:
         return _one_process(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1248,18 +1287,18 @@ def main():
         raise SystemExit("bench.py needs a HIP device: the coalescence RHS has no CPU fallback")
     pkg._lib.check(pkg.lib().cloudy_set_device(local_rank))
     _fault("before_barrier", rank)
-    _comm_setup(pkg, world, local_rank, dist, torch)
+    if args.full:   # the communicator serves the conservation diagnostic only: the timed path has no collective
+        _comm_setup(pkg, world, local_rank, dist, torch)
 
     spec = workload_spec(args.workload)
     n_local = args.parcels or spec["default_parcels"]
-    res = _run_workload(pkg, args.workload, n_local, args.steps, args.warmup, rank, dist, torch)
+    res = _run_workload(pkg, args.workload, n_local, args.steps, args.warmup, rank, dist, torch, full=args.full,
+                        dump_dir=args.dump_outputs if rank == 0 else None)
     t_headline = time.perf_counter()
     nmom = res["nmom"]
     bytes_per_eval = 2 * nmom * 8  # read nmom moments + write nmom tendencies, fp64
     total = n_local * world
     value = total * args.steps / res["wall"]
-    achieved = bytes_per_eval * n_local / (res["event_ms"] * 1e-3) / 1e9
-    per_rank_ms = _gather(res["event_ms"], dist, torch)   # every rank's HIP-event average of its own launches
     # which device each rank ran on -- a SCALE record must show N distinct devices
     import ctypes as _C
 
@@ -1267,7 +1306,12 @@ def main():
     _rc = pkg.lib().cloudy_device_pci_bus_id(local_rank, _bus, 64)
     per_rank_dev = _gather_objects({"rank": rank, "pid": os.getpid(), "device": local_rank,
                                     "pci_bus_id": _bus.value.decode() if _rc == 0 else None,
-                                    "kernel_ms": res["event_ms"]}, dist)
+                                    "kernel_ms": res.get("event_ms")}, dist)
+    if not args.full:
+        return _plain_result(args, rank, world, dist, json_out, spec, n_local, nmom, value, res, per_rank_dev,
+                             t_start, t_headline)
+    achieved = bytes_per_eval * n_local / (res["event_ms"] * 1e-3) / 1e9
+    per_rank_ms = _gather(res["event_ms"], dist, torch)   # every rank's HIP-event average of its own launches
 
     measured = _measured_latest()
     traffic = None
@@ -1604,23 +1648,8 @@ def main():
                 variants["cfg4q"]["cpu_baseline"] = _cpu_baseline_cfg4q(cpu["cores"], target_seconds=6.0)
 
     if rank == 0:
-        out = {
-            "metric": "parcel moment-RHS evals/sec at 1e7 parcels; achieved HBM GB/s vs 8 TB/s peak",
-            "value": value,
-            "unit": "parcel-RHS/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * res["wall"] / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"{args.workload}: {n_local} parcels/GPU, {spec['n_modes']}-mode Gamma mixture, "
-                                   f"order-{2 if spec['kernel'] == 'long' else 1} polynomial CoalescenceTensor, "
-                                   f"{nmom} moments, thresholds {spec['thresholds']}, norms {NORMS}",
-                       "parcels_per_gpu": n_local, "global_parcels": total, "sharding": f"parcel ranges x{world}"},
+        out = _headline_keys(args, world, spec, n_local, nmom, value, res["wall"])
+        out.update({
             "roofline": dict(_headline_roofline(args.workload, res["plan"], n_local, nmom, res["event_ms"], per_rank_ms,
                                                 traffic, measured), **({"traffic_note": traffic_note} if traffic_note else {})),
             "cpu_baseline": cpu,
@@ -1637,12 +1666,53 @@ def main():
             # workloads under "variants", and the CPU baseline
             "process_wall_s": {"setup_and_headline": t_headline - t_start, "timed_region": res["wall"],
                                "variants": t_variants - t_headline, "cpu_baseline": time.perf_counter() - t_variants},
-        }
+        })
         emit(out, json_out)
         if hung:
             sys.stderr.write("bench.py rank 0: RCCL communicator set-up hung; the line carries collective_fallback = true; exit 3\n")
             sys.stderr.flush()
             os._exit(3)   # (as the other ranks above: a thread is still inside ncclCommInitRank)
+    _rank_done()
+    return 0
+
+
+def _headline_keys(args, world, spec, n_local, nmom, value, wall):
+    """the keys of the line that mean the same in a plain run and in a --full run"""
+    return {
+        "metric": "parcel moment-RHS evals/sec at 1e7 parcels; achieved HBM GB/s vs 8 TB/s peak",
+        "value": value,
+        "unit": "parcel-RHS/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * wall / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {n_local} parcels/GPU, {spec['n_modes']}-mode Gamma mixture, "
+                               f"order-{2 if spec['kernel'] == 'long' else 1} polynomial CoalescenceTensor, "
+                               f"{nmom} moments, thresholds {spec['thresholds']}, norms {NORMS}",
+                   "parcels_per_gpu": n_local, "global_parcels": n_local * world, "sharding": f"parcel ranges x{world}"},
+    }
+
+
+def _plain_result(args, rank, world, dist, json_out, spec, n_local, nmom, value, res, per_rank_dev, t_start, t_headline):
+    """The end of a plain run (no --full): the headline keys, which devices the ranks ran on, no side file"""
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        out = _headline_keys(args, world, spec, n_local, nmom, value, res["wall"])
+        out.update({
+            "per_rank_devices": per_rank_dev,
+            "ranks_share_a_gpu": not _COMM["own_gpu_per_rank"],
+            "distinct_devices": len({d.get("pci_bus_id") for d in per_rank_dev if d.get("pci_bus_id")}),
+            "collective": "none: the conservation diagnostic, kernel times, variants and CPU baselines run with --full",
+            "process_wall_s": {"setup_and_headline": t_headline - t_start, "timed_region": res["wall"]},
+        })
+        emit(out, json_out, side_file=False)
     _rank_done()
     return 0
 

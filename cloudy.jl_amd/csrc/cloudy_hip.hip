@@ -1019,11 +1019,14 @@ int cloudy_closure_stats(const cloudy_plan *plan, size_t n, size_t ld, const voi
     hipStream_t st = (hipStream_t)stream;
     size_t blocks = (n + kBlock - 1) / kBlock;
     if (blocks > (size_t)(4 * kSumBlocks)) blocks = 4 * kSumBlocks;
-    // one row of 4N counters per workgroup, every one of them stored by its workgroup (nothing to zero, no atomics)
+    // one row of 4N counters per workgroup, every one of them stored by its workgroup (nothing to zero, no atomics).
+    // The rows live in a plain device allocation: taken from the stream-ordered pool (hipMallocAsync / hipFreeAsync) they came
+    // back all zero for a 4-mode plan on one box (every counter, the oracle's 469 ... 940 included), as the v1 counters came back
+    // short -- the stores of the kernel not seen by the copy.  The other reductions use plain allocations and never did.
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counter width");
     std::vector<uint64_t> rows(blocks * (size_t)nc);
     unsigned long long *dev = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&dev, sizeof(unsigned long long) * rows.size(), st));
+    HIP_TRY(hipMalloc((void **)&dev, sizeof(unsigned long long) * rows.size()));
     if (h.dtype != CLOUDY_F64)
         hipLaunchKernelGGL(closure_stats_kernel<float>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a, n, ld, (const float *)mom_dev, dev);
     else
@@ -1031,7 +1034,7 @@ int cloudy_closure_stats(const cloudy_plan *plan, size_t n, size_t ld, const voi
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(rows.data(), dev, sizeof(uint64_t) * rows.size(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFreeAsync(dev, st);
+    (void)hipFree(dev);
     if (e == hipSuccess)
         for (size_t b = 0; b < blocks; ++b)
             for (int q = 0; q < nc; ++q) counts_host[q] += rows[b * (size_t)nc + q];

@@ -529,3 +529,31 @@ def test_bench_contract_line_is_compact_strict_json():
            "collective": "ncclAllReduce", "mass_rate_residual": 1e-17}
     o1 = _strict_loads(bench.compact_line(one))
     assert o1["config"]["launch"].startswith("ONE process") and o1["cpu_baseline"] is None and o1["variants"] == {}
+
+
+def test_bench_dump_outputs_is_a_fixed_capped_sample(tmp_path):
+    """bench._dump_outputs (`bench.py --dump-outputs DIR`): a batch within the cap is written whole, in its own precision; a
+    larger one as the same sorted, distinct parcel columns on every run, within the 64 MB the option may write"""
+    import bench
+
+    class Host:   # stands in for a DeviceArray: .shape and .to_numpy()
+        def __init__(self, a):
+            self.a, self.shape = a, a.shape
+
+        def to_numpy(self):
+            return self.a.copy()
+
+    small = np.arange(6 * 1000, dtype=np.float64).reshape(6, 1000)
+    bench._dump_outputs(str(tmp_path / "small"), Host(small))
+    got = np.load(tmp_path / "small" / "dm.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    bench._dump_outputs(str(tmp_path / "f32"), Host(small.astype(np.float32)))
+    assert np.load(tmp_path / "f32" / "dm.npy").dtype == np.float32
+    n = bench.DUMP_MAX_BYTES // 48 + 54_321
+    big = np.tile(np.arange(n, dtype=np.float64), (6, 1))
+    for d in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / d), Host(big))
+    a, b = np.load(tmp_path / "a" / "dm.npy"), np.load(tmp_path / "b" / "dm.npy")
+    assert np.array_equal(a, b) and a.nbytes <= bench.DUMP_MAX_BYTES <= 64 << 20 and a.shape == (6, bench.DUMP_MAX_BYTES // 48)
+    cols = a[0]
+    assert np.all(np.diff(cols) > 0) and cols[0] >= 0 and cols[-1] < n and np.array_equal(a, np.tile(cols, (6, 1)))

@@ -218,8 +218,8 @@ def test_bench_gpus_2_spawns_two_ranks(gpu_cloudy, tmp_path):
     env = dict(os.environ, CLOUDY_BENCH_BACKEND="gloo", CLOUDY_BENCH_ALLOW_SHARED_GPU="1", CLOUDY_BENCH_LOG_DIR=str(tmp_path))
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--parcels", "400000", "--steps", "5",
-                        "--warmup", "2", "--no-variants", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
-                       timeout=900)
+                        "--warmup", "2", "--full", "--no-variants", "--no-cpu-baseline"], env=env, capture_output=True,
+                       text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
@@ -256,7 +256,8 @@ def test_bench_gpus_8_on_one_gpu_with_an_empty_jit_cache(gpu_cloudy, tmp_path):
                CLOUDY_BENCH_LOG_DIR=str(tmp_path / "logs"))
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--parcels", "200000", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                       timeout=1500)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = p.stdout.splitlines()[-1]
     assert len(line) < 4096, len(line)
@@ -358,8 +359,38 @@ def test_bench_single_rank_line_uses_the_c_abi_collective(gpu_cloudy):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--parcels", "400000", "--steps", "5", "--warmup", "2",
-                        "--no-variants", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-variants", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     out = json.loads(p.stdout.splitlines()[-1])
     assert "ncclAllReduce" in out["collective"] and "libcloudy_hip.so" in out["collective"], out["collective"]
     assert out["mass_rate_residual"] is not None and out["collective_fallback"] is False
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(gpu_cloudy, oracle, tmp_path):
+    """`python bench.py` without --full: the headline keys and nothing measured besides them; ms_per_step is the wall time
+    of one of the --steps timed steps; --dump-outputs writes the tendencies of the timed path, which equal the oracle's on
+    the bench's own batch"""
+    import json
+
+    import bench
+
+    n = 200_000
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--parcels", str(n), "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    out = json.loads(p.stdout.splitlines()[-1])
+    assert out["steps"] == 7 and out["warmup"] == 2 and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["unit"] == "parcel-RHS/s" and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(n * 1e3 / out["ms_per_step"], rel=1e-6)
+    assert out["variants"] == {} and out["cpu_baseline"] is None and out["mass_rate_residual"] is None
+    assert out["variants_file"] is None and out["process_wall_s"]["timed_region"] == pytest.approx(7e-3 * out["ms_per_step"], rel=1e-3)
+    dm = np.load(tmp_path / "out" / "dm.npy")
+    assert dm.shape == (6, n) and dm.dtype == np.float64
+    mom = bench.synth_moments(2, n, bench.SEED)          # rank 0's batch of the run
+    want, scale = oracle.rhs_coal_batch(bench.oracle_params("cfg3a"), mom, with_scale=True)
+    assert np.array_equal(np.isnan(dm), np.isnan(want))
+    ok = ~np.isnan(want)
+    assert np.all(np.abs(dm[ok] - want[ok]) <= 1e-13 * scale[ok])
