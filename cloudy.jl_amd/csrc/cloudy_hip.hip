@@ -14,7 +14,6 @@
 
 #include <map>
 #include <mutex>
-#include <mutex>
 #include <string>
 #include <utility>
 
@@ -29,22 +28,10 @@ using namespace cloudy;
 
 struct cloudy_plan {
     HostPlan h;
-    bool jit_on = false;   // plan-time specialised kernels (jit.hpp) serve cloudy_coal_rhs / cloudy_ssprk33_steps
-    JitKernels jit;
-    std::string jit_log;   // why not, when jit_on is false
-    // thresholded plans compile their fused integrator on the first cloudy_ssprk33_steps call
-    mutable std::once_flag int_once, rs_once, rsint_once, tsit5_once, rsint512_once, rsint1024_once, rsint320_once;
-    mutable hipFunction_t int_ssprk33 = nullptr, rs_coal = nullptr, rs_int = nullptr, int_tsit5 = nullptr;
-    mutable hipFunction_t rs_int512 = nullptr, rs_int1024 = nullptr;  // the column integrator for 256 < nz <= 512 / 1024
-    mutable hipFunction_t rs_int320 = nullptr;                        // ... with 320-thread workgroups (jit_rainshaft_part)
-    mutable hipFunction_t rs_rhs = nullptr, rs_rhs512 = nullptr, rs_rhs1024 = nullptr;  // one RHS evaluation, same modules
-    // one log per once-flag (a single string written from seven independent call_once lambdas raced when two host
-    // threads made first calls to different entry points of one plan, and a later successful compile overwrote the log an
-    // earlier failure's message refers to); each is written once, inside its call_once, and read only after it
-    mutable std::string int_log, rs_log, rsint_log, rsint512_log, rsint1024_log, rsint320_log, tsit5_log, diag_log;
-    // plans beyond the ahead-of-time families: diagnostics and parameter-plane entry points compiled on first use (jit.hpp part 7)
-    mutable std::once_flag diag_once;
-    mutable JitDiag diag;
+    bool jit_on = false;   // the main unit compiled for the plan (jit.hpp) loaded: plan-time specialised kernels serve the plan
+    // one lazy slot per translation unit compiled for the plan (jit_unit(); the main unit is filled at plan creation, its log
+    // says why jit_on is false)
+    mutable JitSlot jit[JIT_UNITS];
     // NumericalCoalStyle plans in converged mode: the cost hints of coal_rhs_quad_body (quad_kernels.hpp) -- one byte per parcel,
     // two for a Long-kernel plan (second plane at hint + cap).  Allocated on the first cloudy_coal_rhs call, grown (x 2 at least)
     // when a larger batch arrives, never per call otherwise; CLOUDY_HIP_CONV_HINTS=0 turns the mechanism off.  Kernels of
@@ -132,8 +119,6 @@ int fail_hip(hipError_t e, const char *what) {
 
 constexpr int kSumBlocks = 1024;
 
-inline bool plan_beyond_aot(const HostPlan &h) { return h.N > CLOUDY_AOT_MAX_MODES || h.P > CLOUDY_AOT_MAX_P; }
-
 hipError_t dispatch(const HostPlan &h, const LaunchReq &r) {
     using Fn = hipError_t (*)(const HostPlan &, const LaunchReq &);
     static const Fn table[CLOUDY_AOT_MAX_MODES][CLOUDY_AOT_MAX_P] = {
@@ -174,61 +159,48 @@ int check_batch(const cloudy_plan *plan, size_t n, size_t ld, const void *a, con
     return CLOUDY_OK;
 }
 
-// The column kernel compiled for the plan that serves columns of nz cells: the workgroup size jit_rainshaft_part prefers, then
-//  every smaller one that still holds a column and fits the LDS -- a kernel that does not compile or load is not the
-// end of the call while another can serve it.  Compiles on first use.  fn == nullptr: none (the caller steps stage by stage, or
-// runs the ahead-of-time integrator).  rhs_only: the one-evaluation kernel of the same translation unit (cloudy_rainshaft_rhs).
-struct RsPick {
-    hipFunction_t fn = nullptr;
-    int bs = 0;
-};
-RsPick pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, bool rhs_only) {
-    RsPick r;
-    if (!plan->jit_on || nz < 1 || nz > 1024) return r;
-    const HostPlan &h = plan->h;
-    const auto get = [&](int part) -> hipFunction_t {
-        switch (part) {
-        case 3:
-            std::call_once(plan->rsint_once, [&] { (void)jit_get_rainshaft_integrator(h, plan->rs_int, plan->rsint_log, 3, &plan->rs_rhs); });
-            return rhs_only ? plan->rs_rhs : plan->rs_int;
-        case 5:
-            std::call_once(plan->rsint512_once, [&] { (void)jit_get_rainshaft_integrator(h, plan->rs_int512, plan->rsint512_log, 5, &plan->rs_rhs512); });
-            return rhs_only ? plan->rs_rhs512 : plan->rs_int512;
-        case 6:
-            std::call_once(plan->rsint1024_once, [&] { (void)jit_get_rainshaft_integrator(h, plan->rs_int1024, plan->rsint1024_log, 6, &plan->rs_rhs1024); });
-            return rhs_only ? plan->rs_rhs1024 : plan->rs_int1024;
-        case 8:   // (CLOUDY_HIP_RS_BLOCK=320: an experiment switch of the integrator only)
-            if (rhs_only) return nullptr;
-            std::call_once(plan->rsint320_once, [&] { (void)jit_get_rainshaft_integrator(h, plan->rs_int320, plan->rsint320_log, 8); });
-            return plan->rs_int320;
-        default: return nullptr;
-        }
-    };
-    int part = jit_rainshaft_part(h, nz, n_columns);
-    if (part == 8) {
-        if ((r.fn = get(8)) != nullptr) {
-            r.bs = jit_rainshaft_block(8);
-            return r;
-        }
-        part = jit_rainshaft_part(h, nz, n_columns, false);   // (the normal pick for this height, not unconditionally 256 threads)
-    }
-    const int order[3] = {6, 5, 3};
-    bool reached = false;
-    for (int i = 0; i < 3; ++i) {
-        if (order[i] == part) reached = true;
-        if (!reached || !jit_rainshaft_fits(h, order[i], nz)) continue;
-        if ((r.fn = get(order[i])) != nullptr) {
-            r.bs = jit_rainshaft_block(order[i]);
-            return r;
-        }
-    }
-    return r;
+// Unit u of the plan, compiled and loaded on first use (the main unit at plan creation); never ok when plan-time compilation is off.
+const JitSlot &jit_unit(const cloudy_plan *plan, JitUnit u) {
+    JitSlot &s = plan->jit[u];
+    std::call_once(s.once, [&] { s.ok = plan->jit_on && jit_load(plan->h, u, s); });
+    return s;
 }
 
-// cloudy_coal_rhs / cloudy_ssprk33_steps of a specialised plan: same grids and the same two-parcels-per-lane
-// alignment rule as launch_io() in launch_impl.hpp.
-hipError_t launch_jit(const cloudy_plan *plan, const LaunchReq &r) {
+// The column unit that serves columns of nz cells: the one jit_rainshaft_part prefers, then every smaller one that
+// still holds a column and fits the LDS -- a unit that does not compile or load is not the end of the call while another can
+// serve it.  Loads on first use.  JIT_UNITS: none (the caller steps stage by stage, or runs the ahead-of-time integrator).
+// rhs_only: a unit with the one-evaluation kernel (cloudy_rainshaft_rhs).
+JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, bool rhs_only) {
+    if (!plan->jit_on || nz < 1 || nz > 1024) return JIT_UNITS;
+    const JitUnit pref = jit_rainshaft_part(plan->h, nz, n_columns);
+    bool reached = false;
+    for (JitUnit u : {JIT_COL1024, JIT_COL512, JIT_COL256}) {
+        reached = reached || u == pref;
+        if (reached && jit_rainshaft_fits(plan->h, u, nz) && jit_unit(plan, u).fn[rhs_only ? K_COL_RHS : 0] != nullptr) return u;
+    }
+    return JIT_UNITS;
+}
+
+// Which unit compiled for the plan serves this call (JIT_UNITS: none -- the ahead-of-time kernels, or the diagnostics below)
+JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     const HostPlan &h = plan->h;
+    if (!plan->jit_on || r.input_kind != IN_MOMENTS || !r.physical_out) return JIT_UNITS;
+    switch (r.op) {
+    case OP_COAL: return r.rainshaft ? JIT_CELL : JIT_MAIN;
+    case OP_SSPRK33:
+        if (r.rainshaft) return JIT_UNITS;
+        return h.mode == MODE_ALLINF && h.coal_style != CLOUDY_NUMERICAL_COAL ? JIT_MAIN : JIT_INTEGRATOR;
+    case OP_TSIT5: return JIT_TSIT5;
+    case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
+    default: return JIT_UNITS;
+    }
+}
+
+// a call served by unit u of the plan (serving_unit): same grids and the same two-parcels-per-lane alignment rule as launch_io()
+// in launch_impl.hpp
+hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
+    const HostPlan &h = plan->h;
+    const hipFunction_t *fn = jit_unit(plan, u).fn;
     size_t n = r.n, ld = r.ld;
     const void *in = r.in;
     void *out = r.out;
@@ -238,13 +210,10 @@ hipError_t launch_jit(const cloudy_plan *plan, const LaunchReq &r) {
         int nz = (int)r.nz, n_steps = r.n_steps;
         size_t n_columns = r.n / r.nz;
         double dt = r.dt, dz = r.dz;
-        const RsPick pk = pick_rainshaft(plan, r.nz, r.n / r.nz, false);   // (as run() decided: compiled by then)
-        if (pk.fn == nullptr) return hipErrorInvalidValue;
-        const unsigned bs = (unsigned)pk.bs;
-        hipFunction_t fn = pk.fn;
+        const unsigned bs = (unsigned)jit_rainshaft_block(u);
         const size_t cpb = bs / r.nz;
         void *args[] = {&nodes, &nz, &n_columns, &ld, &in, &out, &dt, &dz, &n_steps};
-        return hipModuleLaunchKernel(fn, (unsigned)((n_columns + cpb - 1) / cpb), 1, 1, bs, 1, 1, 0, r.stream, args, nullptr);
+        return hipModuleLaunchKernel(fn[0], (unsigned)((n_columns + cpb - 1) / cpb), 1, 1, bs, 1, 1, 0, r.stream, args, nullptr);
     }
     if (r.op == OP_TSIT5) {
         double dt = r.dt;
@@ -253,11 +222,11 @@ hipError_t launch_jit(const cloudy_plan *plan, const LaunchReq &r) {
             const unsigned qb = h.q.mode == QUAD_CONVERGED ? (unsigned)jit_conv_block_size(h) : (unsigned)quad_block(h.q.nq);
             ConvHints hints = h.q.mode == QUAD_CONVERGED ? conv_hints(plan, n, r.stream) : ConvHints{};
             void *args[] = {&n, &ld, &in, &out, &dt, &n_steps, &hints.p1, &hints.p2};
-            return hipModuleLaunchKernel(plan->int_tsit5, (unsigned)((n + qb - 1) / qb), 1, 1, qb, 1, 1, 0, r.stream, args, nullptr);
+            return hipModuleLaunchKernel(fn[0], (unsigned)((n + qb - 1) / qb), 1, 1, qb, 1, 1, 0, r.stream, args, nullptr);
         }
         const double *nodes = h.nodes_dev;
         void *args[] = {&nodes, &n, &ld, &in, &out, &dt, &n_steps};
-        return hipModuleLaunchKernel(plan->int_tsit5, g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+        return hipModuleLaunchKernel(fn[0], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
     }
     if (h.coal_style == CLOUDY_NUMERICAL_COAL) {
         const unsigned qb = h.q.mode == QUAD_CONVERGED ? (unsigned)jit_conv_block_size(h) : (unsigned)quad_block(h.q.nq);
@@ -266,14 +235,12 @@ hipError_t launch_jit(const cloudy_plan *plan, const LaunchReq &r) {
             int n_steps = r.n_steps;
             ConvHints hints = h.q.mode == QUAD_CONVERGED ? conv_hints(plan, n, r.stream) : ConvHints{};
             void *args[] = {&n, &ld, &in, &out, &dt, &n_steps, &hints.p1, &hints.p2};
-            return hipModuleLaunchKernel(plan->int_ssprk33, (unsigned)((n + qb - 1) / qb), 1, 1, qb, 1, 1, 0, r.stream, args,
-                                         nullptr);
+            return hipModuleLaunchKernel(fn[0], (unsigned)((n + qb - 1) / qb), 1, 1, qb, 1, 1, 0, r.stream, args, nullptr);
         }
         ConvHints hints = h.q.mode == QUAD_CONVERGED ? conv_hints(plan, n, r.stream) : ConvHints{};
         void *args[] = {&n, &ld, &in, &out, &hints.p1, &hints.p2};
         const size_t per_wg = (size_t)qb * (size_t)(h.q.mode == QUAD_CONVERGED ? h.jit_conv_rounds : 1);
-        return hipModuleLaunchKernel(plan->jit.quad, (unsigned)((n + per_wg - 1) / per_wg), 1, 1, qb, 1, 1, 0, r.stream, args,
-                                     nullptr);
+        return hipModuleLaunchKernel(fn[0], (unsigned)((n + per_wg - 1) / per_wg), 1, 1, qb, 1, 1, 0, r.stream, args, nullptr);
     }
     if (r.op == OP_SSPRK33) {
         double dt = r.dt;
@@ -282,42 +249,40 @@ hipError_t launch_jit(const cloudy_plan *plan, const LaunchReq &r) {
             const double *nodes = h.nodes_dev;
             void *args[] = {&nodes, &n, &ld, &in, &out, &dt, &n_steps};
             const unsigned bs = (unsigned)jit_sorted_block_size(h);
-            return hipModuleLaunchKernel(plan->int_ssprk33, (unsigned)((n + bs - 1) / bs), 1, 1, bs, 1, 1, 0, r.stream, args,
-                                         nullptr);
+            return hipModuleLaunchKernel(fn[0], (unsigned)((n + bs - 1) / bs), 1, 1, bs, 1, 1, 0, r.stream, args, nullptr);
         }
         void *args[] = {&n, &ld, &in, &out, &dt, &n_steps};
-        return hipModuleLaunchKernel(plan->jit.ssprk33, g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+        return hipModuleLaunchKernel(fn[K_SSPRK33], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
     }
     void *out2 = r.out2;  // rainshaft cell body: the sedimentation flux planes (cloudy_rainshaft_sources), or null
     if (h.mode != MODE_ALLINF) {
         const double *nodes = h.nodes_dev;
-        void *args[] = {&nodes, &n, &ld, &in, &out, &out2};  // (the plain kernel takes the first five)
+        void *args[] = {&nodes, &n, &ld, &in, &out, &out2};  // (the main unit's kernel takes the first five)
         const unsigned bs = (unsigned)jit_sorted_block_size(h);
-        return hipModuleLaunchKernel(r.rainshaft ? plan->rs_coal : plan->jit.sorted, (unsigned)((n + bs - 1) / bs), 1, 1, bs, 1,
-                                     1, 0, r.stream, args, nullptr);
+        return hipModuleLaunchKernel(fn[0], (unsigned)((n + bs - 1) / bs), 1, 1, bs, 1, 1, 0, r.stream, args, nullptr);
     }
     if (r.rainshaft) {
         void *args[] = {&n, &ld, &in, &out, &out2};
-        return hipModuleLaunchKernel(plan->rs_coal, g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+        return hipModuleLaunchKernel(fn[0], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
     }
     const size_t esz = h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double);
     const uintptr_t amask = 2 * esz - 1;
     const bool aligned2 =
         ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & amask) == 0 && (ld % 2 == 0);
     void *args[] = {&n, &ld, &in, &out};
-    if (plan->jit.allinf4_f32 && !h.force_ppl1) {
+    if (fn[K_ALLINF4] && !h.force_ppl1) {
         // CLOUDY_F32_FAST without thresholds: the packed single-precision kernel for EVERY layout (16-B accesses where the
         // planes allow them, scalar ones otherwise): the arithmetic is a property of the plan, not of the batch's alignment
         int aligned16 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
         void *args4[] = {&n, &ld, &in, &out, &aligned16};
         const unsigned g4 = (unsigned)(((n + 3) / 4 + kBlock - 1) / kBlock);
-        return hipModuleLaunchKernel(plan->jit.allinf4_f32, g4, 1, 1, kBlock, 1, 1, 0, r.stream, args4, nullptr);
+        return hipModuleLaunchKernel(fn[K_ALLINF4], g4, 1, 1, kBlock, 1, 1, 0, r.stream, args4, nullptr);
     }
     if (aligned2 && !h.force_ppl1) {
         const unsigned g2 = (unsigned)(((n + 1) / 2 + kBlock - 1) / kBlock);
-        return hipModuleLaunchKernel(plan->jit.allinf2, g2, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+        return hipModuleLaunchKernel(fn[0], g2, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
     }
-    return hipModuleLaunchKernel(plan->jit.ppl1, g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+    return hipModuleLaunchKernel(fn[K_PPL1], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
 }
 
 // the diagnostics of a plan beyond the ahead-of-time families: argument lists as the kernels of launch_impl.hpp take them,
@@ -329,6 +294,7 @@ hipError_t launch_diag(const cloudy_plan *plan, const LaunchReq &r) {
     void *out = r.out, *out2 = r.out2;
     const double *nodes = h.nodes_dev;
     const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
+    const hipFunction_t *fns = jit_unit(plan, JIT_DIAG).fn;
     hipFunction_t fn = nullptr;
     void *args[8];
     int na = 0;
@@ -336,29 +302,29 @@ hipError_t launch_diag(const cloudy_plan *plan, const LaunchReq &r) {
     const double *s_dev = r.s_dev;
     switch (r.op) {
     case OP_UPDATE_DIST:
-        fn = plan->diag.update_dist;
+        fn = fns[K_UPDATE_DIST];
         args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
         break;
     case OP_FINITE_2D:
-        fn = plan->diag.finite_2d;
+        fn = fns[K_FINITE_2D];
         args[na++] = &nodes, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out, args[na++] = &out2;
         break;
     case OP_SEDI:
-        fn = plan->diag.sedi_flux;
+        fn = fns[K_SEDI_FLUX];
         args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
         break;
     case OP_COND:
-        fn = plan->diag.cond_evap;
+        fn = fns[K_COND_EVAP];
         d0 = r.coef, d1 = r.s_scalar;
         args[na++] = &d0, args[na++] = &d1, args[na++] = &s_dev, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
         break;
     case OP_NQ:
-        fn = plan->diag.standard_nq;
+        fn = fns[K_STANDARD_NQ];
         d0 = r.s_scalar / h.norms[1], d1 = h.norms[0], d2 = h.norms[1];
         args[na++] = &d0, args[na++] = &d1, args[na++] = &d2, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
         break;
     case OP_COAL:
-        fn = plan->diag.coal_ints;
+        fn = fns[K_COAL_INTS];
         args[na++] = &nodes, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
         break;
     default: return hipErrorInvalidValue;
@@ -375,51 +341,34 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
     if (r.n == 0) return CLOUDY_OK;
     DeviceGuard guard(plan->h.device);
     if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-    bool use_jit = plan->jit_on && r.input_kind == IN_MOMENTS && r.physical_out &&
-                   (r.op == OP_COAL || (r.op == OP_SSPRK33 && !r.rainshaft) || r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_TSIT5);
-    if (use_jit && r.op == OP_TSIT5) {
-        std::call_once(plan->tsit5_once, [&] { (void)jit_get_tsit5(plan->h, plan->int_tsit5, plan->tsit5_log); });
-        use_jit = plan->int_tsit5 != nullptr;  // otherwise the ahead-of-time integrator (tensor plans)
-    }
-    if (!use_jit && r.op == OP_TSIT5 && plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
-        return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_steps of a NumericalCoalStyle plan runs the kernel compiled for the plan "
-                                         "(hiprtc); plan-time compilation is off or failed: %s", plan->tsit5_log.c_str());
-    if (use_jit && r.op == OP_RAINSHAFT_SSPRK33)   // otherwise the ahead-of-time integrator (nz <= 256, the ahead-of-time families)
-        use_jit = plan->h.mode != MODE_MOVING && pick_rainshaft(plan, r.nz, r.n / r.nz, false).fn != nullptr;
-    if (!use_jit && r.op == OP_RAINSHAFT_SSPRK33 && r.nz > (size_t)kRainshaftBlock)
-        return fail(CLOUDY_EUNSUPPORTED, "columns of %zu cells run the column integrator compiled for the plan (hiprtc, up to 1024 "
-                                         "cells); plan-time compilation is off or failed: %s", r.nz,
-                    (r.nz <= 512 ? plan->rsint512_log : plan->rsint1024_log).c_str());
-    if (use_jit && r.op == OP_COAL && r.rainshaft) {
-        std::call_once(plan->rs_once, [&] { (void)jit_get_rainshaft(plan->h, plan->rs_coal, plan->rs_log); });
-        use_jit = plan->rs_coal != nullptr;
-    }
-    if (use_jit && r.op == OP_SSPRK33 && (plan->h.mode != MODE_ALLINF || plan->h.coal_style == CLOUDY_NUMERICAL_COAL)) {
-        std::call_once(plan->int_once,
-                       [&] { (void)jit_get_integrator(plan->h, plan->int_ssprk33, plan->int_log); });
-        use_jit = plan->int_ssprk33 != nullptr;  // otherwise the ahead-of-time integrator
-    }
-    if (use_jit) {
-        hipError_t e = launch_jit(plan, r);
+    const JitUnit u = serving_unit(plan, r);
+    if (u != JIT_UNITS && jit_unit(plan, u).ok) {
+        hipError_t e = launch_jit(plan, u, r);
         if (e != hipSuccess) return fail_hip(e, "specialised kernel launch");
         return CLOUDY_OK;
     }
+    // otherwise the ahead-of-time kernels, where they exist
+    if (r.op == OP_TSIT5 && plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_steps of a NumericalCoalStyle plan runs the kernel compiled for the plan "
+                                         "(hiprtc); plan-time compilation is off or failed: %s", jit_unit(plan, JIT_TSIT5).log.c_str());
+    if (r.op == OP_RAINSHAFT_SSPRK33 && r.nz > (size_t)kRainshaftBlock)
+        return fail(CLOUDY_EUNSUPPORTED, "columns of %zu cells run the column integrator compiled for the plan (hiprtc, up to 1024 "
+                                         "cells); plan-time compilation is off or failed: %s", r.nz,
+                    jit_unit(plan, r.nz <= 512 ? JIT_COL512 : JIT_COL1024).log.c_str());
     if (plan_beyond_aot(plan->h)) {
         // no ahead-of-time kernel exists for this (N, P): the diagnostics and the parameter-plane entry points run the
-        // bodies of their ahead-of-time kernels compiled for the plan (jit.hpp part 7, on first use)
+        // bodies of their ahead-of-time kernels compiled for the plan (the diagnostics unit, on first use)
         const bool diag_op = !r.rainshaft && (r.op == OP_UPDATE_DIST || r.op == OP_FINITE_2D || r.op == OP_SEDI || r.op == OP_COND ||
                                               r.op == OP_NQ || (r.op == OP_COAL && r.input_kind == IN_PARAMS));
-        if (diag_op && plan->jit_on) {
-            std::call_once(plan->diag_once, [&] { (void)jit_get_diag(plan->h, plan->diag, plan->diag_log); });
-            if (plan->diag.ok) {
-                hipError_t e = launch_diag(plan, r);
-                if (e != hipSuccess) return fail_hip(e, "diagnostic kernel launch");
-                return CLOUDY_OK;
-            }
+        const JitSlot *diag = diag_op ? &jit_unit(plan, JIT_DIAG) : nullptr;
+        if (diag && diag->ok) {
+            hipError_t e = launch_diag(plan, r);
+            if (e != hipSuccess) return fail_hip(e, "diagnostic kernel launch");
+            return CLOUDY_OK;
         }
         return fail(CLOUDY_EUNSUPPORTED, "plans of more than %d modes or order > %d are served by the kernels compiled for the plan "
                                          "(this call has none, or its compilation failed: %s)",
-                    CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, plan->diag_log.c_str());
+                    CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, diag ? diag->log.c_str() : "");
     }
     hipError_t e = dispatch(plan->h, r);
     if (e != hipSuccess) return fail_hip(e, "kernel launch");
@@ -789,23 +738,19 @@ int cloudy_plan_create(const cloudy_plan_desc *d, cloudy_plan **out) {
     }
     // plan-time specialisation (jit.hpp): 0 = when available, 1 = required, -1 = off
     const char *env = std::getenv("CLOUDY_HIP_JIT");
-    const bool env_off = env && env[0] == '0';
-    // every (threshold mode, plane type) combination of cloudy_coal_rhs has a specialised kernel
-    if (d->specialize >= 0 && !(env_off && d->specialize == 0)) {
-        p->jit_on = jit_get(h, p->jit, p->jit_log);
-        if (!p->jit_on && (d->specialize > 0 || plan_beyond_aot(h))) {
-            int rc = fail(CLOUDY_EUNSUPPORTED, "plan-time specialisation failed: %.400s", p->jit_log.c_str());
-            cloudy_plan_destroy(p);
-            return rc;
-        }
-    } else {
-        p->jit_log = "switched off (desc.specialize < 0 or CLOUDY_HIP_JIT=0)";
-        if (plan_beyond_aot(h)) {
-            int rc = fail(CLOUDY_EUNSUPPORTED, "plans of more than %d modes or order > %d need plan-time compilation, which is %s",
-                          CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, p->jit_log.c_str());
-            cloudy_plan_destroy(p);
-            return rc;
-        }
+    const bool on = d->specialize >= 0 && !(env && env[0] == '0' && d->specialize == 0);
+    JitSlot &m = p->jit[JIT_MAIN];
+    std::call_once(m.once, [&] {
+        if (on) m.ok = jit_load(h, JIT_MAIN, m);
+        else m.log = "switched off (desc.specialize < 0 or CLOUDY_HIP_JIT=0)";
+    });
+    p->jit_on = m.ok;
+    if (!p->jit_on && (d->specialize > 0 || plan_beyond_aot(h))) {
+        const int rc = on ? fail(CLOUDY_EUNSUPPORTED, "plan-time specialisation failed: %.400s", m.log.c_str())
+                          : fail(CLOUDY_EUNSUPPORTED, "plans of more than %d modes or order > %d need plan-time compilation, which is %s",
+                                 CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, m.log.c_str());
+        cloudy_plan_destroy(p);
+        return rc;
     }
     *out = p;
     return CLOUDY_OK;
@@ -816,45 +761,32 @@ int cloudy_plan_specialized(const cloudy_plan *plan) {
     return plan->jit_on ? 1 : 0;
 }
 
-const char *cloudy_plan_jit_log(const cloudy_plan *plan) { return plan ? plan->jit_log.c_str() : "plan is NULL"; }
+const char *cloudy_plan_jit_log(const cloudy_plan *plan) { return plan ? plan->jit[JIT_MAIN].log.c_str() : "plan is NULL"; }
 
 int cloudy_jit_selfcheck(const cloudy_plan_desc *d, const char *arch) {
     cloudy_plan *p = nullptr;
     std::vector<double> nodes;
     int rc = build_host_plan(d, &p, nodes);
     if (rc != CLOUDY_OK) return rc;
-    std::string log;
-    std::vector<char> code;
+    // the units the runtime could request for the plan, with their compile options.  "source-only" (tests/test_host_sanitizers.py:
+    // the string assembly of an N = 8 / P = 8 plan without the minutes of hiprtc its kernels take) compiles nothing.  Either way
+    // every kernel the loader requires must be defined in its unit's text: on the GPU a missing one would leave the plan on
+    // slower kernels.
     const std::string a = (arch && *arch) ? arch : "gfx950";
-    const bool numerical = p->h.coal_style == CLOUDY_NUMERICAL_COAL;
-    if (a == "source-only") {
-        // (tests/test_host_sanitizers.py: the string assembly of EVERY translation-unit part of the plan, nothing compiled -- the
-        // host code an N = 8 / P = 8 plan exercises, without the minutes of hiprtc its kernels take)
-        size_t bytes = 0;
-        for (int part : {0, 1, 2, 3, 4, 5, 6, 7, 8}) {
-            if (numerical && (part == 2 || part == 3 || part == 5 || part == 6 || part == 8)) continue;   // no column kernels
-            bytes += jit_source(p->h, part).size();
-        }
-        delete p;
-        return bytes > 0 ? CLOUDY_OK : fail(CLOUDY_EUNSUPPORTED, "no source generated");
+    for (int i = 0; i < JIT_UNITS && rc == CLOUDY_OK; ++i) {
+        const JitUnit u = (JitUnit)i;
+        const JitUnitDesc ud = jit_unit_desc(p->h, u);
+        if (!ud.exists) continue;
+        for (const JitKernel &k : ud.kernels)
+            if (rc == CLOUDY_OK && !k.optional && !k.name.empty() && ud.src.find(" " + k.name + "(") == std::string::npos)
+                rc = fail(CLOUDY_EUNSUPPORTED, "plan-time %s unit: kernel %s is not defined in its source", jit_unit_name(u), k.name.c_str());
+        std::string log;
+        std::vector<char> code;
+        if (rc == CLOUDY_OK && a != "source-only" && !jit_compile(ud.src, a, ud.licm_off, code, log))
+            rc = fail(CLOUDY_EUNSUPPORTED, "plan-time compilation failed: %.440s", log.c_str());
     }
-    bool ok = jit_compile(jit_source(p->h, 0), a, numerical ? jit_quad_licm_off(p->h) : p->h.mode == MODE_ALLINF, code, log);
-    if (ok && numerical) ok = jit_compile(jit_source(p->h, 1), a, true, code, log);  // fused SSPRK33 of the quadrature plan
-    if (ok && !numerical && p->h.mode != MODE_ALLINF) ok = jit_compile(jit_source(p->h, 1), a, true, code, log);
-    if (ok && !numerical) ok = jit_compile(jit_source(p->h, 2), a, false, code, log);  // rainshaft cell body
-    if (ok && !numerical && p->h.n_vel > 0 && p->h.mode != MODE_MOVING)
-    {
-        const char *l = std::getenv("CLOUDY_HIP_JIT_RS_LICM");  // (the experiment switch of jit_get_rainshaft_integrator)
-        // the fused column integrator + column RHS at every workgroup size whose LDS rows fit a workgroup (jit_rainshaft_fits: what
-        // pick_rainshaft may choose); at least one must exist for columns of up to 256 cells unless the plan is beyond them all
-        for (int part : {3, 5, 6})
-            if (ok && jit_rainshaft_fits(p->h, part, 1)) ok = jit_compile(jit_source(p->h, part), a, !(l && l[0] == '1'), code, log);
-    }
-    if (ok && p->h.dtype != CLOUDY_F32_FAST) ok = jit_compile(jit_source(p->h, 4), a, true, code, log);  // cloudy_tsit5_steps
-    if (ok && plan_beyond_aot(p->h)) ok = jit_compile(jit_source(p->h, 7), a, false, code, log);  // diagnostics
     delete p;
-    if (!ok) return fail(CLOUDY_EUNSUPPORTED, "plan-time compilation failed: %.440s", log.c_str());
-    return CLOUDY_OK;
+    return rc;
 }
 
 void cloudy_plan_destroy(cloudy_plan *plan) {
@@ -1105,12 +1037,9 @@ int cloudy_rainshaft_sources(const cloudy_plan *plan, size_t n, size_t ld, const
                  (hipStream_t)stream};
     // The cell-body kernel compiled for the plan writes the sedimentation flux as well (one launch, one read of the
     // moments, one closure inversion); the ahead-of-time path is two launches.
-    if (plan->jit_on && n > 0) {
-        std::call_once(plan->rs_once, [&] { (void)jit_get_rainshaft(plan->h, plan->rs_coal, plan->rs_log); });
-        if (plan->rs_coal != nullptr) {
-            r1.out2 = sedi_flux_dev;
-            return run(plan, r1);
-        }
+    if (n > 0 && jit_unit(plan, JIT_CELL).ok) {
+        r1.out2 = sedi_flux_dev;
+        return run(plan, r1);
     }
     rc = run(plan, r1);
     if (rc) return rc;
@@ -1139,14 +1068,14 @@ int cloudy_rainshaft_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, s
         if (!(fe && fe[0] == '0')) {
             DeviceGuard guard(plan->h.device);
             if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-            const RsPick pk = pick_rainshaft(plan, nz, n_columns, true);
-            if (pk.fn != nullptr) {
+            const JitUnit u = pick_rainshaft(plan, nz, n_columns, true);
+            if (u != JIT_UNITS) {
                 const double *nodes = plan->h.nodes_dev;
                 int nzi = (int)nz;
-                const unsigned bs = (unsigned)pk.bs;
+                const unsigned bs = (unsigned)jit_rainshaft_block(u);
                 const size_t cpb = bs / nz;
                 void *args[] = {&nodes, &nzi, &n_columns, &ld, &mom_dev, &rhs_dev, &flux_work_dev, &dz};
-                hipError_t e = hipModuleLaunchKernel(pk.fn, (unsigned)((n_columns + cpb - 1) / cpb), 1, 1, bs, 1, 1, 0, (hipStream_t)stream,
+                hipError_t e = hipModuleLaunchKernel(jit_unit(plan, u).fn[K_COL_RHS], (unsigned)((n_columns + cpb - 1) / cpb), 1, 1, bs, 1, 1, 0, (hipStream_t)stream,
                                                      args, nullptr);
                 if (e != hipSuccess) return fail_hip(e, "column right-hand side launch");
                 return CLOUDY_OK;
@@ -1188,14 +1117,17 @@ int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_
         if (!aot) {
             DeviceGuard guard(plan->h.device);
             if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-            staged = plan->h.mode == MODE_MOVING || pick_rainshaft(plan, nz, n_columns, false).fn == nullptr;
+            staged = plan->h.mode == MODE_MOVING || pick_rainshaft(plan, nz, n_columns, false) == JIT_UNITS;
         }
     }
     if (staged) {
         // Round 5 (VERDICT r4 missing #4): the reference's cell loop is unbounded in nz (rainshaft_helpers.jl:55-78), the fused
         // kernel keeps a column inside one workgroup (<= 1024 cells).  Taller columns are stepped stage by stage on the stream:
         // cloudy_rainshaft_rhs (cell sources + flux divergence: two launches) and one update launch per stage, with three
-        // stream-ordered scratch arrays of the state's size (allocated and released on the caller's stream per call).
+        // scratch arrays of the state's size per call.  They are a plain allocation, freed when the steps are done: taken from the
+        // stream-ordered pool (hipMallocAsync / hipFreeAsync) about one call in five came back wrong on a box (garbage in ~1000
+        // of 13500 values of the 5-mode, 300-cell case of test_column_integrator_picks_a_workgroup_size_whose_lds_fits), as
+        // cloudy_closure_stats' rows did.
         //
         // Experiment switch CLOUDY_HIP_GRAPH=1 (round 5, measured SLOWER on ROCm 7.2 and therefore off): from the second step on
         // ONE step -- nine launches -- is captured into a hipGraph and replayed.  The first step runs eagerly (it builds whatever
@@ -1235,7 +1167,7 @@ int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_
         hipError_t e = hipSuccess;
         if (u_out_dev != u_in_dev) e = hipMemcpyAsync(u_out_dev, u_in_dev, bytes, hipMemcpyDeviceToDevice, st);
         char *ws = nullptr;
-        if (e == hipSuccess) e = hipMallocAsync((void **)&ws, 3 * bytes, st);
+        if (e == hipSuccess) e = hipMalloc((void **)&ws, 3 * bytes);
         if (e != hipSuccess) {
             release();
             return fail_hip(e, "scratch of the stage-by-stage column integrator");
@@ -1283,7 +1215,7 @@ int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_
         }
         for (; step < n_steps && rc == CLOUDY_OK && e == hipSuccess; ++step) one_step();
         if (rc == CLOUDY_OK && e == hipSuccess && n_steps > 0) e = stage(3);
-        (void)hipFreeAsync(ws, st);
+        (void)hipFree(ws);   // (waits for the steps)
         if (own != nullptr) {   // the caller's stream goes on after this call's work
             hipError_t eo = hipEventRecord(ev_out, own);
             if (eo == hipSuccess) eo = hipStreamWaitEvent(user, ev_out, 0);

@@ -399,7 +399,7 @@ def test_plans_beyond_the_ahead_of_time_families(gpu_cloudy, oracle, dist_types,
     print(f"dt = {dt:.2e}: fused SSPRK33 vs three RHS calls {r3:.1e}, Tsit5 vs SSPRK33 {r5:.1e} (of max(|u|, dt scale))")
     assert r3 <= 1e-12 and r5 <= 1e-6
     # ---- the diagnostics and the parameter-plane entry points of such a plan: the bodies of the ahead-of-time kernels compiled
-    # for the plan on first use (jit.hpp part 7)
+    # for the plan on first use (jit.hpp: the JIT_DIAG unit)
     prm_d = cloudy.update_dist_from_moments(plan, u0)
     prm, prm_o = prm_d.to_numpy(), oracle.update_dist_batch(op, mom)
     assert np.allclose(prm[:, regular], prm_o[:, regular], rtol=1e-14, atol=0)
