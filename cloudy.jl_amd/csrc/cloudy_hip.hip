@@ -122,10 +122,10 @@ constexpr int kSumBlocks = 1024;
 hipError_t dispatch(const HostPlan &h, const LaunchReq &r) {
     using Fn = hipError_t (*)(const HostPlan &, const LaunchReq &);
     static const Fn table[CLOUDY_AOT_MAX_MODES][CLOUDY_AOT_MAX_P] = {
-        {launch_n1_p1, launch_n1_p2, launch_n1_p3, launch_n1_p4, launch_n1_p5},
-        {launch_n2_p1, launch_n2_p2, launch_n2_p3, launch_n2_p4, launch_n2_p5},
-        {launch_n3_p1, launch_n3_p2, launch_n3_p3, launch_n3_p4, launch_n3_p5},
-        {launch_n4_p1, launch_n4_p2, launch_n4_p3, launch_n4_p4, launch_n4_p5}};
+        {launch_np<1, 1>, launch_np<1, 2>, launch_np<1, 3>, launch_np<1, 4>, launch_np<1, 5>},
+        {launch_np<2, 1>, launch_np<2, 2>, launch_np<2, 3>, launch_np<2, 4>, launch_np<2, 5>},
+        {launch_np<3, 1>, launch_np<3, 2>, launch_np<3, 3>, launch_np<3, 4>, launch_np<3, 5>},
+        {launch_np<4, 1>, launch_np<4, 2>, launch_np<4, 3>, launch_np<4, 4>, launch_np<4, 5>}};
     if (h.N < 1 || h.N > CLOUDY_AOT_MAX_MODES || h.P < 1 || h.P > CLOUDY_AOT_MAX_P) return hipErrorInvalidValue;
     if (h.coal_style == CLOUDY_NUMERICAL_COAL && (r.op == OP_COAL || r.op == OP_SSPRK33)) {
         static const Fn quad[CLOUDY_AOT_MAX_MODES] = {launch_quad_n1, launch_quad_n2, launch_quad_n3, launch_quad_n4};
@@ -181,6 +181,16 @@ JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, boo
     return JIT_UNITS;
 }
 
+// Whether cloudy_rainshaft_ssprk33_steps steps the columns stage by stage (rainshaft_staged_steps) because no fused integrator
+// holds them: taller than a workgroup, or (round 6) a plan whose LDS rows leave no workgroup size that holds a column
+// (5+ modes with a threshold beyond 256 cells, ...) and that the ahead-of-time integrator (<= 256 cells, <= CLOUDY_AOT_MAX_MODES
+// modes) does not serve either.  Loads the column units on first use.
+bool rainshaft_staged(const cloudy_plan *plan, size_t nz, size_t n_columns) {
+    if (nz > 1024) return true;
+    if (nz <= (size_t)kRainshaftBlock && !plan_beyond_aot(plan->h)) return false;
+    return plan->h.mode == MODE_MOVING || pick_rainshaft(plan, nz, n_columns, false) == JIT_UNITS;
+}
+
 // Which unit compiled for the plan serves this call (JIT_UNITS: none -- the ahead-of-time kernels, or the diagnostics below)
 JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     const HostPlan &h = plan->h;
@@ -192,97 +202,74 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
         return h.mode == MODE_ALLINF && h.coal_style != CLOUDY_NUMERICAL_COAL ? JIT_MAIN : JIT_INTEGRATOR;
     case OP_TSIT5: return JIT_TSIT5;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
+    case OP_RAINSHAFT_RHS: {  // CLOUDY_HIP_RS_FUSED_RHS=0 (read per call): sources + divergence (rainshaft_rhs_unfused)
+        const char *e = std::getenv("CLOUDY_HIP_RS_FUSED_RHS");
+        return h.mode == MODE_MOVING || (e && e[0] == '0') ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, true);
+    }
     default: return JIT_UNITS;
     }
 }
 
-// a call served by unit u of the plan (serving_unit): same grids and the same two-parcels-per-lane alignment rule as launch_io()
-// in launch_impl.hpp
-hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
-    const HostPlan &h = plan->h;
-    const hipFunction_t *fn = jit_unit(plan, u).fn;
-    size_t n = r.n, ld = r.ld;
-    const void *in = r.in;
-    void *out = r.out;
-    const unsigned g1 = (unsigned)((n + kBlock - 1) / kBlock);
-    if (r.op == OP_RAINSHAFT_SSPRK33) {  // as launch_int_io() in launch_int_impl.hpp: whole columns per workgroup
-        const double *nodes = h.nodes_dev;
-        int nz = (int)r.nz, n_steps = r.n_steps;
-        size_t n_columns = r.n / r.nz;
-        double dt = r.dt, dz = r.dz;
+// How a call served by unit u of the plan (serving_unit) launches: which of the unit's kernels (K_*), its workgroup size and the
+// parcels (cells) one workgroup takes
+struct JitShape {
+    int k = 0;
+    unsigned block = kBlock;
+    size_t per_wg = kBlock;
+};
+JitShape jit_shape(const HostPlan &h, JitUnit u, const LaunchReq &r) {
+    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS) {  // whole columns per workgroup, as launch_int_io()
         const unsigned bs = (unsigned)jit_rainshaft_block(u);
-        const size_t cpb = bs / r.nz;
-        void *args[] = {&nodes, &nz, &n_columns, &ld, &in, &out, &dt, &dz, &n_steps};
-        return hipModuleLaunchKernel(fn[0], (unsigned)((n_columns + cpb - 1) / cpb), 1, 1, bs, 1, 1, 0, r.stream, args, nullptr);
-    }
-    if (r.op == OP_TSIT5) {
-        double dt = r.dt;
-        int n_steps = r.n_steps;
-        if (h.coal_style == CLOUDY_NUMERICAL_COAL) {
-            const unsigned qb = h.q.mode == QUAD_CONVERGED ? (unsigned)jit_conv_block_size(h) : (unsigned)quad_block(h.q.nq);
-            ConvHints hints = h.q.mode == QUAD_CONVERGED ? conv_hints(plan, n, r.stream) : ConvHints{};
-            void *args[] = {&n, &ld, &in, &out, &dt, &n_steps, &hints.p1, &hints.p2};
-            return hipModuleLaunchKernel(fn[0], (unsigned)((n + qb - 1) / qb), 1, 1, qb, 1, 1, 0, r.stream, args, nullptr);
-        }
-        const double *nodes = h.nodes_dev;
-        void *args[] = {&nodes, &n, &ld, &in, &out, &dt, &n_steps};
-        return hipModuleLaunchKernel(fn[0], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+        return {r.op == OP_RAINSHAFT_RHS ? K_COL_RHS : 0, bs, bs / r.nz * r.nz};
     }
     if (h.coal_style == CLOUDY_NUMERICAL_COAL) {
-        const unsigned qb = h.q.mode == QUAD_CONVERGED ? (unsigned)jit_conv_block_size(h) : (unsigned)quad_block(h.q.nq);
-        if (r.op == OP_SSPRK33) {
-            double dt = r.dt;
-            int n_steps = r.n_steps;
-            ConvHints hints = h.q.mode == QUAD_CONVERGED ? conv_hints(plan, n, r.stream) : ConvHints{};
-            void *args[] = {&n, &ld, &in, &out, &dt, &n_steps, &hints.p1, &hints.p2};
-            return hipModuleLaunchKernel(fn[0], (unsigned)((n + qb - 1) / qb), 1, 1, qb, 1, 1, 0, r.stream, args, nullptr);
-        }
-        ConvHints hints = h.q.mode == QUAD_CONVERGED ? conv_hints(plan, n, r.stream) : ConvHints{};
-        void *args[] = {&n, &ld, &in, &out, &hints.p1, &hints.p2};
-        const size_t per_wg = (size_t)qb * (size_t)(h.q.mode == QUAD_CONVERGED ? h.jit_conv_rounds : 1);
-        return hipModuleLaunchKernel(fn[0], (unsigned)((n + per_wg - 1) / per_wg), 1, 1, qb, 1, 1, 0, r.stream, args, nullptr);
+        const bool conv = h.q.mode == QUAD_CONVERGED;
+        const unsigned qb = conv ? (unsigned)jit_conv_block_size(h) : (unsigned)quad_block(h.q.nq);
+        return {0, qb, (size_t)qb * (r.op == OP_COAL && conv ? h.jit_conv_rounds : 1)};
     }
-    if (r.op == OP_SSPRK33) {
-        double dt = r.dt;
-        int n_steps = r.n_steps;
-        if (h.mode != MODE_ALLINF) {
-            const double *nodes = h.nodes_dev;
-            void *args[] = {&nodes, &n, &ld, &in, &out, &dt, &n_steps};
-            const unsigned bs = (unsigned)jit_sorted_block_size(h);
-            return hipModuleLaunchKernel(fn[0], (unsigned)((n + bs - 1) / bs), 1, 1, bs, 1, 1, 0, r.stream, args, nullptr);
-        }
-        void *args[] = {&n, &ld, &in, &out, &dt, &n_steps};
-        return hipModuleLaunchKernel(fn[K_SSPRK33], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
-    }
-    void *out2 = r.out2;  // rainshaft cell body: the sedimentation flux planes (cloudy_rainshaft_sources), or null
-    if (h.mode != MODE_ALLINF) {
-        const double *nodes = h.nodes_dev;
-        void *args[] = {&nodes, &n, &ld, &in, &out, &out2};  // (the main unit's kernel takes the first five)
+    if (h.mode != MODE_ALLINF && r.op != OP_TSIT5) {  // the threshold kernels: RHS, cell body, SSPRK33 integrator
         const unsigned bs = (unsigned)jit_sorted_block_size(h);
-        return hipModuleLaunchKernel(fn[0], (unsigned)((n + bs - 1) / bs), 1, 1, bs, 1, 1, 0, r.stream, args, nullptr);
+        return {0, bs, bs};
     }
-    if (r.rainshaft) {
-        void *args[] = {&n, &ld, &in, &out, &out2};
-        return hipModuleLaunchKernel(fn[0], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
-    }
+    if (r.op == OP_TSIT5 || r.rainshaft) return {};
+    if (r.op == OP_SSPRK33) return {K_SSPRK33};
     const size_t esz = h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double);
-    const uintptr_t amask = 2 * esz - 1;
-    const bool aligned2 =
-        ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & amask) == 0 && (ld % 2 == 0);
-    void *args[] = {&n, &ld, &in, &out};
-    if (fn[K_ALLINF4] && !h.force_ppl1) {
-        // CLOUDY_F32_FAST without thresholds: the packed single-precision kernel for EVERY layout (16-B accesses where the
-        // planes allow them, scalar ones otherwise): the arithmetic is a property of the plan, not of the batch's alignment
-        int aligned16 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-        void *args4[] = {&n, &ld, &in, &out, &aligned16};
-        const unsigned g4 = (unsigned)(((n + 3) / 4 + kBlock - 1) / kBlock);
-        return hipModuleLaunchKernel(fn[K_ALLINF4], g4, 1, 1, kBlock, 1, 1, 0, r.stream, args4, nullptr);
+    const int ppl = allinf_parcels_per_lane(h, r, esz, jit_allinf_f32_fast(h));
+    return {ppl == 4 ? K_ALLINF4 : ppl == 2 ? 0 : K_PPL1, kBlock, (size_t)ppl * kBlock};
+}
+
+hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
+    const HostPlan &h = plan->h;
+    const JitShape s = jit_shape(h, u, r);
+    const bool numerical = h.coal_style == CLOUDY_NUMERICAL_COAL;
+    ConvHints hints = numerical && h.q.mode == QUAD_CONVERGED ? conv_hints(plan, r.n, r.stream) : ConvHints{};
+    // the kernel's arguments in the order of its signature (jit.hpp)
+    const double *nodes = h.nodes_dev;
+    size_t n = r.n, ld = r.ld, n_columns = r.nz ? r.n / r.nz : 0;
+    const void *in = r.in;
+    void *out = r.out, *out2 = r.out2;
+    double dt = r.dt, dz = r.dz;
+    int nz = (int)r.nz, n_steps = r.n_steps;
+    int aligned16 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    void *args[9];
+    int na = 0;
+    const auto push = [&](std::initializer_list<void *> a) {
+        for (void *p : a) args[na++] = p;
+    };
+    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS) {
+        push({&nodes, &nz, &n_columns, &ld, &in, &out});
+        if (r.op == OP_RAINSHAFT_RHS) push({&out2, &dz});
+        else push({&dt, &dz, &n_steps});
+    } else {
+        if (!numerical && (h.mode != MODE_ALLINF || r.op == OP_TSIT5)) push({&nodes});
+        push({&n, &ld, &in, &out});
+        if (r.op != OP_COAL) push({&dt, &n_steps});
+        if (numerical) push({&hints.p1, &hints.p2});
+        else if (r.rainshaft) push({&out2});  // the cell body: the sedimentation flux planes, or null
+        else if (s.k == K_ALLINF4) push({&aligned16});  // 16-B accesses where the planes allow them, scalar ones otherwise
     }
-    if (aligned2 && !h.force_ppl1) {
-        const unsigned g2 = (unsigned)(((n + 1) / 2 + kBlock - 1) / kBlock);
-        return hipModuleLaunchKernel(fn[0], g2, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
-    }
-    return hipModuleLaunchKernel(fn[K_PPL1], g1, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+    return hipModuleLaunchKernel(jit_unit(plan, u).fn[s.k], (unsigned)((n + s.per_wg - 1) / s.per_wg), 1, 1, s.block, 1, 1, 0,
+                                 r.stream, args, nullptr);
 }
 
 // the diagnostics of a plan beyond the ahead-of-time families: argument lists as the kernels of launch_impl.hpp take them,
@@ -332,22 +319,93 @@ hipError_t launch_diag(const cloudy_plan *plan, const LaunchReq &r) {
     return hipModuleLaunchKernel(fn, g, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
 }
 
-int run(const cloudy_plan *plan, const LaunchReq &r) {
-    if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL &&
-        (r.op == OP_FINITE_2D || r.op == OP_RAINSHAFT_SSPRK33 || r.rainshaft))
-        return fail(CLOUDY_EUNSUPPORTED,
-                    "NumericalCoalStyle plans serve cloudy_coal_rhs / cloudy_get_coal_ints / cloudy_ssprk33_steps and the "
-                    "per-mode diagnostics; thresholds and the rainshaft body belong to AnalyticalCoalStyle plans");
-    if (r.n == 0) return CLOUDY_OK;
-    DeviceGuard guard(plan->h.device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
+int launch(const cloudy_plan *plan, const LaunchReq &r);
+
+// cloudy_rainshaft_rhs without a column unit: the cell sources into rhs and the cell fluxes into the work planes (a rainshaft
+// OP_COAL), then the flux divergence
+int rainshaft_rhs_unfused(const cloudy_plan *plan, const LaunchReq &r) {
+    LaunchReq src = r;
+    src.op = OP_COAL;
+    const int rc = launch(plan, src);
+    if (rc) return rc;
+    const unsigned g = (unsigned)((r.n + kBlock - 1) / kBlock);
+    if (plan->h.dtype != CLOUDY_F64)
+        hipLaunchKernelGGL(rainshaft_divergence_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, r.n, r.ld, plan->h.nmom, r.nz,
+                           r.dz, (const float *)r.out2, (float *)r.out);
+    else
+        hipLaunchKernelGGL(rainshaft_divergence_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, r.n, r.ld, plan->h.nmom, r.nz,
+                           r.dz, (const double *)r.out2, (double *)r.out);
+    HIP_TRY(hipGetLastError());
+    return CLOUDY_OK;
+}
+
+// Round 5 (VERDICT r4 missing #4): the reference's cell loop is unbounded in nz (rainshaft_helpers.jl:55-78), the fused kernel
+// keeps a column inside one workgroup (<= 1024 cells).  The columns rainshaft_staged() picks are stepped stage by stage on the
+// stream: the column RHS (OP_RAINSHAFT_RHS, sources + flux divergence: two launches) and one update launch per stage, with three
+// scratch arrays of the state's size per call.  They are a plain allocation, freed when the steps are done: taken from the
+// stream-ordered pool (hipMallocAsync / hipFreeAsync) about one call in five came back wrong on a box (garbage in ~1000 of 13500
+// values of the 5-mode, 300-cell case of test_column_integrator_picks_a_workgroup_size_whose_lds_fits), as cloudy_closure_stats'
+// rows did.  (Replaying one captured step as a graph was measured slower than these eager launches: DESIGN 7 (4).)
+int rainshaft_staged_steps(const cloudy_plan *plan, const LaunchReq &r) {
+    const HostPlan &h = plan->h;
+    const size_t n = r.n, ld = r.ld, bytes = (size_t)h.nmom * ld * (h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double));
+    hipError_t e = hipSuccess;
+    if (r.out != r.in) e = hipMemcpyAsync(r.out, r.in, bytes, hipMemcpyDeviceToDevice, r.stream);
+    char *ws = nullptr;
+    if (e == hipSuccess) e = hipMalloc((void **)&ws, 3 * bytes);
+    if (e != hipSuccess) return fail_hip(e, "scratch of the stage-by-stage column integrator");
+    void *up = ws, *f = ws + bytes, *flux = ws + 2 * bytes;
+    LaunchReq rhs(OP_RAINSHAFT_RHS, n, ld, r.out, f, r.stream);
+    rhs.rainshaft = 1;
+    rhs.out2 = flux;
+    rhs.nz = r.nz;
+    rhs.dz = r.dz;
+    const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
+    const int planes = h.nmom;
+    const auto stage = [&](int sidx) -> hipError_t {
+        if (h.dtype != CLOUDY_F64)
+            hipLaunchKernelGGL(rainshaft_stage_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, sidx, n, ld, planes, (float *)up,
+                               (float *)r.out, (const float *)f, r.dt);
+        else
+            hipLaunchKernelGGL(rainshaft_stage_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, sidx, n, ld, planes, (double *)up,
+                               (double *)r.out, (const double *)f, r.dt);
+        return hipGetLastError();
+    };
+    int rc = CLOUDY_OK;
+    for (int step = 0; step < r.n_steps && rc == CLOUDY_OK && e == hipSuccess; ++step)
+        for (int sidx = 0; sidx < 3 && rc == CLOUDY_OK && e == hipSuccess; ++sidx) {
+            rc = launch(plan, rhs);
+            if (rc == CLOUDY_OK) e = stage(sidx);
+        }
+    if (rc == CLOUDY_OK && e == hipSuccess && r.n_steps > 0) e = stage(3);
+    (void)hipFree(ws);   // (waits for the steps)
+    if (rc != CLOUDY_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "stage-by-stage column integrator");
+    return CLOUDY_OK;
+}
+
+// One request on the plan's device (run() selected it): the kernels compiled for the plan where a unit serves the call, the calls
+// that take several launches, then the ahead-of-time kernels where they exist
+int launch(const cloudy_plan *plan, const LaunchReq &r) {
     const JitUnit u = serving_unit(plan, r);
     if (u != JIT_UNITS && jit_unit(plan, u).ok) {
         hipError_t e = launch_jit(plan, u, r);
-        if (e != hipSuccess) return fail_hip(e, "specialised kernel launch");
+        if (e != hipSuccess) return fail_hip(e, r.op == OP_RAINSHAFT_RHS ? "column right-hand side launch" : "specialised kernel launch");
         return CLOUDY_OK;
     }
-    // otherwise the ahead-of-time kernels, where they exist
+    if (r.op == OP_RAINSHAFT_RHS) return rainshaft_rhs_unfused(plan, r);
+    if (r.op == OP_RAINSHAFT_SSPRK33 && rainshaft_staged(plan, r.nz, r.n / r.nz)) return rainshaft_staged_steps(plan, r);
+    if (r.op == OP_COAL && r.rainshaft && r.out2) {
+        // the cell sources without the cell body compiled for the plan (which writes the sedimentation flux in the same launch):
+        // the RHS, then the flux
+        LaunchReq coal = r, sedi = r;
+        coal.out2 = nullptr;
+        sedi.op = OP_SEDI;
+        sedi.out = r.out2;
+        sedi.out2 = nullptr;
+        const int rc = launch(plan, coal);
+        return rc ? rc : launch(plan, sedi);
+    }
     if (r.op == OP_TSIT5 && plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_steps of a NumericalCoalStyle plan runs the kernel compiled for the plan "
                                          "(hiprtc); plan-time compilation is off or failed: %s", jit_unit(plan, JIT_TSIT5).log.c_str());
@@ -373,6 +431,18 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
     hipError_t e = dispatch(plan->h, r);
     if (e != hipSuccess) return fail_hip(e, "kernel launch");
     return CLOUDY_OK;
+}
+
+// Every launch of a plan's kernels: the calls its coalescence style does not serve fail, the rest run on the plan's device
+int run(const cloudy_plan *plan, const LaunchReq &r) {
+    if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL && (r.op == OP_FINITE_2D || r.rainshaft))
+        return fail(CLOUDY_EUNSUPPORTED,
+                    "NumericalCoalStyle plans serve cloudy_coal_rhs / cloudy_get_coal_ints / cloudy_ssprk33_steps and the "
+                    "per-mode diagnostics; thresholds and the rainshaft body belong to AnalyticalCoalStyle plans");
+    if (r.n == 0) return CLOUDY_OK;
+    DeviceGuard guard(plan->h.device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
+    return launch(plan, r);
 }
 
 }  // namespace
@@ -729,8 +799,7 @@ int cloudy_plan_create(const cloudy_plan_desc *d, cloudy_plan **out) {
         return fail_hip(e, "workspace allocation");
     }
     if (!plan_beyond_aot(h)) {  // (the kernels compiled for the plan carry its constants as literals)
-        LaunchReq prep{OP_PREPARE, IN_MOMENTS, 1, 0, 0, 0, nullptr, &h.kargs_dev, nullptr, nullptr};
-        e = dispatch(h, prep);
+        e = dispatch(h, LaunchReq(OP_PREPARE, 0, 0, nullptr, &h.kargs_dev, nullptr));
         if (e != hipSuccess) {
             cloudy_plan_destroy(p);
             return fail_hip(e, "constant block upload");
@@ -873,17 +942,16 @@ int cloudy_plan_get(const cloudy_plan *plan, int32_t *N_mom_max, int32_t *N_2d_i
 int cloudy_coal_rhs(const cloudy_plan *plan, size_t n, size_t ld, const void *mom_dev, void *dmom_dev, void *stream) {
     int rc = check_batch(plan, n, ld, mom_dev, dmom_dev);
     if (rc) return rc;
-    LaunchReq r{OP_COAL, IN_MOMENTS, 1, 0, n, ld, mom_dev, dmom_dev, nullptr,
-                (hipStream_t)stream};
-    return run(plan, r);
+    return run(plan, LaunchReq(OP_COAL, n, ld, mom_dev, dmom_dev, stream));
 }
 
 int cloudy_get_coal_ints(const cloudy_plan *plan, size_t n, size_t ld, const void *params_dev, void *out_dev,
                          void *stream) {
     int rc = check_batch(plan, n, ld, params_dev, out_dev);
     if (rc) return rc;
-    LaunchReq r{OP_COAL, IN_PARAMS, 0, 0, n, ld, params_dev, out_dev, nullptr,
-                (hipStream_t)stream};
+    LaunchReq r(OP_COAL, n, ld, params_dev, out_dev, stream);
+    r.input_kind = IN_PARAMS;
+    r.physical_out = 0;
     return run(plan, r);
 }
 
@@ -892,8 +960,7 @@ int cloudy_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const voi
     int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
     if (rc) return rc;
     if (n_steps < 0 || !(dt == dt)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
-    LaunchReq r{OP_SSPRK33, IN_MOMENTS, 1, 0, n, ld, u_in_dev, u_out_dev, nullptr,
-                (hipStream_t)stream};
+    LaunchReq r(OP_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
     r.dt = dt;
     r.n_steps = n_steps;
     return run(plan, r);
@@ -907,7 +974,7 @@ int cloudy_tsit5_steps(const cloudy_plan *plan, size_t n, size_t ld, const void 
     if (plan->h.dtype == CLOUDY_F32_FAST)
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_steps serves CLOUDY_F64 and CLOUDY_F32 plans (the fused integrators keep "
                                          "the state in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode)");
-    LaunchReq r{OP_TSIT5, IN_MOMENTS, 1, 0, n, ld, u_in_dev, u_out_dev, nullptr, (hipStream_t)stream};
+    LaunchReq r(OP_TSIT5, n, ld, u_in_dev, u_out_dev, stream);
     r.dt = dt;
     r.n_steps = n_steps;
     return run(plan, r);
@@ -919,8 +986,8 @@ int cloudy_update_dist_from_moments(const cloudy_plan *plan, size_t n, size_t ld
     if (rc) return rc;
     if (plan->h.dtype != CLOUDY_F64)
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_update_dist_from_moments reads fp64 planes: use a CLOUDY_F64 plan");
-    LaunchReq r{OP_UPDATE_DIST, IN_MOMENTS, 0, 0, n, ld, mom_dev, params_dev, nullptr,
-                (hipStream_t)stream};
+    LaunchReq r(OP_UPDATE_DIST, n, ld, mom_dev, params_dev, stream);
+    r.physical_out = 0;
     return run(plan, r);
 }
 
@@ -978,8 +1045,9 @@ int cloudy_finite_2d_integrals(const cloudy_plan *plan, size_t n, size_t ld, con
                                void *stream) {
     int rc = check_batch(plan, n, ld, params_dev, F_dev);
     if (rc) return rc;
-    LaunchReq r{OP_FINITE_2D, IN_PARAMS, 0, 0, n, ld, params_dev, F_dev, nullptr,
-                (hipStream_t)stream};
+    LaunchReq r(OP_FINITE_2D, n, ld, params_dev, F_dev, stream);
+    r.input_kind = IN_PARAMS;
+    r.physical_out = 0;
     return run(plan, r);
 }
 
@@ -987,8 +1055,10 @@ int cloudy_compute_thresholds(const cloudy_plan *plan, size_t n, size_t ld, cons
                               void *thresholds_dev, void *stream) {
     int rc = check_batch(plan, n, ld, params_dev, thresholds_dev);
     if (rc) return rc;
-    LaunchReq r{OP_FINITE_2D, IN_PARAMS, 0, 0, n, ld, params_dev, nullptr, thresholds_dev,
-                (hipStream_t)stream};
+    LaunchReq r(OP_FINITE_2D, n, ld, params_dev, nullptr, stream);
+    r.input_kind = IN_PARAMS;
+    r.physical_out = 0;
+    r.out2 = thresholds_dev;
     return run(plan, r);
 }
 
@@ -997,16 +1067,14 @@ int cloudy_sedimentation_flux(const cloudy_plan *plan, size_t n, size_t ld, cons
     int rc = check_batch(plan, n, ld, mom_dev, flux_dev);
     if (rc) return rc;
     if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
-    LaunchReq r{OP_SEDI, IN_MOMENTS, 1, 0, n, ld, mom_dev, flux_dev, nullptr,
-                (hipStream_t)stream};
-    return run(plan, r);
+    return run(plan, LaunchReq(OP_SEDI, n, ld, mom_dev, flux_dev, stream));
 }
 
 int cloudy_cond_evap(const cloudy_plan *plan, size_t n, size_t ld, const void *mom_dev, const double *s_dev, double s,
                      double xi, void *dmom_dev, void *stream) {
     int rc = check_batch(plan, n, ld, mom_dev, dmom_dev);
     if (rc) return rc;
-    LaunchReq r{OP_COND, IN_MOMENTS, 1, 0, n, ld, mom_dev, dmom_dev, nullptr, (hipStream_t)stream};
+    LaunchReq r(OP_COND, n, ld, mom_dev, dmom_dev, stream);
     // rhs_condensation!: xi_normalized = p.xi / norms[2]^(2/3) (box_model_helpers.jl:65); rho_l = 1000 (Condensation.jl:26)
     const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
     r.coef = 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
@@ -1020,7 +1088,7 @@ int cloudy_standard_N_q(const cloudy_plan *plan, size_t n, size_t ld, const void
     int rc = check_batch(plan, n, ld, mom_dev, nq_dev);
     if (rc) return rc;
     if (!(size_cutoff > 0)) return fail(CLOUDY_EINVAL, "size_cutoff must be positive");
-    LaunchReq r{OP_NQ, IN_MOMENTS, 1, 0, n, ld, mom_dev, nq_dev, nullptr, (hipStream_t)stream};
+    LaunchReq r(OP_NQ, n, ld, mom_dev, nq_dev, stream);
     r.s_scalar = size_cutoff;
     return run(plan, r);
 }
@@ -1033,19 +1101,12 @@ int cloudy_rainshaft_sources(const cloudy_plan *plan, size_t n, size_t ld, const
     if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
     if (plan->h.threshold_style != CLOUDY_FIXED_THRESHOLD)
         return fail(CLOUDY_EINVAL, "make_rainshaft_rhs uses FixedThreshold (rainshaft_helpers.jl:70)");
-    LaunchReq r1{OP_COAL, IN_MOMENTS, 1, 1, n, ld, mom_dev, coal_source_dev, nullptr,
-                 (hipStream_t)stream};
-    // The cell-body kernel compiled for the plan writes the sedimentation flux as well (one launch, one read of the
-    // moments, one closure inversion); the ahead-of-time path is two launches.
-    if (n > 0 && jit_unit(plan, JIT_CELL).ok) {
-        r1.out2 = sedi_flux_dev;
-        return run(plan, r1);
-    }
-    rc = run(plan, r1);
-    if (rc) return rc;
-    LaunchReq r2{OP_SEDI, IN_MOMENTS, 1, 1, n, ld, mom_dev, sedi_flux_dev, nullptr,
-                 (hipStream_t)stream};
-    return run(plan, r2);
+    // the cell body compiled for the plan writes the sedimentation flux in the same launch (one read of the moments, one closure
+    // inversion); the ahead-of-time path is two launches (launch())
+    LaunchReq r(OP_COAL, n, ld, mom_dev, coal_source_dev, stream);
+    r.rainshaft = 1;
+    r.out2 = sedi_flux_dev;
+    return run(plan, r);
 }
 
 int cloudy_rainshaft_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *mom_dev, double dz,
@@ -1056,45 +1117,19 @@ int cloudy_rainshaft_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, s
     if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
     // Round 5: one launch when the plan has the column kernels compiled for it and a workgroup holds a column (nz <= 1024):
     // the RHS_ONLY instance of the column integrator's body -- sources, flux, exchange through LDS, divergence, sum -- writes
-    // rhs and the cell fluxes; fp64 planes: the same bits as the two launches below (test).  CLOUDY_HIP_RS_FUSED_RHS=0: off.
-    // (the argument checks of the two-launch path come first -- whether a call is valid must not depend on whether the
-    // kernels compiled for the plan are on)
+    // rhs and the cell fluxes; fp64 planes: the same bits as the two launches of rainshaft_rhs_unfused (test).
+    // CLOUDY_HIP_RS_FUSED_RHS=0: off.  (the argument checks come first -- whether a call is valid must not depend on
+    // whether the kernels compiled for the plan are on)
     if (!flux_work_dev && n > 0) return fail(CLOUDY_EINVAL, "device buffer is NULL");
     if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
     if (plan->h.threshold_style != CLOUDY_FIXED_THRESHOLD)
         return fail(CLOUDY_EINVAL, "make_rainshaft_rhs uses FixedThreshold (rainshaft_helpers.jl:70)");
-    if (n > 0 && nz <= 1024 && plan->jit_on && plan->h.coal_style != CLOUDY_NUMERICAL_COAL && plan->h.mode != MODE_MOVING) {
-        const char *fe = std::getenv("CLOUDY_HIP_RS_FUSED_RHS");
-        if (!(fe && fe[0] == '0')) {
-            DeviceGuard guard(plan->h.device);
-            if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-            const JitUnit u = pick_rainshaft(plan, nz, n_columns, true);
-            if (u != JIT_UNITS) {
-                const double *nodes = plan->h.nodes_dev;
-                int nzi = (int)nz;
-                const unsigned bs = (unsigned)jit_rainshaft_block(u);
-                const size_t cpb = bs / nz;
-                void *args[] = {&nodes, &nzi, &n_columns, &ld, &mom_dev, &rhs_dev, &flux_work_dev, &dz};
-                hipError_t e = hipModuleLaunchKernel(jit_unit(plan, u).fn[K_COL_RHS], (unsigned)((n_columns + cpb - 1) / cpb), 1, 1, bs, 1, 1, 0, (hipStream_t)stream,
-                                                     args, nullptr);
-                if (e != hipSuccess) return fail_hip(e, "column right-hand side launch");
-                return CLOUDY_OK;
-            }
-        }
-    }
-    rc = cloudy_rainshaft_sources(plan, n, ld, mom_dev, rhs_dev, flux_work_dev, stream);
-    if (rc || n == 0) return rc;
-    DeviceGuard guard(plan->h.device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-    const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
-    if (plan->h.dtype != CLOUDY_F64)
-        hipLaunchKernelGGL(rainshaft_divergence_kernel<float>, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, n, ld,
-                           plan->h.nmom, nz, dz, (const float *)flux_work_dev, (float *)rhs_dev);
-    else
-        hipLaunchKernelGGL(rainshaft_divergence_kernel<double>, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, n, ld,
-                           plan->h.nmom, nz, dz, (const double *)flux_work_dev, (double *)rhs_dev);
-    HIP_TRY(hipGetLastError());
-    return CLOUDY_OK;
+    LaunchReq r(OP_RAINSHAFT_RHS, n, ld, mom_dev, rhs_dev, stream);
+    r.rainshaft = 1;
+    r.out2 = flux_work_dev;
+    r.nz = nz;
+    r.dz = dz;
+    return run(plan, r);
 }
 
 int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev,
@@ -1108,125 +1143,8 @@ int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_
     if (plan->h.threshold_style != CLOUDY_FIXED_THRESHOLD)
         return fail(CLOUDY_EINVAL, "make_rainshaft_rhs uses FixedThreshold (rainshaft_helpers.jl:70)");
     if (n == 0) return CLOUDY_OK;
-    // no fused kernel for this column height: taller than a workgroup, or (round 6) a plan whose LDS rows leave no
-    // workgroup size that holds a column (5+ modes with a threshold beyond 256 cells, ...) and that the ahead-of-time
-    // integrator (<= 256 cells, <= CLOUDY_AOT_MAX_MODES modes) does not serve either
-    bool staged = nz > 1024;
-    if (!staged && plan->h.coal_style != CLOUDY_NUMERICAL_COAL) {
-        const bool aot = nz <= (size_t)kRainshaftBlock && plan->h.N <= CLOUDY_AOT_MAX_MODES && plan->h.P <= CLOUDY_AOT_MAX_P;
-        if (!aot) {
-            DeviceGuard guard(plan->h.device);
-            if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-            staged = plan->h.mode == MODE_MOVING || pick_rainshaft(plan, nz, n_columns, false) == JIT_UNITS;
-        }
-    }
-    if (staged) {
-        // Round 5 (VERDICT r4 missing #4): the reference's cell loop is unbounded in nz (rainshaft_helpers.jl:55-78), the fused
-        // kernel keeps a column inside one workgroup (<= 1024 cells).  Taller columns are stepped stage by stage on the stream:
-        // cloudy_rainshaft_rhs (cell sources + flux divergence: two launches) and one update launch per stage, with three
-        // scratch arrays of the state's size per call.  They are a plain allocation, freed when the steps are done: taken from the
-        // stream-ordered pool (hipMallocAsync / hipFreeAsync) about one call in five came back wrong on a box (garbage in ~1000
-        // of 13500 values of the 5-mode, 300-cell case of test_column_integrator_picks_a_workgroup_size_whose_lds_fits), as
-        // cloudy_closure_stats' rows did.
-        //
-        // Experiment switch CLOUDY_HIP_GRAPH=1 (round 5, measured SLOWER on ROCm 7.2 and therefore off): from the second step on
-        // ONE step -- nine launches -- is captured into a hipGraph and replayed.  The first step runs eagerly (it builds whatever
-        // the plan still has to compile; nothing may be compiled or loaded during a capture), the second is recorded on a stream
-        // of this call (the caller's stream may be the legacy NULL stream, which cannot capture) ordered after the caller's
-        // stream by an event and before it by another.  Same bits (test_tall_columns_replay_a_captured_step); per step of
-        // 3 x 1500 / 64 x 1500 / 256 x 4000 cells: eager 0.143 / 0.128 / 0.52 ms, replayed 0.158 / 0.162 / 0.84 ms, plus 3-5 ms
-        // of capture and instantiation per call (profiles/r05_tall_columns_graph_experiment.txt):
-        // the eager launches already queue back to back on the stream, and the graph's kernel nodes do not run closer together.
-        DeviceGuard guard(plan->h.device);
-        if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-        hipStream_t user = (hipStream_t)stream, st = user;
-        const size_t esz = plan->h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double);
-        const size_t bytes = (size_t)plan->h.nmom * ld * esz;
-        bool graph_on = false;
-        if (const char *e = std::getenv("CLOUDY_HIP_GRAPH")) graph_on = n_steps >= 4 && e[0] == '1';
-        if (graph_on) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(user, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) graph_on = false;
-            (void)hipGetLastError();
-        }
-        hipStream_t own = nullptr;
-        hipEvent_t ev_in = nullptr, ev_out = nullptr;
-        if (graph_on) {
-            graph_on = hipStreamCreateWithFlags(&own, hipStreamNonBlocking) == hipSuccess &&
-                       hipEventCreateWithFlags(&ev_in, hipEventDisableTiming) == hipSuccess &&
-                       hipEventCreateWithFlags(&ev_out, hipEventDisableTiming) == hipSuccess &&
-                       hipEventRecord(ev_in, user) == hipSuccess && hipStreamWaitEvent(own, ev_in, 0) == hipSuccess;
-            if (graph_on) st = own;
-            else (void)hipGetLastError();
-        }
-        const auto release = [&] {
-            if (ev_in) (void)hipEventDestroy(ev_in);
-            if (ev_out) (void)hipEventDestroy(ev_out);
-            if (own) (void)hipStreamDestroy(own);   // (returns at once; the stream goes when its work is done)
-        };
-        hipError_t e = hipSuccess;
-        if (u_out_dev != u_in_dev) e = hipMemcpyAsync(u_out_dev, u_in_dev, bytes, hipMemcpyDeviceToDevice, st);
-        char *ws = nullptr;
-        if (e == hipSuccess) e = hipMalloc((void **)&ws, 3 * bytes);
-        if (e != hipSuccess) {
-            release();
-            return fail_hip(e, "scratch of the stage-by-stage column integrator");
-        }
-        void *up = ws, *f = ws + bytes, *flux = ws + 2 * bytes;
-        const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
-        const int planes = plan->h.nmom;
-        const auto stage = [&](int sidx) -> hipError_t {
-            if (plan->h.dtype != CLOUDY_F64)
-                hipLaunchKernelGGL(rainshaft_stage_kernel<float>, dim3(g), dim3(kBlock), 0, st, sidx, n, ld, planes, (float *)up,
-                                   (float *)u_out_dev, (const float *)f, dt);
-            else
-                hipLaunchKernelGGL(rainshaft_stage_kernel<double>, dim3(g), dim3(kBlock), 0, st, sidx, n, ld, planes, (double *)up,
-                                   (double *)u_out_dev, (const double *)f, dt);
-            return hipGetLastError();
-        };
-        rc = CLOUDY_OK;
-        const auto one_step = [&] {
-            for (int sidx = 0; sidx < 3 && rc == CLOUDY_OK && e == hipSuccess; ++sidx) {
-                rc = cloudy_rainshaft_rhs(plan, nz, n_columns, ld, u_out_dev, dz, flux, f, st);
-                if (rc == CLOUDY_OK) e = stage(sidx);
-            }
-        };
-        int step = 0;
-        if (n_steps > 0) {
-            one_step();
-            ++step;
-        }
-        if (graph_on && rc == CLOUDY_OK && e == hipSuccess) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                one_step();   // recorded, not run
-                const hipError_t ec = hipStreamEndCapture(st, &graph);
-                const bool recorded = rc == CLOUDY_OK && e == hipSuccess && ec == hipSuccess && graph != nullptr;
-                rc = CLOUDY_OK;   // (a failure while recording leaves nothing half done: the eager loop below takes over)
-                e = hipSuccess;
-                if (recorded && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    for (; step < n_steps && e == hipSuccess; ++step) e = hipGraphLaunch(exec, st);
-                    (void)hipGraphExecDestroy(exec);
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();
-        }
-        for (; step < n_steps && rc == CLOUDY_OK && e == hipSuccess; ++step) one_step();
-        if (rc == CLOUDY_OK && e == hipSuccess && n_steps > 0) e = stage(3);
-        (void)hipFree(ws);   // (waits for the steps)
-        if (own != nullptr) {   // the caller's stream goes on after this call's work
-            hipError_t eo = hipEventRecord(ev_out, own);
-            if (eo == hipSuccess) eo = hipStreamWaitEvent(user, ev_out, 0);
-            if (eo != hipSuccess && e == hipSuccess) e = eo;
-        }
-        release();
-        if (rc != CLOUDY_OK) return rc;
-        if (e != hipSuccess) return fail_hip(e, "stage-by-stage column integrator");
-        return CLOUDY_OK;
-    }
-    LaunchReq r{OP_RAINSHAFT_SSPRK33, IN_MOMENTS, 1, 1, n, ld, u_in_dev, u_out_dev, nullptr, (hipStream_t)stream};
+    LaunchReq r(OP_RAINSHAFT_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
+    r.rainshaft = 1;
     r.dt = dt;
     r.n_steps = n_steps;
     r.nz = nz;

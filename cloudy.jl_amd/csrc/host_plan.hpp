@@ -46,52 +46,53 @@ struct HostPlan {
     double *qtab_dev = nullptr;
 };
 
-enum Op { OP_COAL = 0, OP_UPDATE_DIST = 1, OP_FINITE_2D = 2, OP_SEDI = 3, OP_SSPRK33 = 4, OP_COND = 5, OP_PREPARE = 6 /* plan creation: upload the constant block */, OP_NQ = 7, OP_RAINSHAFT_SSPRK33 = 8, OP_TSIT5 = 9 };
+enum Op {
+    OP_COAL = 0, OP_UPDATE_DIST = 1, OP_FINITE_2D = 2, OP_SEDI = 3, OP_SSPRK33 = 4, OP_COND = 5,
+    OP_PREPARE = 6 /* plan creation: upload the constant block */, OP_NQ = 7, OP_RAINSHAFT_SSPRK33 = 8, OP_TSIT5 = 9,
+    OP_RAINSHAFT_RHS = 10 /* one evaluation of the column right-hand side (cloudy_rainshaft_rhs) */
+};
 
 struct LaunchReq {
     int op;
-    int input_kind;   // IN_MOMENTS / IN_PARAMS
-    int physical_out; // 1: multiply by mom_norms (rhs_coal!), 0: normalised units (get_coal_ints)
-    int rainshaft;    // clamp negatives + skip empty cells
+    int input_kind = 0;    // IN_MOMENTS (0) / IN_PARAMS (1), kernels.hpp
+    int physical_out = 1;  // 1: multiply by mom_norms (rhs_coal!), 0: normalised units (get_coal_ints)
+    int rainshaft = 0;     // clamp negatives + skip empty cells
     size_t n, ld;
     const void *in;   // planes of the plan's dtype (double, or float for CLOUDY_F32 plans)
-    void *out;        // OP_COAL: dmom; OP_UPDATE_DIST: params; OP_FINITE_2D: F (may be null); OP_SEDI: flux
-    void *out2;       // OP_FINITE_2D: thresholds (may be null)
+    void *out;        // OP_COAL: dmom; OP_UPDATE_DIST: params; OP_FINITE_2D: F (may be null); OP_SEDI: flux; OP_RAINSHAFT_RHS: rhs
+    void *out2 = nullptr;  // OP_FINITE_2D: thresholds (may be null); rainshaft OP_COAL: the sedimentation flux (null: not wanted);
+                           // OP_RAINSHAFT_RHS: the cell fluxes (work planes)
     hipStream_t stream;
-    double dt = 0.0;  // OP_SSPRK33
-    int n_steps = 0;  // OP_SSPRK33
+    double dt = 0.0;  // OP_SSPRK33, OP_TSIT5, OP_RAINSHAFT_SSPRK33
+    int n_steps = 0;  // likewise
     double coef = 0.0, s_scalar = 0.0;  // OP_COND
     const double *s_dev = nullptr;      // OP_COND (optional per-parcel supersaturation)
-    size_t nz = 0;    // OP_RAINSHAFT_SSPRK33: cells per column (n = nz * n_columns)
-    double dz = 0.0;  // OP_RAINSHAFT_SSPRK33
+    size_t nz = 0;    // OP_RAINSHAFT_*: cells per column (n = nz * n_columns)
+    double dz = 0.0;  // OP_RAINSHAFT_*
+    LaunchReq(int op_, size_t n_, size_t ld_, const void *in_, void *out_, void *stream_)
+        : op(op_), n(n_), ld(ld_), in(in_), out(out_), stream(static_cast<hipStream_t>(stream_)) {}
 };
 
+// Parcels per lane of the all-Inf RHS kernels (ahead-of-time launch_io() and the plan's main unit alike): 4 where the plan has
+// the packed single-precision kernel (CLOUDY_F32_FAST, for every layout: the arithmetic is a property of the plan, not of the
+// batch's alignment), 2 where both planes allow 2-element accesses, else 1 (CLOUDY_HIP_PPL1=1: always 1).  esz: bytes per
+// plane element.
+inline int allinf_parcels_per_lane(const HostPlan &h, const LaunchReq &r, size_t esz, bool packed4) {
+    if (h.force_ppl1) return 1;
+    if (packed4) return 4;
+    const uintptr_t amask = 2 * esz - 1;
+    const bool aligned2 = ((reinterpret_cast<uintptr_t>(r.in) | reinterpret_cast<uintptr_t>(r.out)) & amask) == 0 && r.ld % 2 == 0;
+    return aligned2 ? 2 : 1;
+}
+
+// every kernel family of one (N, P), explicitly instantiated one per unit (inst_n<N>_p<P>.hip) so that the families compile in
+// parallel
+template <int N, int P>
+hipError_t launch_np(const HostPlan &h, const LaunchReq &r);
 // the fused integrators (cloudy_ssprk33_steps, cloudy_rainshaft_ssprk33_steps) live in their own units
 // (int_n<N>_p<P>.hip), compiled with machine LICM off: see launch_int_impl.hpp
 template <int N, int P>
 hipError_t launch_int(const HostPlan &h, const LaunchReq &r);
-
-// one per instantiation unit (inst_n<N>_p<P>.hip), so that the kernel families compile in parallel
-hipError_t launch_n1_p1(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n1_p2(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n1_p3(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n1_p4(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n1_p5(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n2_p1(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n2_p2(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n2_p3(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n2_p4(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n2_p5(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n3_p1(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n3_p2(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n3_p3(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n3_p4(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n3_p5(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n4_p1(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n4_p2(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n4_p3(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n4_p4(const HostPlan &h, const LaunchReq &r);
-hipError_t launch_n4_p5(const HostPlan &h, const LaunchReq &r);
 // cloudy_coal_rhs / cloudy_get_coal_ints of a NumericalCoalStyle plan, ahead-of-time kernels (quad_n<N>.hip)
 hipError_t launch_quad_n1(const HostPlan &h, const LaunchReq &r);
 hipError_t launch_quad_n2(const HostPlan &h, const LaunchReq &r);

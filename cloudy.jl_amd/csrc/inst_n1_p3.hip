@@ -1,5 +1,5 @@
 // instantiation unit: every kernel of the N = 1 modes, P = 3 (tensor order 2) family
 #include "launch_impl.hpp"
 namespace cloudy {
-hipError_t launch_n1_p3(const HostPlan &h, const LaunchReq &r) { return launch_np<1, 3>(h, r); }
+template hipError_t launch_np<1, 3>(const HostPlan &h, const LaunchReq &r);
 }  // namespace cloudy

@@ -1,5 +1,5 @@
 // instantiation unit: every kernel of the N = 2 modes, P = 1 (tensor order 0) family
 #include "launch_impl.hpp"
 namespace cloudy {
-hipError_t launch_n2_p1(const HostPlan &h, const LaunchReq &r) { return launch_np<2, 1>(h, r); }
+template hipError_t launch_np<2, 1>(const HostPlan &h, const LaunchReq &r);
 }  // namespace cloudy

@@ -1,5 +1,5 @@
 // instantiation unit: every kernel of the N = 2 modes, P = 5 (tensor order 4) family
 #include "launch_impl.hpp"
 namespace cloudy {
-hipError_t launch_n2_p5(const HostPlan &h, const LaunchReq &r) { return launch_np<2, 5>(h, r); }
+template hipError_t launch_np<2, 5>(const HostPlan &h, const LaunchReq &r);
 }  // namespace cloudy

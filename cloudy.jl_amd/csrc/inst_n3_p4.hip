@@ -1,5 +1,5 @@
 // instantiation unit: every kernel of the N = 3 modes, P = 4 (tensor order 3) family
 #include "launch_impl.hpp"
 namespace cloudy {
-hipError_t launch_n3_p4(const HostPlan &h, const LaunchReq &r) { return launch_np<3, 4>(h, r); }
+template hipError_t launch_np<3, 4>(const HostPlan &h, const LaunchReq &r);
 }  // namespace cloudy

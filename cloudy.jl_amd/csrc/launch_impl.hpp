@@ -1,15 +1,30 @@
-// launch_impl.hpp -- fills KArgs<N,P> from the host plan and launches the kernel for one N (all P, all modes).
-// Included by inst_n{1,2,3,4}.hip so that the instantiations compile in parallel.
+// launch_impl.hpp -- fills KArgs<N,P> from the host plan and launches the kernels of one (N, P) family (all modes).
+// Included by inst_n<N>_p<P>.hip so that the instantiations compile in parallel.
 #pragma once
+#include <type_traits>
+
 #include "host_plan.hpp"
 #include "kernels.hpp"
 
 namespace cloudy {
 
-inline unsigned grid_for(size_t n, bool /*heavy*/) {
-    size_t blocks = (n + kBlock - 1) / kBlock;  // one parcel per lane (see kernels.hpp)
+// workgroups for n items, per_wg of them per workgroup (one parcel per lane by default: see kernels.hpp)
+inline unsigned grid_for(size_t n, size_t per_wg = kBlock) {
+    size_t blocks = (n + per_wg - 1) / per_wg;
     if (blocks < 1) blocks = 1;
     return (unsigned)blocks;
+}
+
+// Calls f(std::integral_constant<T, V>{}) for the one V of Vs equal to the run-time value v (none: hipErrorInvalidValue), so
+// that the launch of a kernel family is written once and instantiated for the listed values only.  The kernels one pick()
+// instantiates land in the code object in the reverse order of Vs, and that order changes the code generated for kernels that
+// share device functions: the value lists below run backwards, which keeps every unit's kernels, and their code, in the order of
+// the launch ladders they replace.
+template <auto... Vs, typename T, typename F>
+auto pick(T v, F &&f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs && (e = f(std::integral_constant<decltype(Vs), Vs>{}), true)) || ...);
+    return e;
 }
 
 template <int N, int P>
@@ -54,6 +69,9 @@ inline int sorted_block_size(const HostPlan &h) {
     for (int i = 0; i < h.N - 1; ++i) passes += h.finite[i] ? 1 : 0;
     return passes == 1 ? 512 : kBlock;
 }
+// the workgroup sizes of the threshold kernels of mode M: 512 threads for MODE_FIXED plans of N <= 2 only
+template <int N, int M, int BS>
+constexpr bool sorted_block_exists = BS == kBlock || (N <= 2 && M == MODE_FIXED);
 
 inline void fill_sedi(const HostPlan &h, SediArgs &S) {
     S.n_vel = h.n_vel;
@@ -67,63 +85,45 @@ inline void fill_sedi(const HostPlan &h, SediArgs &S) {
 // kernels that exist for both plane types (double / float storage)
 template <int N, int P, typename TIO>
 hipError_t launch_io(const HostPlan &h, const LaunchReq &r, const KArgs<N, P> &A) {
-    const bool heavy = h.mode != MODE_ALLINF;
     const TIO *in = static_cast<const TIO *>(r.in);
     TIO *out = static_cast<TIO *>(r.out);
     switch (r.op) {
     case OP_COAL: {
-        const unsigned g = grid_for(r.n, heavy);
-        const uintptr_t amask = 2 * sizeof(TIO) - 1;  // two parcels per lane need 2-element aligned planes
-        const bool aligned2 = ((reinterpret_cast<uintptr_t>(r.in) | reinterpret_cast<uintptr_t>(r.out)) & amask) == 0 &&
-                              (r.ld % 2 == 0);
-        if (h.mode == MODE_ALLINF && r.input_kind == IN_MOMENTS && !r.rainshaft && aligned2 && !h.force_ppl1)
-            hipLaunchKernelGGL((coal_rhs_allinf2_kernel<N, P, TIO>), dim3(grid_for((r.n + 1) / 2, false)), dim3(kBlock),
-                               0, r.stream, A, r.n, r.ld, in, out);
-        else if (h.mode == MODE_ALLINF)
-            hipLaunchKernelGGL((coal_rhs_kernel<N, P, MODE_ALLINF, TIO>), dim3(g), dim3(kBlock), 0, r.stream, A,
-                               h.nodes_dev, r.n, r.ld, in, out);
-        else {
-            // FixedThreshold plans with N <= 2 and one thresholded mode rank 512 parcels per workgroup (kernels.hpp)
-            const bool fast = h.dtype == CLOUDY_F32_FAST && sizeof(TIO) == 4 && r.input_kind == IN_MOMENTS;
-            if (N <= 2 && sorted_block_size(h) == 512) {
-                if constexpr (N <= 2) {
-                    const unsigned g5 = (unsigned)((r.n + 511) / 512);
-                    if (fast)
-                        hipLaunchKernelGGL((coal_rhs_sorted_kernel<N, P, MODE_FIXED, TIO, true, 512>), dim3(g5), dim3(512), 0,
-                                           r.stream, A, h.nodes_dev, r.n, r.ld, in, out);
-                    else
-                        hipLaunchKernelGGL((coal_rhs_sorted_kernel<N, P, MODE_FIXED, TIO, false, 512>), dim3(g5), dim3(512), 0,
-                                           r.stream, A, h.nodes_dev, r.n, r.ld, in, out);
-                }
-            } else if (fast) {
-                if (h.mode == MODE_FIXED)
-                    hipLaunchKernelGGL((coal_rhs_sorted_kernel<N, P, MODE_FIXED, TIO, true>), dim3(g), dim3(kBlock), 0,
-                                       r.stream, A, h.nodes_dev, r.n, r.ld, in, out);
-                else
-                    hipLaunchKernelGGL((coal_rhs_sorted_kernel<N, P, MODE_MOVING, TIO, true>), dim3(g), dim3(kBlock), 0,
-                                       r.stream, A, h.nodes_dev, r.n, r.ld, in, out);
-            } else if (h.mode == MODE_FIXED)
-                hipLaunchKernelGGL((coal_rhs_sorted_kernel<N, P, MODE_FIXED, TIO>), dim3(g), dim3(kBlock), 0, r.stream, A,
-                                   h.nodes_dev, r.n, r.ld, in, out);
+        if (h.mode == MODE_ALLINF) {
+            if (r.input_kind == IN_MOMENTS && !r.rainshaft && allinf_parcels_per_lane(h, r, sizeof(TIO), false) == 2)
+                hipLaunchKernelGGL((coal_rhs_allinf2_kernel<N, P, TIO>), dim3(grid_for(r.n, 2 * kBlock)), dim3(kBlock), 0, r.stream,
+                                   A, r.n, r.ld, in, out);
             else
-                hipLaunchKernelGGL((coal_rhs_sorted_kernel<N, P, MODE_MOVING, TIO>), dim3(g), dim3(kBlock), 0, r.stream, A,
+                hipLaunchKernelGGL((coal_rhs_kernel<N, P, MODE_ALLINF, TIO>), dim3(grid_for(r.n)), dim3(kBlock), 0, r.stream, A,
                                    h.nodes_dev, r.n, r.ld, in, out);
+            break;
         }
-        break;
+        const bool fast = h.dtype == CLOUDY_F32_FAST && sizeof(TIO) == 4 && r.input_kind == IN_MOMENTS;
+        return pick<kBlock, 512>(sorted_block_size(h), [&](auto BS) {
+            return pick<false, true>(fast, [&](auto FAST) {
+                return pick<MODE_MOVING, MODE_FIXED>(h.mode, [&](auto M) {
+                    if constexpr (!sorted_block_exists<N, M, BS>) return hipErrorInvalidValue;
+                    else {
+                        hipLaunchKernelGGL((coal_rhs_sorted_kernel<N, P, M, TIO, FAST, BS>), dim3(grid_for(r.n, BS)), dim3(BS), 0,
+                                           r.stream, A, h.nodes_dev, r.n, r.ld, in, out);
+                        return hipGetLastError();
+                    }
+                });
+            });
+        });
     }
     case OP_SEDI: {
         SediArgs S;
         fill_sedi(h, S);
-        hipLaunchKernelGGL((sedi_flux_kernel<N, P, TIO>), dim3(grid_for(r.n, false)), dim3(kBlock), 0, r.stream, A, S,
-                           r.n, r.ld, in, out);
+        hipLaunchKernelGGL((sedi_flux_kernel<N, P, TIO>), dim3(grid_for(r.n)), dim3(kBlock), 0, r.stream, A, S, r.n, r.ld, in, out);
         break;
     }
     case OP_NQ:  // r.s_scalar = size cutoff in physical mass units
-        hipLaunchKernelGGL((standard_nq_kernel<N, P, TIO>), dim3(grid_for(r.n, false)), dim3(kBlock), 0, r.stream, A,
+        hipLaunchKernelGGL((standard_nq_kernel<N, P, TIO>), dim3(grid_for(r.n)), dim3(kBlock), 0, r.stream, A,
                            r.s_scalar / h.norms[1], h.norms[0], h.norms[1], r.n, r.ld, in, out);
         break;
     case OP_COND:
-        hipLaunchKernelGGL((cond_evap_kernel<N, P, TIO>), dim3(grid_for(r.n, false)), dim3(kBlock), 0, r.stream, A,
+        hipLaunchKernelGGL((cond_evap_kernel<N, P, TIO>), dim3(grid_for(r.n)), dim3(kBlock), 0, r.stream, A,
                            r.coef, r.s_scalar, r.s_dev, r.n, r.ld, in, out);
         break;
     default: return hipErrorInvalidValue;
@@ -135,7 +135,6 @@ template <int N, int P>
 hipError_t launch_np(const HostPlan &h, const LaunchReq &r) {
     KArgs<N, P> A;
     fill_args<N, P>(h, r, A);
-    const bool heavy = h.mode != MODE_ALLINF;
     switch (r.op) {
     case OP_PREPARE: {  // constant block in device memory for the fused integrators (moments in, physical units out)
         struct Block {  // SediArgs directly behind KArgs: rainshaft_ssprk33_kernel reads it at (Ag + 1)
@@ -168,24 +167,15 @@ hipError_t launch_np(const HostPlan &h, const LaunchReq &r) {
         if (h.dtype != CLOUDY_F64 && r.input_kind == IN_MOMENTS) return launch_io<N, P, float>(h, r, A);
         return launch_io<N, P, double>(h, r, A);
     case OP_UPDATE_DIST:
-        hipLaunchKernelGGL((update_dist_kernel<N, P>), dim3(grid_for(r.n, false)), dim3(kBlock), 0, r.stream, A, r.n,
-                           r.ld, static_cast<const double *>(r.in), static_cast<double *>(r.out));
+        hipLaunchKernelGGL((update_dist_kernel<N, P>), dim3(grid_for(r.n)), dim3(kBlock), 0, r.stream, A, r.n, r.ld,
+                           static_cast<const double *>(r.in), static_cast<double *>(r.out));
         break;
-    case OP_FINITE_2D: {
-        const unsigned g = grid_for(r.n, heavy);
-        const double *in = static_cast<const double *>(r.in);
-        double *out = static_cast<double *>(r.out), *out2 = static_cast<double *>(r.out2);
-        if (h.mode == MODE_ALLINF)
-            hipLaunchKernelGGL((finite_2d_kernel<N, P, MODE_ALLINF>), dim3(g), dim3(kBlock), 0, r.stream, A,
-                               h.nodes_dev, r.n, r.ld, in, out, out2);
-        else if (h.mode == MODE_FIXED)
-            hipLaunchKernelGGL((finite_2d_kernel<N, P, MODE_FIXED>), dim3(g), dim3(kBlock), 0, r.stream, A,
-                               h.nodes_dev, r.n, r.ld, in, out, out2);
-        else
-            hipLaunchKernelGGL((finite_2d_kernel<N, P, MODE_MOVING>), dim3(g), dim3(kBlock), 0, r.stream, A,
-                               h.nodes_dev, r.n, r.ld, in, out, out2);
-        break;
-    }
+    case OP_FINITE_2D:
+        return pick<MODE_MOVING, MODE_FIXED, MODE_ALLINF>(h.mode, [&](auto M) {
+            hipLaunchKernelGGL((finite_2d_kernel<N, P, M>), dim3(grid_for(r.n)), dim3(kBlock), 0, r.stream, A, h.nodes_dev, r.n,
+                               r.ld, static_cast<const double *>(r.in), static_cast<double *>(r.out), static_cast<double *>(r.out2));
+            return hipGetLastError();
+        });
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

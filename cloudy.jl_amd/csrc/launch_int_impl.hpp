@@ -12,63 +12,40 @@ namespace cloudy {
 
 template <int N, int P, typename TIO>
 hipError_t launch_int_io(const HostPlan &h, const LaunchReq &r) {
-    const bool heavy = h.mode != MODE_ALLINF;
+    if (!h.kargs_dev) return hipErrorNotInitialized;  // uploaded by OP_PREPARE at plan creation
+    const KArgs<N, P> *Ad = static_cast<const KArgs<N, P> *>(h.kargs_dev);
     const TIO *in = static_cast<const TIO *>(r.in);
     TIO *out = static_cast<TIO *>(r.out);
     switch (r.op) {
-    case OP_SSPRK33: {
-        const unsigned g = grid_for(r.n, heavy);
-        if (!h.kargs_dev) return hipErrorNotInitialized;  // uploaded by OP_PREPARE at plan creation
-        const KArgs<N, P> *Ad = static_cast<const KArgs<N, P> *>(h.kargs_dev);
-        if (h.mode == MODE_ALLINF)
-            hipLaunchKernelGGL((ssprk33_kernel<N, P, MODE_ALLINF, TIO>), dim3(g), dim3(kBlock), 0, r.stream, Ad,
-                               h.nodes_dev, r.n, r.ld, in, out, r.dt, r.n_steps);
-        else if (h.mode == MODE_FIXED && N <= 2 && sorted_block_size(h) == 512) {
-            if constexpr (N <= 2)
-                hipLaunchKernelGGL((ssprk33_kernel<N, P, MODE_FIXED, TIO, 512>), dim3((unsigned)((r.n + 511) / 512)),
-                                   dim3(512), 0, r.stream, Ad, h.nodes_dev, r.n, r.ld, in, out, r.dt, r.n_steps);
-        } else if (h.mode == MODE_FIXED)
-            hipLaunchKernelGGL((ssprk33_kernel<N, P, MODE_FIXED, TIO>), dim3(g), dim3(kBlock), 0, r.stream, Ad,
-                               h.nodes_dev, r.n, r.ld, in, out, r.dt, r.n_steps);
-        else
-            hipLaunchKernelGGL((ssprk33_kernel<N, P, MODE_MOVING, TIO>), dim3(g), dim3(kBlock), 0, r.stream, Ad,
-                               h.nodes_dev, r.n, r.ld, in, out, r.dt, r.n_steps);
-        break;
-    }
-    case OP_TSIT5: {  // cloudy_tsit5_steps: thresholds Inf, fixed or moving; fp64 or float planes
-        if (!h.kargs_dev) return hipErrorNotInitialized;
-        const KArgs<N, P> *Ad = static_cast<const KArgs<N, P> *>(h.kargs_dev);
-        const unsigned g = grid_for(r.n, heavy);
-        if (h.mode == MODE_ALLINF)
-            hipLaunchKernelGGL((tsit5_kernel<N, P, MODE_ALLINF, TIO>), dim3(g), dim3(kBlock), 0, r.stream, Ad, h.nodes_dev,
-                               r.n, r.ld, in, out, r.dt, r.n_steps);
-        else if (h.mode == MODE_FIXED)
-            hipLaunchKernelGGL((tsit5_kernel<N, P, MODE_FIXED, TIO>), dim3(g), dim3(kBlock), 0, r.stream, Ad, h.nodes_dev,
-                               r.n, r.ld, in, out, r.dt, r.n_steps);
-        else
-            hipLaunchKernelGGL((tsit5_kernel<N, P, MODE_MOVING, TIO>), dim3(g), dim3(kBlock), 0, r.stream, Ad, h.nodes_dev,
-                               r.n, r.ld, in, out, r.dt, r.n_steps);
-        break;
-    }
+    case OP_SSPRK33:
+        return pick<MODE_MOVING, MODE_FIXED, MODE_ALLINF>(h.mode, [&](auto M) {
+            return pick<kBlock, 512>(sorted_block_size(h), [&](auto BS) {
+                if constexpr (!sorted_block_exists<N, M, BS>) return hipErrorInvalidValue;
+                else {
+                    hipLaunchKernelGGL((ssprk33_kernel<N, P, M, TIO, BS>), dim3(grid_for(r.n, BS)), dim3(BS), 0, r.stream, Ad,
+                                       h.nodes_dev, r.n, r.ld, in, out, r.dt, r.n_steps);
+                    return hipGetLastError();
+                }
+            });
+        });
+    case OP_TSIT5:  // cloudy_tsit5_steps: thresholds Inf, fixed or moving; fp64 or float planes
+        return pick<MODE_MOVING, MODE_FIXED, MODE_ALLINF>(h.mode, [&](auto M) {
+            hipLaunchKernelGGL((tsit5_kernel<N, P, M, TIO>), dim3(grid_for(r.n)), dim3(kBlock), 0, r.stream, Ad, h.nodes_dev, r.n,
+                               r.ld, in, out, r.dt, r.n_steps);
+            return hipGetLastError();
+        });
     case OP_RAINSHAFT_SSPRK33: {
-        if (!h.kargs_dev) return hipErrorNotInitialized;
         if (r.nz < 1 || r.nz > (size_t)kBlock) return hipErrorInvalidValue;
-        const KArgs<N, P> *Ad = static_cast<const KArgs<N, P> *>(h.kargs_dev);
         const size_t cpb = kRainshaftBlock / r.nz, n_columns = r.n / r.nz;
-        const unsigned g = (unsigned)((n_columns + cpb - 1) / cpb);
-        if (h.mode == MODE_ALLINF)
-            hipLaunchKernelGGL((rainshaft_ssprk33_kernel<N, P, MODE_ALLINF, TIO>), dim3(g), dim3(kRainshaftBlock), 0, r.stream,
-                               Ad, h.nodes_dev, (int)r.nz, n_columns, r.ld, in, out, r.dt, r.dz, r.n_steps);
-        else if (h.mode == MODE_FIXED)
-            hipLaunchKernelGGL((rainshaft_ssprk33_kernel<N, P, MODE_FIXED, TIO>), dim3(g), dim3(kRainshaftBlock), 0, r.stream,
-                               Ad, h.nodes_dev, (int)r.nz, n_columns, r.ld, in, out, r.dt, r.dz, r.n_steps);
-        else
-            return hipErrorInvalidValue;  // make_rainshaft_rhs is FixedThreshold only (rainshaft_helpers.jl:70)
-        break;
+        // make_rainshaft_rhs is FixedThreshold only (rainshaft_helpers.jl:70): no MovingThreshold kernel
+        return pick<MODE_FIXED, MODE_ALLINF>(h.mode, [&](auto M) {
+            hipLaunchKernelGGL((rainshaft_ssprk33_kernel<N, P, M, TIO>), dim3(grid_for(n_columns, cpb)), dim3(kRainshaftBlock), 0,
+                               r.stream, Ad, h.nodes_dev, (int)r.nz, n_columns, r.ld, in, out, r.dt, r.dz, r.n_steps);
+            return hipGetLastError();
+        });
     }
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 template <int N, int P>
