@@ -85,15 +85,15 @@ inline int allinf_parcels_per_lane(const HostPlan &h, const LaunchReq &r, size_t
     return aligned2 ? 2 : 1;
 }
 
-// every kernel family of one (N, P), explicitly instantiated one per unit (inst_n<N>_p<P>.hip) so that the families compile in
-// parallel
+// every kernel family of one (N, P), explicitly instantiated one per unit (inst.hip -> inst_n<N>_p<P>.o) so that the families
+// compile in parallel
 template <int N, int P>
 hipError_t launch_np(const HostPlan &h, const LaunchReq &r);
 // the fused integrators (cloudy_ssprk33_steps, cloudy_rainshaft_ssprk33_steps) live in their own units
-// (int_n<N>_p<P>.hip), compiled with machine LICM off: see launch_int_impl.hpp
+// (int.hip -> int_n<N>_p<P>.o), compiled with machine LICM off: see launch_int_impl.hpp
 template <int N, int P>
 hipError_t launch_int(const HostPlan &h, const LaunchReq &r);
-// cloudy_coal_rhs / cloudy_get_coal_ints of a NumericalCoalStyle plan, ahead-of-time kernels (quad_n<N>.hip)
+// cloudy_coal_rhs / cloudy_get_coal_ints of a NumericalCoalStyle plan, ahead-of-time kernels (quad.hip -> quad_n<N>.o)
 hipError_t launch_quad_n1(const HostPlan &h, const LaunchReq &r);
 hipError_t launch_quad_n2(const HostPlan &h, const LaunchReq &r);
 hipError_t launch_quad_n3(const HostPlan &h, const LaunchReq &r);

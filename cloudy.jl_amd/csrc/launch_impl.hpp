@@ -1,5 +1,5 @@
 // launch_impl.hpp -- fills KArgs<N,P> from the host plan and launches the kernels of one (N, P) family (all modes).
-// Included by inst_n<N>_p<P>.hip so that the instantiations compile in parallel.
+// Included by inst.hip, compiled once per family (inst_n<N>_p<P>.o) so that the instantiations compile in parallel.
 #pragma once
 #include <type_traits>
 
@@ -158,7 +158,7 @@ hipError_t launch_np(const HostPlan &h, const LaunchReq &r) {
     case OP_SSPRK33:
     case OP_TSIT5:
     case OP_RAINSHAFT_SSPRK33:
-        return launch_int<N, P>(h, r);  // int_n<N>_p<P>.hip
+        return launch_int<N, P>(h, r);  // int.hip (int_n<N>_p<P>.o)
     case OP_COAL:
     case OP_SEDI:
     case OP_COND:

@@ -1,5 +1,6 @@
-// launch_quad_impl.hpp -- ahead-of-time kernels of the NumericalCoalStyle plans for one N (quad_n<N>.hip): every kernel
-// function family x both plane types, run-time rule order.  The plan-time compiled kernels (jit.hpp) are the fast path.
+// launch_quad_impl.hpp -- ahead-of-time kernels of the NumericalCoalStyle plans for one N (quad.hip, compiled once per
+// N: quad_n<N>.o): every kernel function family x both plane types, run-time rule order.  The plan-time compiled
+// kernels (jit.hpp) are the fast path.
 #pragma once
 #include "launch_impl.hpp"
 #include "quad_kernels.hpp"
