@@ -107,14 +107,7 @@
             } else {  // no threshold on this mode: only the (rare) M_p M_q < eps rule can promote anything
                 promoted_mode<N, P, MODE, FAST>(A, nodes, k, nn2[k], th2[k], kk2[k], Mm[k], T0, T1, T2);
             }
-            acc[k][0] -= T0;
-            acc[k][1] -= T1;
-            acc[k][2] -= T2;
-            if (k + 1 < N) {
-                acc[k + 1][0] += T0;
-                acc[k + 1][1] += T1;
-                acc[k + 1][2] += T2;
-            }
+            promoted_transfer<N>(k, T0, T1, T2, acc);
         }
         pair_terms<N, P, CLOUDY_SPEC>(A, Mm, acc);
         const bool skip = A.rainshaft && all_small;  // rainshaft_helpers.jl:67-68

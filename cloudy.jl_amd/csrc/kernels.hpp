@@ -823,6 +823,19 @@ __device__ __forceinline__ void promoted_mode(const KArgs<N, P> &A, const double
     promoted_finish<N, P>(A, k, n, kk, Mk, f, msh, T0, T1, T2);
 }
 
+// the promoted amounts T_m of the self collisions leave mode k for mode k+1 (lost for k = N-1)
+template <int N>
+__device__ __forceinline__ void promoted_transfer(int k, double T0, double T1, double T2, double (&acc)[N][3]) {
+    acc[k][0] -= T0;
+    acc[k][1] -= T1;
+    acc[k][2] -= T2;
+    if (k + 1 < N) {
+        acc[k + 1][0] += T0;
+        acc[k + 1][1] += T1;
+        acc[k + 1][2] += T2;
+    }
+}
+
 // ---- pair terms: Q - R for j < k, -R for j > k, S_1(full products) - R for j == k, with the
 //      products common to Q and R (and to S_1 and R) cancelled analytically:
 //      Q_0 = R_0;  Q_1 = R_1 + sum v1_b Mk_b;  Q_2 = R_2 + 2 sum v1_b Mk_{b+1} + sum v2_b Mk_b
@@ -898,19 +911,12 @@ __device__ __forceinline__ void coal_ints_parcel(const KArgs<N, P> &A, const dou
     for (int i = 0; i < N; ++i) moment_row<M>(A.dist_type[i], nn[i], th[i], kk[i], A.n_mom_max, Mm[i]);
 #pragma unroll
     for (int k = 0; k < N; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
-    // ---- promoted part of the self collisions: moves T_m from mode k to mode k+1 (lost for k = N-1)
+    // ---- promoted part of the self collisions (promoted_transfer)
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         double T0, T1, T2;
         promoted_mode<N, P, MODE, FAST>(A, nodes, k, nn[k], th[k], kk[k], Mm[k], T0, T1, T2);
-        acc[k][0] -= T0;
-        acc[k][1] -= T1;
-        acc[k][2] -= T2;
-        if (k + 1 < N) {
-            acc[k + 1][0] += T0;
-            acc[k + 1][1] += T1;
-            acc[k + 1][2] += T2;
-        }
+        promoted_transfer<N>(k, T0, T1, T2, acc);
     }
     pair_terms<N, P, SPEC>(A, Mm, acc);
 }
@@ -991,14 +997,7 @@ __device__ __forceinline__ void coal_ints_ranked_impl(const KArgs<N, P> &A, cons
         } else {  // no threshold on this mode: only the (rare) M_p M_q < eps rule can promote anything
             promoted_mode<N, P, MODE, false>(A, nodes, k, nn2[k], th2[k], kk2[k], Mm[k], T0, T1, T2);
         }
-        acc[k][0] -= T0;
-        acc[k][1] -= T1;
-        acc[k][2] -= T2;
-        if (k + 1 < N) {
-            acc[k + 1][0] += T0;
-            acc[k + 1][1] += T1;
-            acc[k + 1][2] += T2;
-        }
+        promoted_transfer<N>(k, T0, T1, T2, acc);
     }
     pair_terms<N, P, SPEC>(A, Mm, acc);
     if (RELOAD) {  // (read again rather than kept across pair_terms: 3N doubles the moment rows and pair sums do not need)

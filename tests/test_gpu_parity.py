@@ -1005,6 +1005,45 @@ def test_fused_ssprk33_batch_vs_oracle_stepping(gpu_cloudy, oracle, name, tol):
     print(f"{name}: fused SSPRK33 vs oracle stepping, max rel err {err.max():.2e}")
 
 
+@pytest.mark.parametrize("thr", [(INF, INF), (5e-9, INF)])
+def test_fused_integrators_two_moment_mode_partial_workgroup_and_padding(gpu_cloudy, oracle, thr):
+    """The corners of the state load and store the fused integrators share: an Exponential (2 moments) next to a Gamma
+    (3 moments) mode -- 5 planes, no third plane for mode 0 -- and n = 300 parcels in buffers of leading dimension 320: one
+    full workgroup and a partial one, whose lanes without a parcel must neither read nor write.  cloudy_ssprk33_steps and
+    cloudy_tsit5_steps, 2 steps out of place, without thresholds and with a finite first one (every lane of the workgroup
+    stays for the ranking's barriers), against the same scheme driven by the oracle RHS on the regular parcels and with
+    the bound of test_fused_ssprk33_batch_vs_oracle_stepping."""
+    cloudy = gpu_cloudy
+    n, ld, dt, n_steps = 300, 320, 1e-3, 2
+    dist_types = [0, 1]
+    par, op, _ = make_case(cloudy, oracle, dist_types, bench.kernel_matrix(bench.workload_spec("cfg3a")), thr, bench.NORMS)
+    plan = par.coal_data.plan(dist_types)
+    assert plan.nmom == 5
+    # (seed and threshold picked on the oracle alone: 300 / 276 regular parcels of 300 without / with the threshold; at the
+    # reference's 5e-10 kg the Exponential cloud mode feeds the rain mode by more than a factor 10 in two steps: 208)
+    mom = mixed_moments(dist_types, n, seed=7)
+    tol = TOL_QUAD if any(np.isfinite(thr)) else TOL_POLY
+    sentinel = np.float64(np.nan).view(np.uint64) | np.uint64(0x5EED)   # a NaN no arithmetic produces
+    L = cloudy.lib()
+    for what, host, entry in (("SSPRK33", _ssprk33_host, L.cloudy_ssprk33_steps), ("Tsit5", _tsit5_host, L.cloudy_tsit5_steps)):
+        with np.errstate(all="ignore"):
+            want = host(lambda v: oracle.rhs_coal_batch(op, v), mom, dt, n_steps)
+            ok = np.isfinite(want).all(axis=0) & (np.abs(want[:3]) <= 10 * np.abs(mom[:3]) + 1e-300).all(axis=0)
+        assert ok.sum() >= 0.9 * n, (what, ok.sum())   # (of the oracle alone: the seed was picked for it)
+        buf = np.full((5, ld), 7.0)
+        buf[:, :n] = mom
+        u_in = dev(cloudy, buf)
+        u_out = dev(cloudy, np.full((5, ld), sentinel, dtype=np.uint64).view(np.float64))
+        cloudy._lib.check(entry(plan.handle, n, ld, u_in.ptr, u_out.ptr, dt, n_steps, None))
+        got = u_out.to_numpy()
+        assert np.all(got[:, n:].view(np.uint64) == sentinel), f"{what}: the padding columns were written"
+        assert np.array_equal(u_in.to_numpy(), buf), f"{what}: the input changed"
+        ref = np.abs(mom) + np.abs(want)
+        err = np.abs(got[:, :n] - want)[:, ok] / np.maximum(ref[:, ok], 1e-300)
+        print(f"thr={thr}: fused {what} vs oracle stepping, {ok.sum()} regular parcels of {n}, max rel err {err.max():.2e}")
+        assert err.max() < max(1e3 * tol, 1e-9), (what, err.max())
+
+
 @pytest.mark.parametrize("name,n", [("cfg3a", 100_001), ("cfg3b", 10_000)])
 def test_fp32_planes_vs_fp64_oracle(gpu_cloudy, oracle, name, n):
     """BASELINE configs[4] "fp32 path with fp64 tolerance check": CLOUDY_F32 plans keep the moment / tendency planes
