@@ -7,7 +7,7 @@ ParticleDistributions, EquationTypes, Coalescence, Sedimentation, helper functio
 RHS factory of test/examples/utils/box_model_helpers.jl.  There is no CPU compute path in this package.
 """
 from . import _lib
-from ._lib import CloudyError, device_count, lib
+from ._lib import SRC_COAL, SRC_COND, CloudyError, device_count, lib
 from .device import DeviceArray, plane_dtype
 from .EquationTypes import (AbstractStyle, AnalyticalCoalStyle, CoalescenceStyle, FixedThreshold, MovingThreshold,
                             NumericalCoalStyle, ThresholdStyle)
@@ -25,7 +25,7 @@ from .Coalescence import (CoalescenceData, NumericalPlan, Plan, get_coal_ints, g
                           F64_RELAXED)
 from .Sedimentation import (get_sedimentation_flux, make_rainshaft_rhs, rainshaft_sources, rhs_condensation,
                             solve_rainshaft_ssprk33)
-from .box_model import ODEParameters, make_box_model_rhs, rhs_coal, solve_ssprk33, solve_tsit5
+from .box_model import ODEParameters, make_box_model_rhs, rhs_coal, solve_box_ssprk33, solve_ssprk33, solve_tsit5
 from .sharding import Communicator, allreduce_sums, mode_sums, moment_sums, shard_range
 
 __all__ = [n for n in dir() if not n.startswith("_")]

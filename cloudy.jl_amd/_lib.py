@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("CLOUDY_HIP_LIB") or os.path.join(_HERE, "libcloudy_hi
 MAX_MODES, MAX_P, MAX_VEL = 8, 8, 4
 OK, EINVAL, ENOTSYMMETRIC, EHIP, ENOMEM, EUNSUPPORTED, ENODEVICE, ECOMM = 0, -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
+SRC_COAL, SRC_COND = 1, 2  # CLOUDY_SRC_*: the sources of cloudy_box_ssprk33_steps
 
 
 class CloudyError(RuntimeError):
@@ -71,6 +72,7 @@ SYMBOLS = {
     "cloudy_get_coal_ints": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "cloudy_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, _i, _vp]),
     "cloudy_tsit5_steps": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, _i, _vp]),
+    "cloudy_box_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, _i, _vp]),
     "cloudy_update_dist_from_moments": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "cloudy_closure_stats": (_i, [_vp, _sz, _sz, _vp, C.POINTER(C.c_uint64), _vp]),
     "cloudy_finite_2d_integrals": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),

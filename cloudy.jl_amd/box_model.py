@@ -11,7 +11,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _lib
-from .device import as_device, dtype_code
+from .device import DeviceArray, as_device, dtype_code
 from .EquationTypes import AnalyticalCoalStyle, CoalescenceStyle, FixedThreshold, MovingThreshold, NumericalCoalStyle
 from .ParticleDistributions import nparams
 
@@ -111,4 +111,32 @@ def solve_tsit5(par, u, dt, n_steps, out=None, stream=None, coal_type=None):
     if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
         raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
     _lib.check(_lib.lib().cloudy_tsit5_steps(plan.handle, n, ld, uptr, optr, float(dt), int(n_steps), stream))
+    return o
+
+
+def solve_box_ssprk33(par, u, dt, n_steps, xi, s, coal=True, cond=True, out=None, stream=None, coal_type=None):
+    """solve(ODEProblem(rhs!, u, tspan, par), SSPRK33(), dt = dt) for n_steps fixed steps on the device, with rhs! the sum of
+    the selected sources: rhs_coal! (`coal`) and rhs_condensation!(dm, m, par, s) (`cond`; condensation_single_gamma.jl:24-28,
+    condensation_exp_gamma.jl:23-31) -- one launch, state in registers, one closure inversion per stage for both sources
+    (cloudy_box_ssprk33_steps).  `xi` = p.xi; `s`: the supersaturation, a float or an (1, n) fp64 device array (one value per
+    parcel), as rhs_condensation takes it.  `u` is advanced in place unless `out` is given.  `coal_type`: as solve_ssprk33; a
+    NumericalCoalStyle plan serves cond alone."""
+    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
+        raise ValueError("Invalid coal style!")
+    sources = (_lib.SRC_COAL if coal else 0) | (_lib.SRC_COND if cond else 0)
+    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
+    uptr, planes, n, ld = as_device(u)
+    o = out if out is not None else u
+    optr, oplanes, on, old = as_device(o)
+    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
+        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    if hasattr(s, "data_ptr") or isinstance(s, DeviceArray):
+        sptr, splanes, sn, _ = as_device(s)
+        if splanes != 1 or sn != n or dtype_code(s) != 0:   # (the kernel reads n doubles, whatever the plan's plane type)
+            raise ValueError("s must be a float or an (1, n) fp64 device array")
+        sval = 0.0
+    else:
+        sptr, sval = None, float(s)
+    _lib.check(_lib.lib().cloudy_box_ssprk33_steps(plan.handle, n, ld, uptr, optr, sources, sptr, sval, float(xi), float(dt),
+                                                  int(n_steps), stream))
     return o

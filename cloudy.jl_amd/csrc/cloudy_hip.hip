@@ -22,6 +22,7 @@
 #include "host_quad.hpp"
 #include "kernels.hpp"
 #include "jit.hpp"
+#include "box_sources.hpp"
 #include "reduce_kernels.hpp"
 
 using namespace cloudy;
@@ -201,6 +202,7 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
         if (r.rainshaft) return JIT_UNITS;
         return h.mode == MODE_ALLINF && h.coal_style != CLOUDY_NUMERICAL_COAL ? JIT_MAIN : JIT_INTEGRATOR;
     case OP_TSIT5: return JIT_TSIT5;
+    case OP_BOX_SSPRK33: return JIT_BOX;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_RHS: {  // CLOUDY_HIP_RS_FUSED_RHS=0 (read per call): sources + divergence (rainshaft_rhs_unfused)
         const char *e = std::getenv("CLOUDY_HIP_RS_FUSED_RHS");
@@ -218,6 +220,11 @@ struct JitShape {
     size_t per_wg = kBlock;
 };
 JitShape jit_shape(const HostPlan &h, JitUnit u, const LaunchReq &r) {
+    if (r.op == OP_BOX_SSPRK33) {  // box_kernel() of jit.hpp: the threshold kernels' workgroup only where the parcels are ranked
+        const bool coal = (r.sources & SRC_COAL) != 0;
+        const unsigned bs = coal && h.mode != MODE_ALLINF ? (unsigned)jit_sorted_block_size(h) : (unsigned)kBlock;
+        return {coal ? K_BOX_COAL_COND : K_BOX_COND, bs, bs};
+    }
     if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS) {  // whole columns per workgroup, as launch_int_io()
         const unsigned bs = (unsigned)jit_rainshaft_block(u);
         return {r.op == OP_RAINSHAFT_RHS ? K_COL_RHS : 0, bs, bs / r.nz * r.nz};
@@ -251,7 +258,9 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
     double dt = r.dt, dz = r.dz;
     int nz = (int)r.nz, n_steps = r.n_steps;
     int aligned16 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    void *args[9];
+    double coef = r.coef, s_scalar = r.s_scalar;
+    const double *s_dev = r.s_dev;
+    void *args[10];
     int na = 0;
     const auto push = [&](std::initializer_list<void *> a) {
         for (void *p : a) args[na++] = p;
@@ -260,6 +269,8 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
         push({&nodes, &nz, &n_columns, &ld, &in, &out});
         if (r.op == OP_RAINSHAFT_RHS) push({&out2, &dz});
         else push({&dt, &dz, &n_steps});
+    } else if (r.op == OP_BOX_SSPRK33) {
+        push({&nodes, &n, &ld, &in, &out, &coef, &s_scalar, &s_dev, &dt, &n_steps});
     } else {
         if (!numerical && (h.mode != MODE_ALLINF || r.op == OP_TSIT5)) push({&nodes});
         push({&n, &ld, &in, &out});
@@ -393,6 +404,10 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         if (e != hipSuccess) return fail_hip(e, r.op == OP_RAINSHAFT_RHS ? "column right-hand side launch" : "specialised kernel launch");
         return CLOUDY_OK;
     }
+    if (r.op == OP_BOX_SSPRK33)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_ssprk33_steps with the condensation source runs the kernel compiled for the plan "
+                                         "(hiprtc); plan-time compilation is off or failed: %s",
+                    plan->jit_on ? jit_unit(plan, JIT_BOX).log.c_str() : plan->jit[JIT_MAIN].log.c_str());
     if (r.op == OP_RAINSHAFT_RHS) return rainshaft_rhs_unfused(plan, r);
     if (r.op == OP_RAINSHAFT_SSPRK33 && rainshaft_staged(plan, r.nz, r.n / r.nz)) return rainshaft_staged_steps(plan, r);
     if (r.op == OP_COAL && r.rainshaft && r.out2) {
@@ -439,6 +454,24 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
         return fail(CLOUDY_EUNSUPPORTED,
                     "NumericalCoalStyle plans serve cloudy_coal_rhs / cloudy_get_coal_ints / cloudy_ssprk33_steps and the "
                     "per-mode diagnostics; thresholds and the rainshaft body belong to AnalyticalCoalStyle plans");
+    if (r.op == OP_BOX_SSPRK33) {
+        if (r.sources < 1 || r.sources > (SRC_COAL | SRC_COND))
+            return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COAL, CLOUDY_SRC_COND or both", r.sources);
+        if (r.n_steps < 0 || !(r.dt == r.dt) || !(r.coef == r.coef)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0, dt and xi not NaN");
+        if (plan->h.dtype == CLOUDY_F32_FAST)
+            return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_ssprk33_steps serves CLOUDY_F64 and CLOUDY_F32 plans (the fused integrators keep "
+                                             "the state in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode)");
+        if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL && (r.sources & SRC_COAL))
+            return fail(CLOUDY_EUNSUPPORTED, "the combined coalescence + condensation kernel is not built for quadrature "
+                                             "(NumericalCoalStyle) plans: step them stage by stage with cloudy_coal_rhs and "
+                                             "cloudy_cond_evap, or pass CLOUDY_SRC_COND alone");
+        if (r.sources == SRC_COAL) {  // coalescence alone is cloudy_ssprk33_steps: the same request, the same kernel
+            LaunchReq coal(OP_SSPRK33, r.n, r.ld, r.in, r.out, r.stream);
+            coal.dt = r.dt;
+            coal.n_steps = r.n_steps;
+            return run(plan, coal);
+        }
+    }
     if (r.n == 0) return CLOUDY_OK;
     DeviceGuard guard(plan->h.device);
     if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
@@ -975,6 +1008,22 @@ int cloudy_tsit5_steps(const cloudy_plan *plan, size_t n, size_t ld, const void 
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_steps serves CLOUDY_F64 and CLOUDY_F32 plans (the fused integrators keep "
                                          "the state in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode)");
     LaunchReq r(OP_TSIT5, n, ld, u_in_dev, u_out_dev, stream);
+    r.dt = dt;
+    r.n_steps = n_steps;
+    return run(plan, r);
+}
+
+int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, int sources,
+                             const double *s_dev, double s, double xi, double dt, int n_steps, void *stream) {
+    int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
+    if (rc) return rc;
+    LaunchReq r(OP_BOX_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
+    r.sources = sources;
+    // as cloudy_cond_evap: xi_normalized = p.xi / norms[2]^(2/3) (box_model_helpers.jl:65); rho_l = 1000 (Condensation.jl:26)
+    const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
+    r.coef = 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
+    r.s_scalar = s;
+    r.s_dev = s_dev;
     r.dt = dt;
     r.n_steps = n_steps;
     return run(plan, r);

@@ -38,6 +38,9 @@
  *   cloudy_ssprk33_steps          <- solve(ODEProblem(rhs, m0, tspan, p), SSPRK33(), dt = p.dt) of the drivers,
  *                                    test/examples/Analytical/box_single_gamma.jl:35-36 (OrdinaryDiffEq stepping)
  *   cloudy_tsit5_steps            <- solve(prob, Tsit5(), dt = ..., adaptive = false) (BASELINE configs[0]; OrdinaryDiffEq tableau)
+ *   cloudy_box_ssprk33_steps      <- solve(ODEProblem(rhs!, ...), SSPRK33(), dt = ...) with rhs! = rhs_condensation! (or the sum
+ *                                    of rhs_coal! and it), test/examples/Analytical/condensation_single_gamma.jl:28,
+ *                                    condensation_exp_gamma.jl:31
  *   cloudy_moment_sums            <- moments_sum diagnostic, test/examples/utils/plotting_helpers.jl:240-252
  *   cloudy_moment_sums_allreduce  <- the same summed over the ranks / GPUs that share a batch (RCCL; the reference is
  *                                    single-process, its global sum is the local one)
@@ -90,6 +93,9 @@ extern "C" {
 #define CLOUDY_AOT_MAX_P 5
 #define CLOUDY_MAX_VEL 4    /* terms of the terminal-velocity power series */
 #define CLOUDY_MAX_MOMENTS (3 * CLOUDY_MAX_MODES)
+/* the sources cloudy_box_ssprk33_steps integrates (bits of its `sources` argument) */
+#define CLOUDY_SRC_COAL 1 /* collision-coalescence, rhs_coal! */
+#define CLOUDY_SRC_COND 2 /* condensation / evaporation, rhs_condensation! */
 
 /* distribution families, ParticleDistributions.jl:66-159.  Parameter planes are (n, theta, k); Monodisperse uses
  * (n, theta), Lognormal keeps (n, mu, sigma) in the same three slots. */
@@ -272,6 +278,27 @@ int cloudy_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, c
  * NumericalCoalStyle plan answers CLOUDY_EUNSUPPORTED. */
 int cloudy_tsit5_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
                        double dt, int n_steps, void *stream);
+
+/* n_steps SSPRK33 steps of du/dt = [coal](u) + [cond](u; s, xi) with fixed dt, fused like cloudy_ssprk33_steps: a lane keeps its
+ * parcel's state in registers over all stages and steps, the state is read once and written once per call and the parcel's
+ * supersaturation is loaded once.  [cond] is rhs_condensation!(dmom, mom, p, s) (test/examples/utils/box_model_helpers.jl:55-67
+ * -> get_cond_evap, src/Sources/Condensation.jl:22-37) and s_dev / s / xi mean what they mean in cloudy_cond_evap: s_dev holds
+ * one fp64 value per parcel or is NULL to use the scalar `s`; xi = p.xi in physical units (rho_l = 1000).
+ *   sources = CLOUDY_SRC_COND: `solve(prob, SSPRK33(), dt = ODE_parameters.dt)` with rhs! = rhs_condensation! of
+ *     test/examples/Analytical/condensation_single_gamma.jl:28 and condensation_exp_gamma.jl:31 in one launch; every plan
+ *     cloudy_cond_evap serves, NumericalCoalStyle plans included (nothing of the coalescence data is read);
+ *   sources = CLOUDY_SRC_COAL | CLOUDY_SRC_COND: both sources from ONE closure inversion per stage; AnalyticalCoalStyle plans
+ *     with thresholds Inf, fixed or MovingThreshold, CLOUDY_F64 / CLOUDY_F64_RELAXED / CLOUDY_F32 planes, up to CLOUDY_MAX_MODES
+ *     modes; a NumericalCoalStyle plan answers CLOUDY_EUNSUPPORTED (step it stage by stage: cloudy_coal_rhs + cloudy_cond_evap);
+ *   sources = CLOUDY_SRC_COAL: forwards to cloudy_ssprk33_steps (the same kernel, the same bits).
+ * The kernels with the condensation source are compiled for the plan on the first call that needs them (cloudy_jit_box_*);
+ * without plan-time compilation such a call answers CLOUDY_EUNSUPPORTED with the compiler's log.  That holds for
+ * CLOUDY_SRC_COND alone as well, a deliberate limit: cloudy_cond_evap has ahead-of-time kernels, this integrator has none (they
+ * would be a third family of translation units), so a plan created with specialize = -1 steps condensation stage by stage
+ * with cloudy_cond_evap, and steps coalescence alone here or with cloudy_ssprk33_steps.  CLOUDY_F32_FAST:
+ * CLOUDY_EUNSUPPORTED.  u_out_dev may equal u_in_dev; n_steps = 0 copies the input to the output. */
+int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
+                             int sources, const double *s_dev, double s, double xi, double dt, int n_steps, void *stream);
 
 /* inner operator on given distributions: params = 3N planes (n, theta, k) per mode, normalised units
  * (k plane ignored for exponential modes); out = nmom planes, normalised units. */

@@ -21,6 +21,7 @@ const lib = get(ENV, "CLOUDY_HIP_LIB", joinpath(@__DIR__, "..", "cloudy.jl_amd",
 
 const MAX_MODES, MAX_P, MAX_VEL = 8, 8, 4
 const COMM_ID_BYTES = 128
+const SRC_COAL, SRC_COND = 1, 2   # CLOUDY_SRC_*: the sources of cloudy_box_ssprk33_steps
 
 # mirrors `struct cloudy_plan_desc` of include/cloudy_hip.h field by field
 mutable struct PlanDesc
@@ -360,6 +361,28 @@ function solve_tsit5!(u, plan::Plan, dt, n_steps; stream = nothing, sync::Bool =
                 (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Cvoid}),
                 plan.handle, n, ld, pointer(u), pointer(u), dt, n_steps, s))
     sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), s))
+    return u
+end
+
+"""
+    solve_box_ssprk33!(u, plan, dt, n_steps, xi, s; coal = true, cond = true, stream = nothing, sync = true)
+
+`solve(ODEProblem(rhs!, u, tspan, p), SSPRK33(), dt = dt)` for `n_steps` fixed steps on the device with `rhs!` the sum of the
+selected sources: `rhs_coal!` (`coal`) and `rhs_condensation!(dm, m, p, s)` (`cond`; the drivers
+test/examples/Analytical/condensation_single_gamma.jl:28 and condensation_exp_gamma.jl:31) -- one launch, one closure inversion
+per stage for both.  `xi` = `p.ξ`; `s` a number, or a device `Vector{Float64}` with one supersaturation per parcel.
+"""
+function solve_box_ssprk33!(u, plan::Plan, dt, n_steps, xi, s; coal::Bool = true, cond::Bool = true, stream = nothing,
+                            sync::Bool = true)
+    n, ld = batch_shape(u, plan.nmom)
+    st = stream === nothing ? current_stream() : stream
+    sources = (coal ? SRC_COAL : 0) | (cond ? SRC_COND : 0)
+    s_dev = s isa Number ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(s))
+    s_val = s isa Number ? Float64(s) : 0.0
+    check(ccall((:cloudy_box_ssprk33_steps, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Cint, Ptr{Cvoid}),
+                plan.handle, n, ld, pointer(u), pointer(u), sources, s_dev, s_val, xi, dt, n_steps, st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
     return u
 end
 

@@ -12,6 +12,9 @@ every experiment switch of the library is an environment variable, so an A/B run
         cloudy_rainshaft_ssprk33_steps and cloudy_rainshaft_rhs (ms per 1e7 cells)
   python tools/timeit.py integrators [--parcels P]
         cloudy_ssprk33_steps / cloudy_tsit5_steps of the tensor plans cfg3a, cfg3b, cfg2
+  python tools/timeit.py box [--parcels P] [--steps S]
+        cloudy_box_ssprk33_steps on cfg3a and cfg3b: (a) cloudy_ssprk33_steps, (b) coalescence + condensation fused, (c) condensation
+        alone, (d) the unfused sequence (b) replaces -- cloudy_coal_rhs + cloudy_cond_evap + torch updates per stage
   python tools/timeit.py host [--parcels P]
         cloudy_coal_rhs_host on cfg3a: the PCIe-inclusive rate (host arrays staged through the device)
 
@@ -131,6 +134,59 @@ def cmd_integrators(a, pkg, L):
         print(f"{name}, {n} parcels: SSPRK33 {ms_s / 12:.4f} ms per evaluation, Tsit5 {ms_t / 25:.4f} ms per evaluation", flush=True)
 
 
+def cmd_box(a, pkg, L):
+    """ms per call of S steps: (a) cloudy_ssprk33_steps, (b) / (c) cloudy_box_ssprk33_steps with COAL | COND / COND, (d) the same
+    steps stage by stage: two right-hand-side launches and the update on the planes (torch, on the same stream) per stage"""
+    here = os.path.dirname(os.path.abspath(__file__))   # torch imports the standard library's timeit: this file must not shadow it
+    sys.path[:] = [p for p in sys.path if os.path.abspath(p or ".") != here]
+    import torch
+
+    n, steps, xi, dt = a.parcels or 10_000_000, a.steps, 1e-8, C.c_double(1e-3)
+    s_host = np.random.default_rng(0).uniform(-0.02, 0.05, n)
+    for name in ("cfg3a", "cfg3b"):
+        wl = bench.make_workload(name, n, seed=7)
+        plan = wl["coal_data"].plan(wl["dist_types"])
+        u0, out = pkg.DeviceArray.from_numpy(wl["mom"]), pkg.DeviceArray.zeros(*wl["mom"].shape)
+        s = pkg.DeviceArray.from_numpy(s_host[None, :])
+        both = pkg.SRC_COAL | pkg.SRC_COND
+        ms_a = bench._sustained_ms(pkg, lambda: pkg._lib.check(L.cloudy_ssprk33_steps(plan.handle, n, n, u0.ptr, out.ptr, dt, steps, None)))
+        ms_b = bench._sustained_ms(pkg, lambda: pkg._lib.check(
+            L.cloudy_box_ssprk33_steps(plan.handle, n, n, u0.ptr, out.ptr, both, s.ptr, 0.0, xi, dt, steps, None)))
+        ms_c = bench._sustained_ms(pkg, lambda: pkg._lib.check(
+            L.cloudy_box_ssprk33_steps(plan.handle, n, n, u0.ptr, out.ptr, pkg.SRC_COND, s.ptr, 0.0, xi, dt, steps, None)))
+        t0 = torch.from_numpy(wl["mom"]).cuda()
+        u, up, f, g = (torch.empty_like(t0) for _ in range(4))
+        h = dt.value
+
+        def unfused():
+            u.copy_(t0)
+            for _ in range(steps):
+                up.copy_(u)
+                for stage in range(3):
+                    pkg._lib.check(L.cloudy_coal_rhs(plan.handle, n, n, u.data_ptr(), f.data_ptr(), None))
+                    pkg._lib.check(L.cloudy_cond_evap(plan.handle, n, n, u.data_ptr(), s.ptr, 0.0, xi, g.data_ptr(), None))
+                    f.add_(g)
+                    if stage == 0:
+                        torch.add(up, f, alpha=h, out=u)
+                    elif stage == 1:
+                        u.add_(f, alpha=h).add_(up, alpha=3.0).mul_(0.25)
+                    else:
+                        u.mul_(2.0).add_(f, alpha=2.0 * h).add_(up).div_(3.0)
+
+        ms_d = bench._sustained_ms(pkg, unfused, min_reps=3)
+        # the two paths compute the same steps (to the roundings of the update formulas)
+        pkg._lib.check(L.cloudy_box_ssprk33_steps(plan.handle, n, n, u0.ptr, out.ptr, both, s.ptr, 0.0, xi, dt, steps, None))
+        unfused()
+        got, want = out.columns_to_numpy(20000), u[:, :20000].cpu().numpy()
+        fin = np.isfinite(want) & np.isfinite(got)
+        dev = float(np.max(np.abs(got - want)[fin] / np.maximum((np.abs(wl["mom"][:, :20000]) + np.abs(want))[fin], 1e-300)))
+        print(f"{name}, {n} parcels, {steps} steps per call: (a) cloudy_ssprk33_steps {ms_a:.3f} ms | (b) box COAL|COND {ms_b:.3f} ms | "
+              f"(c) box COND {ms_c:.3f} ms | (d) unfused coal_rhs + cond_evap + torch updates {ms_d:.3f} ms | b/a {ms_b / ms_a:.2f} | "
+              f"d/b {ms_d / ms_b:.2f} | (b) = {3 * steps * n / ms_b * 1e3:.3e} parcel-RHS/s | fused vs unfused state, first 20000 "
+              f"parcels: {dev:.1e} of |u0| + |u|", flush=True)
+        del u, up, f, g, t0, u0, out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -155,11 +211,14 @@ def main():
     r.add_argument("--steps", type=int, default=2)
     i = sub.add_parser("integrators")
     i.add_argument("--parcels", type=int, default=0)
+    b = sub.add_parser("box")
+    b.add_argument("--parcels", type=int, default=0)
+    b.add_argument("--steps", type=int, default=4)
     hh = sub.add_parser("host")
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
-    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "integrators": cmd_integrators, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
+    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "integrators": cmd_integrators, "box": cmd_box, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
 if __name__ == "__main__":
