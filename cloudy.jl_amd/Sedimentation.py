@@ -79,3 +79,61 @@ def solve_rainshaft_ssprk33(par, u, n_steps, out=None, stream=None):
     _lib.check(_lib.lib().cloudy_rainshaft_ssprk33_steps(plan.handle, nz, n // nz, ld, ptr, optr, float(par.dz),
                                                          float(par.dt), int(n_steps), stream))
     return out if out is not None else u
+
+
+def _cell_supersaturation(s, n):
+    """-> (pointer or None, scalar): `s` a float, or an (1, n) fp64 device array with one supersaturation per cell"""
+    if hasattr(s, "data_ptr") or isinstance(s, DeviceArray):
+        from .device import dtype_code
+
+        sptr, splanes, sn, _ = as_device(s)
+        if splanes != 1 or sn != n or dtype_code(s) != 0:   # (the kernels read n doubles, whatever the plan's plane type)
+            raise ValueError("s must be a float or an (1, n) fp64 device array with one value per cell")
+        return sptr, 0.0
+    return None, float(s)
+
+
+def make_rainshaft_cond_rhs(coal_type=None):
+    """make_rainshaft_rhs(coal_type) with the third source of a column: returns rhs(m, p, t, xi, s) -> d(m)/dt, the
+    coalescence source plus the upwind divergence of the sedimentation flux plus get_cond_evap of every cell
+    (Condensation.jl:22-37) at the cell's supersaturation `s` (a float, or an (1, n) fp64 device array in the cell order of
+    `m`); `xi` = p.xi.  One launch for columns of up to 1024 cells (cloudy_rainshaft_cond_rhs)."""
+    from .box_model import _plan_for
+    from .device import dtype_code
+
+    def rhs(m, p, t, xi, s, out=None, work=None):
+        plan = _plan_for(p, dtype_code(m))
+        ptr, planes, n, ld = as_device(m)
+        nz = int(getattr(p, "nz", n))
+        if n % nz:
+            raise ValueError("number of cells must be a multiple of p.nz")
+        dt = plane_dtype(plan)
+        o = out if out is not None else DeviceArray(plan.nmom, n, dt)
+        w = work if work is not None else DeviceArray(plan.nmom, n, dt)
+        sptr, sval = _cell_supersaturation(s, n)
+        _lib.check(_lib.lib().cloudy_rainshaft_cond_rhs(plan.handle, nz, n // nz, ld, ptr, sptr, sval, float(xi), float(p.dz),
+                                                       as_device(w)[0], as_device(o)[0], None))
+        return o
+
+    return rhs
+
+
+def solve_rainshaft_cond_ssprk33(par, u, n_steps, xi, s, out=None, stream=None):
+    """solve_rainshaft_ssprk33 for columns through air with a supersaturation profile: SSPRK33 steps of coalescence +
+    sedimentation + condensation / evaporation, one closure inversion per stage for the three sources, one launch for columns
+    of up to 1024 cells (cloudy_rainshaft_cond_ssprk33_steps; stage by stage inside the library otherwise).  `xi` = p.xi;
+    `s`: the supersaturation, a float or an (1, n) fp64 device array with one value per cell in the cell order of `u`,
+    constant over the call.  `u` is advanced in place unless `out` is given."""
+    from .box_model import _plan_for
+    from .device import dtype_code
+
+    plan = _plan_for(par, dtype_code(u))
+    ptr, planes, n, ld = as_device(u)
+    nz = int(getattr(par, "nz", n))
+    if n % nz:
+        raise ValueError("number of cells must be a multiple of par.nz")
+    optr = as_device(out)[0] if out is not None else ptr
+    sptr, sval = _cell_supersaturation(s, n)
+    _lib.check(_lib.lib().cloudy_rainshaft_cond_ssprk33_steps(plan.handle, nz, n // nz, ld, ptr, optr, sptr, sval, float(xi),
+                                                              float(par.dz), float(par.dt), int(n_steps), stream))
+    return out if out is not None else u

@@ -7,50 +7,14 @@
 // costs two right-hand-side launches and an update launch per stage, seven passes over the state; here a lane keeps its parcel in
 // registers over all stages and steps as in ssprk33_body, and ONE closure inversion per stage feeds both sources.
 //
-// Nothing of kernels.hpp is changed: the bodies here call its per-parcel device functions (invert_closure, coal_ints_parcel,
-// coal_ints_ranked_impl, log_gamma_ratio, div_by_const).
+// The body here calls the per-parcel device functions of kernels.hpp (invert_closure, coal_ints_parcel, coal_ints_ranked_impl,
+// cond_evap_parcel -- which the column integrator with the condensation source shares -- and div_by_const).
 #pragma once
 #include "kernels.hpp"
 
 namespace cloudy {
 
 enum { SRC_COAL = 1, SRC_COND = 2 };  // CLOUDY_SRC_* of include/cloudy_hip.h
-
-// get_cond_evap (Condensation.jl:22-37) for one parcel, by the formulas of cond_evap_body:
-//   d(M_j)/dt = coef s j M_{j - 2/3}   (0-based order j; zero for j = 0),   coef = 3 xi_normalised (4 pi/3)^(2/3) / rho_l^(1/3)
-// with M_{1/3} of the Gamma family from the log-gamma ratio and M_{4/3} = M_{1/3} theta (k + 1/3); Lognormal (theta = mu,
-// k = sigma) and Monodisperse modes from their closed forms.  (n, theta, k) are the normalised closure parameters; the tendency
-// comes back in the units the caller keeps its state in: normalised (PHYSICAL = false), or times out_scale = mom_norms.
-// Planes a mode does not carry (order 2 of a two-moment mode) get zero.
-// Where cond_evap_body calls log / exp for the Gamma family, this calls log_pos / exp_fin of device_math.hpp (about 32 and 19
-// VALU instructions where the library routines have about 95 and 31: this runs N times per stage).  Their domains hold:
-// invert_closure hands back theta > 0 whenever n > 0 and (0, 1, 1) otherwise, so log_pos sees a positive finite argument
-// (log_pos(0) would be a finite value, not -Inf, but theta = 0 does not reach it), and the exponent q ln(theta) + lgamma ratio
-// of a k within [k_min, k_max] is far inside exp_fin's range.  The results differ from cond_evap_body's by roundings only.
-template <int N, int P, bool PHYSICAL>
-__device__ __forceinline__ void cond_evap_parcel(const KArgs<N, P> &A, double coef, double sv, const double (&nn)[N],
-                                                 const double (&th)[N], const double (&kk)[N], double (&f)[N][3]) {
-    const double cs = coef * sv;
-#pragma unroll
-    for (int m = 0; m < N; ++m) {
-        const int dtp = A.dist_type[m];
-        const bool gam = (dtp == DIST_GAMMA || dtp == DIST_EXP);
-        const double lnth = (dtp == DIST_LOGNORMAL) ? th[m] : log_pos(th[m]);
-        f[m][0] = f[m][1] = f[m][2] = 0.0;
-        double mom = 0.0;
-#pragma unroll
-        for (int j = 1; j < 3; ++j) {
-            if (j >= A.np[m]) continue;
-            const double q = double(j) - 2.0 / 3.0;
-            if (gam)
-                mom = (j == 1) ? nn[m] * exp_fin(fma(q, lnth, log_gamma_ratio(kk[m], q))) : mom * (th[m] * (kk[m] + (q - 1.0)));
-            else
-                mom = nn[m] * exp((dtp == DIST_MONO) ? q * lnth : fma(q, lnth, 0.5 * q * q * (kk[m] * kk[m])));
-            const double v = cs * double(j) * mom;
-            f[m][j] = PHYSICAL ? v * A.out_scale[3 * m + j] : v;
-        }
-    }
-}
 
 // n_steps SSPRK33 steps of du/dt = [coal](u) + [cond](u; s) for one parcel per lane; SRC: SRC_COND or SRC_COAL | SRC_COND
 // (coalescence alone is ssprk33_body).  State and u_prev stay in registers over all stages and steps, the state is read once

@@ -170,16 +170,29 @@ const JitSlot &jit_unit(const cloudy_plan *plan, JitUnit u) {
 // The column unit that serves columns of nz cells: the one jit_rainshaft_part prefers, then every smaller one that
 // still holds a column and fits the LDS -- a unit that does not compile or load is not the end of the call while another can
 // serve it.  Loads on first use.  JIT_UNITS: none (the caller steps stage by stage, or runs the ahead-of-time integrator).
-// rhs_only: a unit with the one-evaluation kernel (cloudy_rainshaft_rhs).
-JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, bool rhs_only) {
+// rhs_only: a unit with the one-evaluation kernel (cloudy_rainshaft_rhs).  cond: the same pick among the units with the
+// condensation source (cloudy_rainshaft_cond_*: the same workgroup sizes, the same LDS); the unit returned is then that one.
+JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, bool rhs_only, bool cond = false) {
     if (!plan->jit_on || nz < 1 || nz > 1024) return JIT_UNITS;
     const JitUnit pref = jit_rainshaft_part(plan->h, nz, n_columns);
     bool reached = false;
     for (JitUnit u : {JIT_COL1024, JIT_COL512, JIT_COL256}) {
         reached = reached || u == pref;
-        if (reached && jit_rainshaft_fits(plan->h, u, nz) && jit_unit(plan, u).fn[rhs_only ? K_COL_RHS : 0] != nullptr) return u;
+        const JitUnit v = cond ? jit_cond_unit(u) : u;
+        if (reached && jit_rainshaft_fits(plan->h, u, nz) && jit_unit(plan, v).fn[rhs_only ? K_COL_RHS : 0] != nullptr) return v;
     }
     return JIT_UNITS;
+}
+
+// Whether the calls with the condensation source take the stage-by-stage form because NO column unit could hold the columns
+// (whatever compiles): MovingThreshold plans, columns taller than a workgroup, LDS rows that fit no workgroup size that holds a
+// column.  Every other case belongs to the units compiled for the plan, and without them the call is refused (there are no
+// ahead-of-time instances).
+bool rainshaft_cond_staged(const HostPlan &h, size_t nz) {
+    if (h.mode == MODE_MOVING || nz > 1024) return true;
+    for (JitUnit u : {JIT_COL1024, JIT_COL512, JIT_COL256})
+        if (jit_rainshaft_fits(h, u, nz)) return false;
+    return true;
 }
 
 // Whether cloudy_rainshaft_ssprk33_steps steps the columns stage by stage (rainshaft_staged_steps) because no fused integrator
@@ -204,6 +217,9 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_TSIT5: return JIT_TSIT5;
     case OP_BOX_SSPRK33: return JIT_BOX;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
+    case OP_RAINSHAFT_COND_SSPRK33:
+    case OP_RAINSHAFT_COND_RHS:
+        return rainshaft_cond_staged(h, r.nz) ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, r.op == OP_RAINSHAFT_COND_RHS, true);
     case OP_RAINSHAFT_RHS: {  // CLOUDY_HIP_RS_FUSED_RHS=0 (read per call): sources + divergence (rainshaft_rhs_unfused)
         const char *e = std::getenv("CLOUDY_HIP_RS_FUSED_RHS");
         return h.mode == MODE_MOVING || (e && e[0] == '0') ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, true);
@@ -225,9 +241,9 @@ JitShape jit_shape(const HostPlan &h, JitUnit u, const LaunchReq &r) {
         const unsigned bs = coal && h.mode != MODE_ALLINF ? (unsigned)jit_sorted_block_size(h) : (unsigned)kBlock;
         return {coal ? K_BOX_COAL_COND : K_BOX_COND, bs, bs};
     }
-    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS) {  // whole columns per workgroup, as launch_int_io()
-        const unsigned bs = (unsigned)jit_rainshaft_block(u);
-        return {r.op == OP_RAINSHAFT_RHS ? K_COL_RHS : 0, bs, bs / r.nz * r.nz};
+    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
+        const unsigned bs = (unsigned)jit_rainshaft_block(u);   // whole columns per workgroup, as launch_int_io()
+        return {r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS ? K_COL_RHS : 0, bs, bs / r.nz * r.nz};
     }
     if (h.coal_style == CLOUDY_NUMERICAL_COAL) {
         const bool conv = h.q.mode == QUAD_CONVERGED;
@@ -260,15 +276,16 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
     int aligned16 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     double coef = r.coef, s_scalar = r.s_scalar;
     const double *s_dev = r.s_dev;
-    void *args[10];
+    void *args[12];
     int na = 0;
     const auto push = [&](std::initializer_list<void *> a) {
         for (void *p : a) args[na++] = p;
     };
-    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS) {
+    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         push({&nodes, &nz, &n_columns, &ld, &in, &out});
-        if (r.op == OP_RAINSHAFT_RHS) push({&out2, &dz});
+        if (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) push({&out2, &dz});
         else push({&dt, &dz, &n_steps});
+        if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) push({&coef, &s_scalar, &s_dev});
     } else if (r.op == OP_BOX_SSPRK33) {
         push({&nodes, &n, &ld, &in, &out, &coef, &s_scalar, &s_dev, &dt, &n_steps});
     } else {
@@ -357,15 +374,24 @@ int rainshaft_rhs_unfused(const cloudy_plan *plan, const LaunchReq &r) {
 // stream-ordered pool (hipMallocAsync / hipFreeAsync) about one call in five came back wrong on a box (garbage in ~1000 of 13500
 // values of the 5-mode, 300-cell case of test_column_integrator_picks_a_workgroup_size_whose_lds_fits), as cloudy_closure_stats'
 // rows did.  (Replaying one captured step as a graph was measured slower than these eager launches: DESIGN 7 (4).)
+// OP_RAINSHAFT_COND_SSPRK33 (cloudy_rainshaft_cond_ssprk33_steps where no fused unit serves it): the same steps with the third
+// source added into the tendency -- per stage the clamp of the stage argument in place (what the reference's rhs does to it, and
+// what the update launch would do: the condensation term has to see it done), the column RHS, a cond_evap launch on the clamped
+// state and an add; a fourth scratch array holds the condensation tendency.
 int rainshaft_staged_steps(const cloudy_plan *plan, const LaunchReq &r) {
     const HostPlan &h = plan->h;
+    const bool cond = r.op == OP_RAINSHAFT_COND_SSPRK33;
     const size_t n = r.n, ld = r.ld, bytes = (size_t)h.nmom * ld * (h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double));
     hipError_t e = hipSuccess;
     if (r.out != r.in) e = hipMemcpyAsync(r.out, r.in, bytes, hipMemcpyDeviceToDevice, r.stream);
     char *ws = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void **)&ws, 3 * bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws, (cond ? 4 : 3) * bytes);
     if (e != hipSuccess) return fail_hip(e, "scratch of the stage-by-stage column integrator");
-    void *up = ws, *f = ws + bytes, *flux = ws + 2 * bytes;
+    void *up = ws, *f = ws + bytes, *flux = ws + 2 * bytes, *g_cond = ws + 3 * bytes;
+    LaunchReq ce(OP_COND, n, ld, r.out, g_cond, r.stream);
+    ce.coef = r.coef;
+    ce.s_scalar = r.s_scalar;
+    ce.s_dev = r.s_dev;
     LaunchReq rhs(OP_RAINSHAFT_RHS, n, ld, r.out, f, r.stream);
     rhs.rainshaft = 1;
     rhs.out2 = flux;
@@ -382,16 +408,76 @@ int rainshaft_staged_steps(const cloudy_plan *plan, const LaunchReq &r) {
                                (double *)r.out, (const double *)f, r.dt);
         return hipGetLastError();
     };
+    const auto add_cond = [&]() -> hipError_t {
+        if (h.dtype != CLOUDY_F64)
+            hipLaunchKernelGGL(rainshaft_add_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, planes, (float *)f,
+                               (const float *)g_cond);
+        else
+            hipLaunchKernelGGL(rainshaft_add_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, planes, (double *)f,
+                               (const double *)g_cond);
+        return hipGetLastError();
+    };
     int rc = CLOUDY_OK;
     for (int step = 0; step < r.n_steps && rc == CLOUDY_OK && e == hipSuccess; ++step)
         for (int sidx = 0; sidx < 3 && rc == CLOUDY_OK && e == hipSuccess; ++sidx) {
-            rc = launch(plan, rhs);
-            if (rc == CLOUDY_OK) e = stage(sidx);
+            if (cond) e = stage(3);
+            if (e == hipSuccess) rc = launch(plan, rhs);
+            if (cond && rc == CLOUDY_OK && e == hipSuccess) rc = launch(plan, ce);
+            if (cond && rc == CLOUDY_OK && e == hipSuccess) e = add_cond();
+            if (rc == CLOUDY_OK && e == hipSuccess) e = stage(sidx);
         }
     if (rc == CLOUDY_OK && e == hipSuccess && r.n_steps > 0) e = stage(3);
     (void)hipFree(ws);   // (waits for the steps)
     if (rc != CLOUDY_OK) return rc;
     if (e != hipSuccess) return fail_hip(e, "stage-by-stage column integrator");
+    return CLOUDY_OK;
+}
+
+// cloudy_rainshaft_cond_rhs without a column unit: rainshaft_rhs_unfused + cond_evap + an add.  The column RHS clamps its
+// argument itself and the caller's moments are const, so the condensation launch reads a clamped copy; plain allocations, as
+// rainshaft_staged_steps says.
+int rainshaft_cond_rhs_unfused(const cloudy_plan *plan, const LaunchReq &r) {
+    const HostPlan &h = plan->h;
+    const bool f32 = h.dtype != CLOUDY_F64;
+    const size_t n = r.n, ld = r.ld, bytes = (size_t)h.nmom * ld * (f32 ? sizeof(float) : sizeof(double));
+    char *ws = nullptr;
+    hipError_t e = hipMalloc((void **)&ws, 2 * bytes);
+    if (e != hipSuccess) return fail_hip(e, "scratch of the unfused column right-hand side with condensation");
+    void *uc = ws, *g_cond = ws + bytes;
+    const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
+    e = hipMemcpyAsync(uc, r.in, bytes, hipMemcpyDeviceToDevice, r.stream);
+    if (e == hipSuccess) {   // (stage 3 of the update kernel is the clamp)
+        if (f32)
+            hipLaunchKernelGGL(rainshaft_stage_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, 3, n, ld, h.nmom, (float *)nullptr,
+                               (float *)uc, (const float *)nullptr, 0.0);
+        else
+            hipLaunchKernelGGL(rainshaft_stage_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, 3, n, ld, h.nmom, (double *)nullptr,
+                               (double *)uc, (const double *)nullptr, 0.0);
+        e = hipGetLastError();
+    }
+    int rc = CLOUDY_OK;
+    if (e == hipSuccess) {
+        LaunchReq ce(OP_COND, n, ld, uc, g_cond, r.stream);
+        ce.coef = r.coef;
+        ce.s_scalar = r.s_scalar;
+        ce.s_dev = r.s_dev;
+        rc = launch(plan, ce);
+        LaunchReq rhs = r;
+        rhs.op = OP_RAINSHAFT_RHS;
+        if (rc == CLOUDY_OK) rc = launch(plan, rhs);
+        if (rc == CLOUDY_OK) {
+            if (f32)
+                hipLaunchKernelGGL(rainshaft_add_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, h.nmom, (float *)r.out,
+                                   (const float *)g_cond);
+            else
+                hipLaunchKernelGGL(rainshaft_add_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, h.nmom, (double *)r.out,
+                                   (const double *)g_cond);
+            e = hipGetLastError();
+        }
+    }
+    (void)hipFree(ws);   // (waits for the launches)
+    if (rc != CLOUDY_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "unfused column right-hand side with condensation");
     return CLOUDY_OK;
 }
 
@@ -408,6 +494,14 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_ssprk33_steps with the condensation source runs the kernel compiled for the plan "
                                          "(hiprtc); plan-time compilation is off or failed: %s",
                     plan->jit_on ? jit_unit(plan, JIT_BOX).log.c_str() : plan->jit[JIT_MAIN].log.c_str());
+    if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
+        if (rainshaft_cond_staged(plan->h, r.nz))
+            return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
+        return fail(CLOUDY_EUNSUPPORTED, "the column kernels with the condensation source are compiled for the plan (hiprtc); "
+                                         "plan-time compilation is off or failed: %s",
+                    plan->jit_on ? jit_unit(plan, jit_cond_unit(jit_rainshaft_part(plan->h, r.nz, r.n / r.nz))).log.c_str()
+                                 : plan->jit[JIT_MAIN].log.c_str());
+    }
     if (r.op == OP_RAINSHAFT_RHS) return rainshaft_rhs_unfused(plan, r);
     if (r.op == OP_RAINSHAFT_SSPRK33 && rainshaft_staged(plan, r.nz, r.n / r.nz)) return rainshaft_staged_steps(plan, r);
     if (r.op == OP_COAL && r.rainshaft && r.out2) {
@@ -454,6 +548,9 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
         return fail(CLOUDY_EUNSUPPORTED,
                     "NumericalCoalStyle plans serve cloudy_coal_rhs / cloudy_get_coal_ints / cloudy_ssprk33_steps and the "
                     "per-mode diagnostics; thresholds and the rainshaft body belong to AnalyticalCoalStyle plans");
+    if ((r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) && plan->h.dtype == CLOUDY_F32_FAST)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_rainshaft_cond_* serve CLOUDY_F64, CLOUDY_F64_RELAXED and CLOUDY_F32 plans (the fused "
+                                         "integrators keep the state in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode)");
     if (r.op == OP_BOX_SSPRK33) {
         if (r.sources < 1 || r.sources > (SRC_COAL | SRC_COND))
             return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COAL, CLOUDY_SRC_COND or both", r.sources);
@@ -1198,6 +1295,62 @@ int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_
     r.n_steps = n_steps;
     r.nz = nz;
     r.dz = dz;
+    return run(plan, r);
+}
+
+// the folded coefficient of get_cond_evap, as cloudy_cond_evap forms it: xi_normalized = p.xi / norms[2]^(2/3)
+// (box_model_helpers.jl:65); rho_l = 1000 (Condensation.jl:26)
+static double cond_coef(const cloudy_plan *plan, double xi) {
+    const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
+    return 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
+}
+
+// (a quadrature plan carries no velocity terms: told what it lacks first, not that)
+static const char kNoNumericalColumns[] = "the column body belongs to AnalyticalCoalStyle plans: NumericalCoalStyle plans are not served";
+
+int cloudy_rainshaft_cond_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *mom_dev,
+                              const double *s_dev, double s, double xi, double dz, void *flux_work_dev, void *rhs_dev, void *stream) {
+    const size_t n = nz * n_columns;
+    int rc = check_batch(plan, n, ld, mom_dev, rhs_dev);
+    if (rc) return rc;
+    if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
+    if (!(xi == xi)) return fail(CLOUDY_EINVAL, "xi must not be NaN");
+    if (!flux_work_dev && n > 0) return fail(CLOUDY_EINVAL, "device buffer is NULL");
+    if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL) return fail(CLOUDY_EUNSUPPORTED, kNoNumericalColumns);
+    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
+    LaunchReq r(OP_RAINSHAFT_COND_RHS, n, ld, mom_dev, rhs_dev, stream);
+    r.rainshaft = 1;
+    r.out2 = flux_work_dev;
+    r.nz = nz;
+    r.dz = dz;
+    r.coef = cond_coef(plan, xi);
+    r.s_scalar = s;
+    r.s_dev = s_dev;
+    return run(plan, r);
+}
+
+int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev,
+                                        void *u_out_dev, const double *s_dev, double s, double xi, double dz, double dt, int n_steps,
+                                        void *stream) {
+    const size_t n = nz * n_columns;
+    int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
+    if (rc) return rc;
+    if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
+    if (n_steps < 0 || !(dt == dt) || !(xi == xi)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0, dt and xi not NaN");
+    if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL) return fail(CLOUDY_EUNSUPPORTED, kNoNumericalColumns);
+    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
+    // (deliberately no FixedThreshold check here or in cloudy_rainshaft_cond_rhs: cloudy_rainshaft_ssprk33_steps refuses
+    // MovingThreshold plans because the reference has no such driver; these entries serve them stage by stage, see the header)
+    if (n == 0) return CLOUDY_OK;   // (as cloudy_rainshaft_ssprk33_steps; run() would return here as well, before any unit is loaded)
+    LaunchReq r(OP_RAINSHAFT_COND_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
+    r.rainshaft = 1;
+    r.dt = dt;
+    r.n_steps = n_steps;
+    r.nz = nz;
+    r.dz = dz;
+    r.coef = cond_coef(plan, xi);
+    r.s_scalar = s;
+    r.s_dev = s_dev;
     return run(plan, r);
 }
 

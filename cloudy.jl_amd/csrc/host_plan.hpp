@@ -50,7 +50,9 @@ enum Op {
     OP_COAL = 0, OP_UPDATE_DIST = 1, OP_FINITE_2D = 2, OP_SEDI = 3, OP_SSPRK33 = 4, OP_COND = 5,
     OP_PREPARE = 6 /* plan creation: upload the constant block */, OP_NQ = 7, OP_RAINSHAFT_SSPRK33 = 8, OP_TSIT5 = 9,
     OP_RAINSHAFT_RHS = 10 /* one evaluation of the column right-hand side (cloudy_rainshaft_rhs) */,
-    OP_BOX_SSPRK33 = 11 /* fused SSPRK33 steps with the condensation source (cloudy_box_ssprk33_steps, box_sources.hpp) */
+    OP_BOX_SSPRK33 = 11 /* fused SSPRK33 steps with the condensation source (cloudy_box_ssprk33_steps, box_sources.hpp) */,
+    OP_RAINSHAFT_COND_SSPRK33 = 12 /* the column integrator with the condensation source (cloudy_rainshaft_cond_ssprk33_steps) */,
+    OP_RAINSHAFT_COND_RHS = 13 /* one evaluation of the column right-hand side with it (cloudy_rainshaft_cond_rhs) */
 };
 
 struct LaunchReq {
@@ -66,8 +68,8 @@ struct LaunchReq {
     hipStream_t stream;
     double dt = 0.0;  // OP_SSPRK33, OP_TSIT5, OP_RAINSHAFT_SSPRK33, OP_BOX_SSPRK33
     int n_steps = 0;  // likewise
-    double coef = 0.0, s_scalar = 0.0;  // OP_COND, OP_BOX_SSPRK33
-    const double *s_dev = nullptr;      // OP_COND, OP_BOX_SSPRK33 (optional per-parcel supersaturation)
+    double coef = 0.0, s_scalar = 0.0;  // OP_COND, OP_BOX_SSPRK33, OP_RAINSHAFT_COND_*
+    const double *s_dev = nullptr;      // OP_COND, OP_BOX_SSPRK33, OP_RAINSHAFT_COND_* (optional per-parcel supersaturation)
     int sources = 0;                    // OP_BOX_SSPRK33: CLOUDY_SRC_* bits
     size_t nz = 0;    // OP_RAINSHAFT_*: cells per column (n = nz * n_columns)
     double dz = 0.0;  // OP_RAINSHAFT_*

@@ -1573,6 +1573,42 @@ __global__ void __launch_bounds__(kBlock)
     sedi_flux_body<N, P, TIO>(A, S, n, ld, in, out);
 }
 
+// get_cond_evap (Condensation.jl:22-37) for one parcel, by the formulas of cond_evap_body:
+//   d(M_j)/dt = coef s j M_{j - 2/3}   (0-based order j; zero for j = 0),   coef = 3 xi_normalised (4 pi/3)^(2/3) / rho_l^(1/3)
+// with M_{1/3} of the Gamma family from the log-gamma ratio and M_{4/3} = M_{1/3} theta (k + 1/3); Lognormal (theta = mu,
+// k = sigma) and Monodisperse modes from their closed forms.  (n, theta, k) are the normalised closure parameters; the tendency
+// comes back in the units the caller keeps its state in: normalised (PHYSICAL = false), or times out_scale = mom_norms.
+// Planes a mode does not carry (order 2 of a two-moment mode) get zero.
+// Where cond_evap_body calls log / exp for the Gamma family, this calls log_pos / exp_fin of device_math.hpp (about 32 and 19
+// VALU instructions where the library routines have about 95 and 31: this runs N times per stage).  Their domains hold:
+// invert_closure hands back theta > 0 whenever n > 0 and (0, 1, 1) otherwise, so log_pos sees a positive finite argument
+// (log_pos(0) would be a finite value, not -Inf, but theta = 0 does not reach it), and the exponent q ln(theta) + lgamma ratio
+// of a k within [k_min, k_max] is far inside exp_fin's range.  The results differ from cond_evap_body's by roundings only.
+template <int N, int P, bool PHYSICAL>
+__device__ __forceinline__ void cond_evap_parcel(const KArgs<N, P> &A, double coef, double sv, const double (&nn)[N],
+                                                 const double (&th)[N], const double (&kk)[N], double (&f)[N][3]) {
+    const double cs = coef * sv;
+#pragma unroll
+    for (int m = 0; m < N; ++m) {
+        const int dtp = A.dist_type[m];
+        const bool gam = (dtp == DIST_GAMMA || dtp == DIST_EXP);
+        const double lnth = (dtp == DIST_LOGNORMAL) ? th[m] : log_pos(th[m]);
+        f[m][0] = f[m][1] = f[m][2] = 0.0;
+        double mom = 0.0;
+#pragma unroll
+        for (int j = 1; j < 3; ++j) {
+            if (j >= A.np[m]) continue;
+            const double q = double(j) - 2.0 / 3.0;
+            if (gam)
+                mom = (j == 1) ? nn[m] * exp_fin(fma(q, lnth, log_gamma_ratio(kk[m], q))) : mom * (th[m] * (kk[m] + (q - 1.0)));
+            else
+                mom = nn[m] * exp((dtp == DIST_MONO) ? q * lnth : fma(q, lnth, 0.5 * q * q * (kk[m] * kk[m])));
+            const double v = cs * double(j) * mom;
+            f[m][j] = PHYSICAL ? v * A.out_scale[3 * m + j] : v;
+        }
+    }
+}
+
 // solve(ODEProblem(make_rainshaft_rhs(...), m, tspan, p), SSPRK33(), dt) of the rainshaft drivers
 // (test/examples/Analytical/rainshaft_gamma_mixture.jl:59-60, rainshaft_helpers.jl:45-89) for many independent
 // columns of nz <= kBlock cells: a workgroup owns floor(kBlock / nz) whole columns, the state stays in registers over
@@ -1587,11 +1623,18 @@ __global__ void __launch_bounds__(kBlock)
 // boundary of the rainshaft drivers -- in one launch: u_out receives coal_source .+ sedi_source of the (clamped) state, flux_out
 // the cell fluxes.  The same stage as the integrator's without the update and without anything parked (cloudy_rainshaft_rhs
 // otherwise runs the cell kernel and a divergence launch: 2.9 GB of HBM traffic per 1e7 cells instead of 1.4).
-template <int N, int P, int MODE, typename TIO, bool SPEC = false, int BS = kRainshaftBlock, bool RHS_ONLY = false>
+// COND: the third source of the column, condensation / evaporation in air with a supersaturation profile
+// (cloudy_rainshaft_cond_ssprk33_steps, cloudy_rainshaft_cond_rhs): get_cond_evap (Condensation.jl:22-37) of the clamped state,
+// formed by cond_evap_parcel after the passes, beside the sedimentation flux, from the same (n, theta, k) -- for every cell, the
+// empty ones included (their fallback distribution (0, 1, 1) gives zero) -- and added last: (coal scale + divergence) + cond.
+// The cell's supersaturation s_dev[col nz + iz] (NULL: s_scalar) is read again in every stage, after the passes, through the
+// re-derived place: nothing more is live across them.  Without COND the three arguments are unused and the code is what it was.
+template <int N, int P, int MODE, typename TIO, bool SPEC = false, int BS = kRainshaftBlock, bool RHS_ONLY = false, bool COND = false>
 __device__ __forceinline__ void rainshaft_ssprk33_body(const KArgs<N, P> *__restrict__ Ag, const SediArgs *__restrict__ Sg,
                                                        const double *__restrict__ nodes, int nz, size_t n_columns,
                                                        size_t ld, const TIO *u_in, TIO *u_out, double dt, double dz,
-                                                       int n_steps, TIO *flux_out = nullptr) {
+                                                       int n_steps, TIO *flux_out = nullptr, double coef = 0.0,
+                                                       double s_scalar = 0.0, const double *__restrict__ s_dev = nullptr) {
     // (workgroup sizes that were measured and dropped, 20-cell columns: 384 threads 40 % slower, 320 threads 40 % slower --
     // six- and five-wave workgroups do not spread evenly over four SIMDs; 128 threads 8 % slower, the ranking over 128 cells
     // is too coarse)
@@ -1713,6 +1756,15 @@ __device__ __forceinline__ void rainshaft_ssprk33_body(const KArgs<N, P> *__rest
                     for (int q = 0; q < 3; ++q)  // (the lane reads its own flux back after the barrier as well: not kept)
                         fx[3 * m + q][pp] = (q < Af.np[m]) ? fl[m][q] * Af.out_scale[3 * m + q] : 0.0;
             }
+            double fc[COND ? N : 1][3];   // the condensation tendency of the lane's own cell, physical units
+            if constexpr (COND) {
+#pragma unroll
+                for (int m = 0; m < N; ++m) fc[m][0] = fc[m][1] = fc[m][2] = 0.0;
+                if (active2) {
+                    const size_t ic = ((size_t)blockIdx.x * cpb + cl2) * (size_t)nz + iz2;   // the cell, not the ranking's parcel
+                    cond_evap_parcel<N, P, true>(Af, coef, s_dev ? s_dev[ic] : s_scalar, nn, th, kk, fc);
+                }
+            }
             CLOUDY_STAGE_BARRIER();
             if (kParkState) {
 #pragma unroll
@@ -1734,7 +1786,8 @@ __device__ __forceinline__ void rainshaft_ssprk33_body(const KArgs<N, P> *__rest
                         const double f_up = top ? 0.0 : fx[3 * m + q][pp + 1];
                         const double fd = -(f_up - fx[3 * m + q][pp]) / dz;  // :83-85
                         // coal_source .+ sedi_source (:88), empty cells skip coalescence (:67-72)
-                        const double ft = ((q < Af.np[m] && !small2) ? acc[m][q] * Af.out_scale[3 * m + q] : 0.0) + fd;
+                        double ft = ((q < Af.np[m] && !small2) ? acc[m][q] * Af.out_scale[3 * m + q] : 0.0) + fd;
+                        if constexpr (COND) ft += fc[m][q];
                         if (RHS_ONLY) {
                             u[m][q] = ft;
                         } else {

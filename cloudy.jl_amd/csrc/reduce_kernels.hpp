@@ -161,6 +161,19 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// a += b on the planes: the condensation tendency added into the column right-hand side where no fused unit serves the call
+// (cloudy_rainshaft_cond_*, stage by stage): (coal + divergence) + cond, the order of the fused kernels
+template <typename TIO>
+__global__ void __launch_bounds__(kBlock)
+    rainshaft_add_kernel(size_t n, size_t ld, int planes, TIO *__restrict__ a, const TIO *__restrict__ b) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    for (int q = 0; q < planes; ++q) {
+        const size_t e = (size_t)q * ld + i;
+        a[e] = (TIO)((double)a[e] + (double)b[e]);
+    }
+}
+
 // One SSPRK33 stage update of the staged column stepping (cloudy_rainshaft_ssprk33_steps for columns too tall for the fused
 // kernel): OrdinaryDiffEq's formulas on the CLAMPED stage argument -- the reference's rhs clamps negative moments of its argument
 // in place before it evaluates (rainshaft_helpers.jl:52), and f = rhs(u) was computed on the clamped values.

@@ -41,6 +41,11 @@
  *   cloudy_box_ssprk33_steps      <- solve(ODEProblem(rhs!, ...), SSPRK33(), dt = ...) with rhs! = rhs_condensation! (or the sum
  *                                    of rhs_coal! and it), test/examples/Analytical/condensation_single_gamma.jl:28,
  *                                    condensation_exp_gamma.jl:31
+ *   cloudy_rainshaft_cond_rhs     <- rhs(m, p, t) of make_rainshaft_rhs (test/examples/utils/rainshaft_helpers.jl:45-89) plus
+ *                                    get_cond_evap of each cell (src/Sources/Condensation.jl:22-37, as rhs_condensation!,
+ *                                    test/examples/utils/box_model_helpers.jl:55-67): the three sources of a column
+ *   cloudy_rainshaft_cond_ssprk33_steps <- solve(ODEProblem(that rhs, m, tspan, p), SSPRK33(), dt = p.dt), the stepping of
+ *                                    test/examples/Analytical/rainshaft_gamma_mixture.jl:59-60 with the third source
  *   cloudy_moment_sums            <- moments_sum diagnostic, test/examples/utils/plotting_helpers.jl:240-252
  *   cloudy_moment_sums_allreduce  <- the same summed over the ranks / GPUs that share a batch (RCCL; the reference is
  *                                    single-process, its global sum is the local one)
@@ -373,6 +378,43 @@ int cloudy_rainshaft_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, s
 int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld,
                                    const void *u_in_dev, void *u_out_dev, double dz, double dt, int n_steps,
                                    void *stream);
+
+/* The column right-hand side with all three sources, for columns through air with a supersaturation profile (rain that
+ * evaporates below the cloud layer).  One evaluation on n_columns independent columns of nz cells is
+ *     clamp m to >= 0                                              (rainshaft_helpers.jl:52)
+ *     f = coal_source(m) [skipped for empty cells, :67-72]
+ *       + upwind divergence of the sedimentation flux              (as cloudy_rainshaft_rhs, :80-86)
+ *       + get_cond_evap(update_dist_from_moments(m), s_cell, xi)   (Condensation.jl:22-37, as cloudy_cond_evap on the clamped m)
+ * summed in this order.  The condensation term is formed for every cell from the same closure inversion as the other two (an
+ * empty cell's fallback distribution gives zero).  s_dev holds one fp64 supersaturation per cell in the cell order of the state
+ * (cell col * nz + iz; always fp64, whatever the plane type), constant over the call, or is NULL to use the scalar `s`; xi and
+ * rho_l = 1000 as in cloudy_cond_evap.  flux_work_dev as in cloudy_rainshaft_rhs.  With s = 0 or xi = 0 the result equals
+ * cloudy_rainshaft_rhs's.
+ * One launch for columns of up to 1024 cells: the kernels are compiled for the plan on the first call that needs them
+ * (cloudy_jit_rainshaft_cond_*, one unit per workgroup size of 256 / 512 / 1024 threads, picked as cloudy_rainshaft_rhs picks);
+ * there are no ahead-of-time instances, so without plan-time compilation such a call answers CLOUDY_EUNSUPPORTED with the
+ * compiler's log.  Where no workgroup can hold a column -- nz > 1024, LDS rows of the plan that fit no workgroup size that
+ * holds a column, MovingThreshold plans (which these two entries accept, unlike cloudy_rainshaft_rhs) -- the library runs the
+ * unfused form: the cell kernel, the divergence launch, a cloudy_cond_evap launch on a clamped copy and an add, with two scratch
+ * arrays of the state's size per call.
+ * Refusals: NULL plan, NaN xi, nz < 1, dz <= 0, a plan without terminal-velocity terms: CLOUDY_EINVAL; NumericalCoalStyle plans
+ * and CLOUDY_F32_FAST planes: CLOUDY_EUNSUPPORTED (CLOUDY_F64, CLOUDY_F64_RELAXED and CLOUDY_F32 are served). */
+int cloudy_rainshaft_cond_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *mom_dev,
+                              const double *s_dev, double s, double xi, double dz, void *flux_work_dev, void *rhs_dev,
+                              void *stream);
+
+/* n_steps SSPRK33 steps of that right-hand side with fixed dt: cloudy_rainshaft_ssprk33_steps with the third source.  The
+ * clamp is part of every evaluation, the FSAL one included, so the returned state is clamped; OrdinaryDiffEq's update
+ * formulas.  One launch for nz <= 1024: the column integrator's body with the condensation term formed after the Simpson
+ * passes, beside the sedimentation flux, from the (n, theta, k) of the lane's own cell; the cell's supersaturation is read again
+ * in every stage (8 bytes per cell and stage), nothing more is live across the passes.  u_out_dev may equal u_in_dev; n_steps = 0
+ * copies the input to the output.  The cases without a fused kernel (see above) are stepped stage by stage inside the library
+ * as cloudy_rainshaft_ssprk33_steps steps tall columns, with a cloudy_cond_evap launch per stage added into the tendency (four
+ * scratch arrays of the state's size per call).  Refusals as above, and n_steps < 0 or a NaN dt: CLOUDY_EINVAL.  With s = 0 or
+ * xi = 0 the result equals cloudy_rainshaft_ssprk33_steps's. */
+int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld,
+                                        const void *u_in_dev, void *u_out_dev, const double *s_dev, double s, double xi,
+                                        double dz, double dt, int n_steps, void *stream);
 
 /* sums_dev[q] = sum over parcels of plane q (fp64 accumulate); `planes` planes are reduced.
  * The multi-GPU conservation check all-reduces these nmom doubles (RCCL), see INTEGRATION.md. */

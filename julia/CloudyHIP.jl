@@ -404,6 +404,44 @@ function solve_rainshaft_ssprk33!(u, plan::Plan, nz, dz, dt, n_steps; stream = n
     return u
 end
 
+"""
+    solve_rainshaft_cond_ssprk33!(u, plan, nz, dz, dt, n_steps, xi, s; stream = nothing, sync = true)
+
+`solve_rainshaft_ssprk33!` for columns through air with a supersaturation profile: the right-hand side of
+`make_rainshaft_rhs` plus `get_cond_evap` (src/Sources/Condensation.jl:22-37) of every cell, one closure inversion per stage
+for the three sources (`cloudy_rainshaft_cond_ssprk33_steps`).  `xi` = `p.ξ`; `s` a number, or a device `Vector{Float64}` with
+one supersaturation per cell in the cell order of `u`, constant over the call.
+"""
+function solve_rainshaft_cond_ssprk33!(u, plan::Plan, nz, dz, dt, n_steps, xi, s; stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(u, plan.nmom)
+    st = stream === nothing ? current_stream() : stream
+    s_dev = s isa Number ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(s))
+    s_val = s isa Number ? Float64(s) : 0.0
+    check(ccall((:cloudy_rainshaft_cond_ssprk33_steps, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Ptr{Cvoid}),
+                plan.handle, nz, n ÷ nz, ld, pointer(u), pointer(u), s_dev, s_val, xi, dz, dt, n_steps, st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return u
+end
+
+"""
+    rainshaft_cond_rhs!(dm, flux, m, plan, nz, dz, xi, s; stream = nothing, sync = true)
+
+One evaluation of that right-hand side on device arrays (`cloudy_rainshaft_cond_rhs`): `dm` receives the tendency of the
+clamped `m`, `flux` the cell fluxes.
+"""
+function rainshaft_cond_rhs!(dm, flux, m, plan::Plan, nz, dz, xi, s; stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(m, plan.nmom)
+    st = stream === nothing ? current_stream() : stream
+    s_dev = s isa Number ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(s))
+    s_val = s isa Number ? Float64(s) : 0.0
+    check(ccall((:cloudy_rainshaft_cond_rhs, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                plan.handle, nz, n ÷ nz, ld, pointer(m), s_dev, s_val, xi, dz, pointer(flux), pointer(dm), st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return dm
+end
+
 # ---- multi-GPU: the conservation diagnostic summed over ranks (moments_sum, plotting_helpers.jl:240-252) ------------
 # One Julia process per GPU (MPI.jl / Distributed.jl own the processes): rank 0 draws the id, the host broadcasts its
 # 128 bytes, every rank forms the communicator; the all-reduce itself is RCCL inside the library.

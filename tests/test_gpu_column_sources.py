@@ -1,0 +1,476 @@
+"""GPU tests of the column entry points with the third source (cloudy_rainshaft_cond_ssprk33_steps, cloudy_rainshaft_cond_rhs):
+coalescence + sedimentation + condensation / evaporation for columns through air with a supersaturation profile -- supersaturated
+in the cloud layer, subsaturated below it, so that the rain evaporates on its way down.
+
+The oracle stepping is _oracle_rainshaft_ssprk33 of test_gpu_parity.py with oracle.rhs_condensation_batch(op, xi, s, x) added
+inside the right-hand side after the clamp.  The device's own stage-by-stage sequence is driven from the host through
+cloudy_rainshaft_rhs + cloudy_cond_evap on the clamped state.  Run with `-m gpu`."""
+import numpy as np
+import pytest
+
+import bench
+from test_gpu_parity import EPS, INF, TOL_POLY, dev, make_case, run_rhs
+
+pytestmark = pytest.mark.gpu
+
+XI = 1e-8
+VEL = ((50.0, 1.0 / 6),)
+GOLOVIN = [[EPS / 1e6, 5.0], [5.0, 0.0]]
+NZ, DZ, DT, N_STEPS, NCOL = 20, 150.0, 1.0, 40, 27   # 25 columns per 512-thread workgroup at 20 cells: 27 spill into a second one
+SENTINEL = np.float64(np.nan).view(np.uint64) | np.uint64(0x5EED)   # a NaN no arithmetic produces
+_CACHE = {}
+
+
+def supersaturation(nz, dz, ncol):
+    """one value per cell in the cell order of the state (cell col * nz + iz): 0.03 in the cloud layer (z >= 1350 m), -0.2 below,
+    scaled by a factor that differs from column to column -- a wrong cell-to-s mapping cannot pass"""
+    z = (np.arange(nz) + 0.5) * dz
+    prof = np.where(z >= 1350.0, 0.03, -0.2)
+    return np.concatenate([(0.5 + 0.05 * c) * prof for c in range(ncol)])
+
+
+def reference_case(cloudy, oracle, case):
+    """par, op, dist_types, amp of the two configurations of test_rainshaft_column_integrator_ssprk33"""
+    if case == "gamma_mixture":   # rainshaft_gamma_mixture.jl:15-60: the ranked body
+        dist_types, thr, amp = [1, 1], (2e-10, INF), np.array([1e7, 1e-3, 2e-13, 0.0, 0.0, 0.0])
+    else:                         # rainshaft_single_gamma.jl: the all-Inf body
+        dist_types, thr, amp = [1], (INF,), np.array([1e7, 1e-3, 2e-13])
+    par, op, _ = make_case(cloudy, oracle, dist_types, GOLOVIN, thr, bench.NORMS, vel=VEL)
+    par.dz, par.nz, par.dt = DZ, NZ, DT
+    return par, op, dist_types, amp
+
+
+def column_set(amp):
+    """the columns of test_rainshaft_column_integrator_ssprk33 (scaled slabs, the slab touching the top, the cell with -1e-30),
+    extended to 27 columns"""
+    z = (np.arange(NZ) + 0.5) * DZ
+    at = ((z >= 0.5 * z.max() - DZ / 2) & (z < 0.75 * z.max() - DZ / 2)).astype(float)
+    cols = [np.outer(amp * s, at) for s in (1.0, 0.3, 3.0)]
+    shifted = np.outer(amp, np.roll(at, 3))
+    dirty = np.outer(amp, at)
+    dirty[:, 2] = -1e-30
+    cols += [shifted, dirty] + [np.outer(amp * (0.5 + 0.1 * i), at) for i in range(NCOL - 5)]
+    return np.ascontiguousarray(np.concatenate(cols, axis=1))
+
+
+def oracle_stepping(oracle, op, u, nz, dz, dt, n_steps, xi, s):
+    """_oracle_rainshaft_ssprk33 with the condensation term of the clamped state added inside the right-hand side"""
+    nmom, n = u.shape
+
+    def f(x):
+        np.maximum(x, 0.0, out=x)
+        cs, sf = oracle.rainshaft_cell_batch(op, x)
+        out = np.empty_like(x)
+        for c in range(n // nz):
+            sl = slice(c * nz, (c + 1) * nz)
+            fl = np.concatenate([sf[:, sl], np.zeros((nmom, 1))], axis=1)
+            out[:, sl] = cs[:, sl] + (-(fl[:, 1:] - fl[:, :-1]) / dz)
+        return out + oracle.rhs_condensation_batch(op, xi, s, x)
+
+    u = u.copy()
+    for _ in range(n_steps):
+        k = f(u)
+        up = u
+        u = up + dt * k
+        k = f(u)
+        u = (3.0 * up + u + dt * k) / 4.0
+        k = f(u)
+        u = (up + 2.0 * u + 2.0 * dt * k) / 3.0
+        np.maximum(u, 0.0, out=u)
+    return u
+
+
+def shared(cloudy, oracle, case):
+    """the setup of test (1), its oracle end state and the fused fp64 results with and without the source: computed once"""
+    if case not in _CACHE:
+        par, op, dist_types, amp = reference_case(cloudy, oracle, case)
+        u0 = column_set(amp)
+        s = supersaturation(NZ, DZ, NCOL)
+        want = oracle_stepping(oracle, op, u0, NZ, DZ, DT, N_STEPS, XI, s)
+        s_dev = dev(cloudy, s[None, :])
+        ud = dev(cloudy, u0)
+        out = cloudy.DeviceArray.zeros(*u0.shape)
+        assert cloudy.solve_rainshaft_cond_ssprk33(par, ud, N_STEPS, XI, s_dev, out=out) is out
+        plain = cloudy.DeviceArray.zeros(*u0.shape)
+        cloudy.solve_rainshaft_ssprk33(par, ud, N_STEPS, out=plain)
+        for a in (u0, s, want):
+            a.setflags(write=False)
+        _CACHE[case] = dict(par=par, op=op, dist_types=dist_types, amp=amp, u0=u0, s=s, s_dev=s_dev, want=want, got=out.to_numpy(),
+                            plain=plain.to_numpy(), input_after=ud.to_numpy())
+    return _CACHE[case]
+
+
+def host_sequence(cloudy, par, plan, u0, s, n_steps, dt, xi=XI, rhs_fn=None):
+    """the device's own stage-by-stage sequence driven from the host: cloudy_rainshaft_rhs + cloudy_cond_evap on the clamped state,
+    OrdinaryDiffEq's update formulas in numpy (the host loop of test_rainshaft_column_integrator_ssprk33)"""
+    rhs = cloudy.make_rainshaft_rhs()
+    s_dev = dev(cloudy, np.ascontiguousarray(s)[None, :])
+
+    def f(x):
+        np.maximum(x, 0.0, out=x)
+        m = dev(cloudy, x)
+        g = cloudy.DeviceArray.zeros(*x.shape)
+        cloudy.rhs_condensation(plan, g, m, xi, s_dev)
+        base = rhs_fn(x, m) if rhs_fn is not None else rhs(m, par, 0.0).to_numpy()
+        return base + g.to_numpy()
+
+    u = u0.copy()
+    for _ in range(n_steps):
+        up = u
+        u = up + dt * f(up)
+        u = (3.0 * up + u + dt * f(u)) / 4.0
+        u = (up + 2.0 * u + 2.0 * dt * f(u)) / 3.0
+    np.maximum(u, 0.0, out=u)
+    return u
+
+
+@pytest.mark.parametrize("case", ["gamma_mixture", "single_gamma"])
+def test_parity_with_the_oracle(gpu_cloudy, oracle, case):
+    """(1) 40 SSPRK33 steps of the three sources on 27 columns of 20 cells with a supersaturation per cell, the ranked body and the
+    all-Inf body, against the oracle stepping at the bound of the existing column test; the source is visible in every plane that
+    carries mass."""
+    c = shared(gpu_cloudy, oracle, case)
+    got, want = c["got"], c["want"]
+    assert np.array_equal(c["input_after"], c["u0"])     # out-of-place call leaves the input alone
+    ref = np.abs(want).max(axis=1, keepdims=True) + 1e-300
+    err = np.abs(got - want) / ref
+    print(f"column + condensation {case}: {N_STEPS} steps, max |hip-oracle| / max|plane| = {err.max():.2e}")
+    assert err.max() < 1e-9
+    assert got.min() >= 0.0
+    moved = np.abs(got - c["plain"]).max(axis=1) / (np.abs(c["plain"]).max(axis=1) + 1e-300)
+    print(f"column + condensation {case}: the source moves the planes by {moved} of their maxima")
+    mass = np.abs(c["plain"]).max(axis=1) > 0.0
+    assert mass.any() and np.all(moved[mass] > 1e-3)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("case", ["gamma_mixture", "single_gamma"])
+def test_without_supersaturation_the_existing_kernels_bits(gpu_cloudy, oracle, case, dtype):
+    """(2) s = 0 (scalar) and, separately, xi = 0 with the profile of (1): the integrator returns what
+    cloudy_rainshaft_ssprk33_steps returns and the right-hand side what cloudy_rainshaft_rhs returns, rhs and flux planes."""
+    cloudy = gpu_cloudy
+    L = cloudy.lib()
+    c = shared(cloudy, oracle, case)
+    code = 0 if dtype == np.float64 else 1
+    plan = c["par"].coal_data.plan(c["dist_types"], vel=VEL, dtype=code)
+    u0 = c["u0"].astype(dtype)
+    nm, n = u0.shape
+    ud = dev(cloudy, u0)
+    new = lambda: cloudy.DeviceArray.zeros(nm, n, dtype)  # noqa: E731
+    ref = new()
+    cloudy._lib.check(L.cloudy_rainshaft_ssprk33_steps(plan.handle, NZ, NCOL, n, ud.ptr, ref.ptr, DZ, DT, N_STEPS, None))
+    ref = ref.to_numpy()
+    if dtype == np.float64:
+        assert np.array_equal(ref, c["plain"])
+    rr, rf = new(), new()
+    cloudy._lib.check(L.cloudy_rainshaft_rhs(plan.handle, NZ, NCOL, n, ud.ptr, DZ, rf.ptr, rr.ptr, None))
+    rr, rf = rr.to_numpy(), rf.to_numpy()
+    assert np.abs(rr).max() > 0.0
+    for s_ptr, s_val, xi in ((None, 0.0, XI), (c["s_dev"].ptr, 0.0, 0.0)):
+        out = new()
+        cloudy._lib.check(L.cloudy_rainshaft_cond_ssprk33_steps(plan.handle, NZ, NCOL, n, ud.ptr, out.ptr, s_ptr, s_val, xi, DZ, DT,
+                                                                N_STEPS, None))
+        assert np.array_equal(out.to_numpy(), ref), (case, dtype, xi)
+        gr, gf = new(), new()
+        cloudy._lib.check(L.cloudy_rainshaft_cond_rhs(plan.handle, NZ, NCOL, n, ud.ptr, s_ptr, s_val, xi, DZ, gf.ptr, gr.ptr, None))
+        assert np.array_equal(gr.to_numpy(), rr) and np.array_equal(gf.to_numpy(), rf), (case, dtype, xi)
+
+
+@pytest.mark.parametrize("case", ["gamma_mixture", "single_gamma"])
+def test_fused_against_the_stage_by_stage_sequence(gpu_cloudy, oracle, case):
+    """(3) 3 steps on the first two columns of (1) against the host-driven sequence, with the figures of the existing column test;
+    the new right-hand side against cloudy_rainshaft_rhs + cloudy_cond_evap within TOL_POLY of the per-plane maximum of
+    |coal| + |divergence| + |cond|."""
+    cloudy = gpu_cloudy
+    c = shared(cloudy, oracle, case)
+    par, plan = c["par"], c["par"].coal_data.plan(c["dist_types"], vel=VEL)
+    n = 2 * NZ
+    u0, s = c["u0"][:, :n].copy(), c["s"][:n].copy()
+    want = host_sequence(cloudy, par, plan, u0, s, 3, DT)
+    s_dev = dev(cloudy, s[None, :])
+    out = cloudy.DeviceArray.zeros(u0.shape[0], n)
+    cloudy.solve_rainshaft_cond_ssprk33(par, dev(cloudy, u0.copy()), 3, XI, s_dev, out=out)
+    got = out.to_numpy()
+    print(f"fused vs staged {case}: max |diff| / max|u| = {np.abs(got - want).max() / np.abs(want).max():.2e}")
+    assert np.allclose(got, want, rtol=1e-12, atol=1e-13 * np.abs(want).max())
+    # one evaluation, on a state the sources have acted on (clamped: cloudy_cond_evap does not clamp)
+    x = np.maximum(c["got"][:, :n], 0.0)
+    m = dev(cloudy, x)
+    coal, flux = cloudy.rainshaft_sources(plan, m)
+    coal, flux = coal.to_numpy(), flux.to_numpy()
+    div = np.empty_like(flux)
+    for col in range(2):
+        sl = slice(col * NZ, (col + 1) * NZ)
+        fl = np.concatenate([flux[:, sl], np.zeros((flux.shape[0], 1))], axis=1)
+        div[:, sl] = -(fl[:, 1:] - fl[:, :-1]) / DZ
+    cond = cloudy.DeviceArray.zeros(*x.shape)
+    cloudy.rhs_condensation(plan, cond, m, XI, s_dev)
+    cond = cond.to_numpy()
+    work0, work = cloudy.DeviceArray.zeros(*x.shape), cloudy.DeviceArray.zeros(*x.shape)
+    base = cloudy.make_rainshaft_rhs()(m, par, 0.0, work=work0).to_numpy()
+    g = cloudy.make_rainshaft_cond_rhs()(m, par, 0.0, XI, s_dev, work=work).to_numpy()
+    scale = (np.abs(coal) + np.abs(div) + np.abs(cond)).max(axis=1, keepdims=True)
+    err = np.abs(g - (base + cond)) / np.maximum(scale, 1e-300)
+    print(f"column RHS with condensation {case}: max |fused - (rhs + cond)| / plane scale = {err.max():.2e}")
+    assert np.abs(cond).max() > 0.0 and err.max() <= TOL_POLY
+    assert np.array_equal(work.to_numpy(), work0.to_numpy()) and np.allclose(work.to_numpy(), flux, rtol=1e-12, atol=0)
+
+
+def rhs_parts(cloudy, par, plan, x, m, ts=None):
+    """coalescence source and upwind flux divergence of the clamped cells `x` (device copy `m`), separately.  FixedThreshold plans:
+    cloudy_rainshaft_sources.  MovingThreshold plans (`ts`), which that entry refuses: the box operator cloudy_coal_rhs with the
+    empty cells skipped (rainshaft_helpers.jl:67-72: every normalised moment below eps(Float64)) and cloudy_sedimentation_flux."""
+    nz, dz = par.nz, par.dz
+    if ts is None:
+        coal, flux = cloudy.rainshaft_sources(plan, m)
+        coal, flux = coal.to_numpy(), flux.to_numpy()
+    else:
+        nmodes = x.shape[0] // 3
+        norm = np.array([bench.NORMS[0] * bench.NORMS[1] ** q for q in (0, 1, 2)] * nmodes)[:, None]
+        coal = run_rhs(cloudy, par, x, ts)
+        coal[:, (x / norm < EPS).all(axis=0)] = 0.0
+        flux = cloudy.get_sedimentation_flux(plan, m).to_numpy()
+    fl = np.concatenate([flux.reshape(x.shape[0], -1, nz), np.zeros((x.shape[0], x.shape[1] // nz, 1))], axis=2)
+    return coal, (-(fl[:, :, 1:] - fl[:, :, :-1]) / dz).reshape(x.shape)
+
+
+def _tall(cloudy, oracle, nz):
+    par, op, dist_types, amp = reference_case(cloudy, oracle, "gamma_mixture")
+    par.nz, par.dz, par.dt = nz, 3000.0 / nz, 0.05   # (thin cells: the upwind flux needs the smaller step)
+    zt = (np.arange(nz) + 0.5) * par.dz
+    att = ((zt >= 0.5 * zt.max()) & (zt < 0.75 * zt.max())).astype(float)
+    u0 = np.concatenate([np.outer(amp * sc, att) for sc in (1.0, 0.4, 2.0)], axis=1)
+    return par, dist_types, np.ascontiguousarray(u0), None
+
+
+def _five_modes(cloudy, oracle, nz=300, ncol=3):
+    """the plan construction of test_column_integrator_picks_a_workgroup_size_whose_lds_fits for N = 5"""
+    N = 5
+    thr = tuple(10.0 ** (-10 + i) for i in range(N - 1)) + (INF,)
+    par, op, _ = make_case(cloudy, oracle, [1] * N, GOLOVIN, thr, bench.NORMS, vel=VEL)
+    par.nz, par.dz, par.dt = nz, 3000.0 / nz, 0.05
+    amp = bench.synth_moments(4, 1, seed=77, degenerate_frac=0.0)[:, 0]
+    amp = np.concatenate([amp] + [amp[9:12] * np.array([0.1, 1.0, 100.0]) * 10.0 ** (m - 3) for m in range(4, N)])[: 3 * N]
+    z = (np.arange(nz) + 0.5) * par.dz
+    at = ((z >= 0.5 * z.max()) & (z < 0.75 * z.max())).astype(float)
+    u0 = np.ascontiguousarray(np.concatenate([np.outer(amp * (0.3 + 0.2 * c), at) for c in range(ncol)], axis=1))
+    return par, [1] * N, u0, None
+
+
+def _moving(cloudy, oracle):
+    """A MovingThreshold two-mode plan.  cloudy_rainshaft_rhs refuses such plans (the reference's make_rainshaft_rhs uses
+    FixedThreshold), so the host-driven right-hand side of this case is put together from the entry points that serve them
+    (rhs_parts)."""
+    par, op, ts = make_case(cloudy, oracle, [1, 1], GOLOVIN, (0.9, 1.0), bench.NORMS, moving=True, vel=VEL)
+    par.nz, par.dz, par.dt = NZ, DZ, DT
+    amp = np.array([1e7, 1e-3, 2e-13, 1e4, 1e-4, 2e-12])
+    u0 = column_set(amp)[:, : 3 * NZ].copy()
+    plan = par.coal_data.plan([1, 1], vel=VEL)
+
+    def rhs_fn(x, m):
+        coal, div = rhs_parts(cloudy, par, plan, x, m, ts)
+        return coal + div
+
+    rhs_fn.ts = ts
+    return par, [1, 1], u0, rhs_fn
+
+
+@pytest.mark.parametrize("path", ["nz300_512_threads", "nz700_1024_threads", "nz1500_stage_by_stage", "five_modes_no_workgroup_fits",
+                                  "moving_threshold"])
+def test_every_pick_and_every_fallback(gpu_cloudy, oracle, path):
+    """(4) two steps against the host-driven sequence of (3): one column per 512-thread workgroup, 1024 threads, columns taller
+    than a workgroup (stage by stage inside the library), a plan whose LDS rows fit no workgroup size that holds a column, and a
+    MovingThreshold plan.  Supersaturation per cell as in (1), recomputed for the grid.  On the state the steps end in, one
+    evaluation of the new right-hand side (on the last three paths: the unfused form inside the library) against the column
+    right-hand side + cloudy_cond_evap as in (3)."""
+    cloudy = gpu_cloudy
+    if path.startswith("nz"):
+        par, dist_types, u0, rhs_fn = _tall(cloudy, oracle, int(path[2:].split("_")[0]))
+    elif path.startswith("five"):
+        par, dist_types, u0, rhs_fn = _five_modes(cloudy, oracle)
+    else:
+        par, dist_types, u0, rhs_fn = _moving(cloudy, oracle)
+    plan = par.coal_data.plan(dist_types, vel=VEL)
+    ncol = u0.shape[1] // par.nz
+    s = supersaturation(par.nz, par.dz, ncol)
+    want = host_sequence(cloudy, par, plan, u0, s, 2, par.dt, rhs_fn=rhs_fn)
+    out = cloudy.DeviceArray.zeros(*u0.shape)
+    cloudy.solve_rainshaft_cond_ssprk33(par, dev(cloudy, u0.copy()), 2, XI, dev(cloudy, s[None, :]), out=out)
+    got = out.to_numpy()
+    fin = np.isfinite(want)
+    if path.startswith("five"):   # (as the test this plan construction comes from: compared where the sequence is finite)
+        assert fin.mean() > 0.99
+    else:
+        assert fin.all()
+    assert np.array_equal(np.isfinite(got), fin)
+    print(f"{path}: max |diff| / max|u| = {np.abs(got - want)[fin].max() / np.abs(want[fin]).max():.2e}")
+    assert np.allclose(got[fin], want[fin], rtol=1e-12, atol=1e-13 * np.abs(want[fin]).max()), path
+    assert got[fin].min() >= 0.0
+    # the source acted: the same steps without it end elsewhere, by 10^4 x what the comparison above allows
+    plain = cloudy.DeviceArray.zeros(*u0.shape)
+    cloudy.solve_rainshaft_cond_ssprk33(par, dev(cloudy, u0.copy()), 2, XI, 0.0, out=plain)
+    assert np.abs(plain.to_numpy() - got)[fin].max() > 1e-9 * np.abs(want[fin]).max()
+    # one evaluation of the new right-hand side on that state
+    x = np.where(fin, got, 0.0)
+    m, s_dev = dev(cloudy, x), dev(cloudy, s[None, :])
+    ts = getattr(rhs_fn, "ts", None)
+    coal, div = rhs_parts(cloudy, par, plan, x, m, ts)
+    base = coal + div if ts is not None else cloudy.make_rainshaft_rhs()(m, par, 0.0).to_numpy()
+    cond = cloudy.DeviceArray.zeros(*x.shape)
+    cloudy.rhs_condensation(plan, cond, m, XI, s_dev)
+    cond = cond.to_numpy()
+    g = cloudy.make_rainshaft_cond_rhs()(m, par, 0.0, XI, s_dev).to_numpy()
+    assert np.isfinite(g).all() and np.isfinite(base).all() and np.abs(cond).max() > 0.0
+    scale = (np.abs(coal) + np.abs(div) + np.abs(cond)).max(axis=1, keepdims=True)
+    err = np.abs(g - (base + cond)) / np.maximum(scale, 1e-300)
+    print(f"{path}: column RHS with condensation, max |got - (rhs + cond)| / plane scale = {err.max():.2e}")
+    assert err.max() <= TOL_POLY
+    assert np.array_equal(dev(cloudy, x).to_numpy(), x)
+
+
+def test_degenerate_cells_with_the_source_on(gpu_cloudy):
+    """The bench's synthetic cfg3b batch stacked as 100 columns of 20 cells: random parcels as neighbours, zero-variance and
+    empty modes among them (closure clamped at k_min / k_max, fallback distributions).  One evaluation of the fused right-hand
+    side with the source against cloudy_rainshaft_rhs + cloudy_cond_evap, entry by entry: the same finite pattern, and
+    |fused - (rhs + cond)| <= 1e-13 (|rhs| + |cond|).  The bound: on fp64 planes the fused column right-hand side without the source
+    has the bits of cloudy_rainshaft_rhs (test_column_rhs_in_one_launch_matches_the_two_launch_path), so the two sides differ by the
+    roundings of one addition (2.2e-16 of |rhs| + |cond|) and by the two forms of the condensation term, whose exponent
+    q ln(theta) + lgamma ratio stays below about 50 in size for normalised theta within 1e-20 .. 1e20 and is accurate to an ulp of
+    itself in either form: 2 x 50 x 2.2e-16 = 2.2e-14 of |cond|.
+    (Stepping this batch as columns is not compared: the oracle alone moves by more than 1e100 in single entries under a 1e-15
+    perturbation of the input, with or without the source -- DESIGN 3.5.)"""
+    cloudy = gpu_cloudy
+    L = cloudy.lib()
+    nz, ncol, dz = 20, 100, 150.0
+    n = nz * ncol
+    wl = bench.make_workload("cfg3b", n, seed=7)
+    mom = np.maximum(wl["mom"], 0.0)
+    m0, m1, m2 = mom[0::3], mom[1::3], mom[2::3]
+    with np.errstate(all="ignore"):
+        kk = (m1 / m0) / (m2 / m1 - m1 / m0)
+    assert ((kk > 10.0) | (kk < EPS) | ~np.isfinite(kk)).sum() >= 10      # cells whose closure is clamped or falls back
+    plan = wl["coal_data"].plan(wl["dist_types"], vel=VEL)
+    s = dev(cloudy, supersaturation(nz, dz, ncol)[None, :])
+    x = dev(cloudy, mom)
+    fused, base, cond, work = (cloudy.DeviceArray.zeros(*mom.shape) for _ in range(4))
+    cloudy._lib.check(L.cloudy_rainshaft_cond_rhs(plan.handle, nz, ncol, n, x.ptr, s.ptr, 0.0, XI, dz, work.ptr, fused.ptr, None))
+    cloudy._lib.check(L.cloudy_rainshaft_rhs(plan.handle, nz, ncol, n, x.ptr, dz, work.ptr, base.ptr, None))
+    cloudy._lib.check(L.cloudy_cond_evap(plan.handle, n, n, x.ptr, s.ptr, 0.0, XI, cond.ptr, None))
+    fused, base, cond = fused.to_numpy(), base.to_numpy(), cond.to_numpy()
+    ref = base + cond
+    fin = np.isfinite(ref)
+    assert np.array_equal(np.isfinite(fused), fin) and fin.mean() > 0.9
+    err = np.abs(fused - ref)[fin] / np.maximum((np.abs(base) + np.abs(cond))[fin], 1e-300)
+    print(f"degenerate cells: {int((~fin).sum())} non-finite entries, max |fused - (rhs + cond)| / (|rhs| + |cond|) = {err.max():.2e}")
+    assert err.max() <= 1e-13
+    assert np.abs(cond[fin]).max() > 0.0
+
+
+@pytest.mark.parametrize("case", ["gamma_mixture", "single_gamma"])
+def test_buffers(gpu_cloudy, oracle, case):
+    """(5) ld > n with sentinel-NaN padding (untouched), out of place (input unchanged), n_steps = 0 the identity, in place the
+    bits of out of place, a second call on the same plan the same bits."""
+    cloudy = gpu_cloudy
+    L = cloudy.lib()
+    c = shared(cloudy, oracle, case)
+    plan = c["par"].coal_data.plan(c["dist_types"], vel=VEL)
+    u0 = c["u0"]
+    nm, n = u0.shape
+    ld = n + 37
+    buf = np.full((nm, ld), 0.0)
+    buf.view(np.uint64)[:] = SENTINEL
+    buf[:, :n] = u0
+    u_in, u_out = dev(cloudy, buf), dev(cloudy, buf)
+    pad = lambda a: a.view(np.uint64)[:, n:]  # noqa: E731
+    steps = lambda a, b, k: cloudy._lib.check(L.cloudy_rainshaft_cond_ssprk33_steps(  # noqa: E731
+        plan.handle, NZ, NCOL, ld, a.ptr, b.ptr, c["s_dev"].ptr, 0.0, XI, DZ, DT, k, None))
+    steps(u_in, u_out, N_STEPS)
+    got = u_out.to_numpy()
+    assert np.array_equal(got[:, :n], c["got"])                       # the bits of the ld = n call of (1): a second call, too
+    assert np.all(pad(got) == SENTINEL)
+    assert np.array_equal(u_in.to_numpy().view(np.uint64), buf.view(np.uint64))
+    ident = dev(cloudy, np.zeros((nm, ld)))
+    steps(u_in, ident, 0)
+    assert np.array_equal(ident.to_numpy()[:, :n], u0)
+    steps(u_in, u_in, 0)
+    assert np.array_equal(u_in.to_numpy().view(np.uint64), buf.view(np.uint64))
+    steps(u_in, u_in, N_STEPS)
+    inplace = u_in.to_numpy()
+    assert np.array_equal(inplace[:, :n], got[:, :n]) and np.all(pad(inplace) == SENTINEL)
+    # the right-hand side in padded buffers
+    u_in = dev(cloudy, buf)
+    rhs_p, flux_p = dev(cloudy, buf), dev(cloudy, buf)
+    cloudy._lib.check(L.cloudy_rainshaft_cond_rhs(plan.handle, NZ, NCOL, ld, u_in.ptr, c["s_dev"].ptr, 0.0, XI, DZ, flux_p.ptr,
+                                                  rhs_p.ptr, None))
+    rhs_n, flux_n = cloudy.DeviceArray.zeros(nm, n), cloudy.DeviceArray.zeros(nm, n)
+    cloudy._lib.check(L.cloudy_rainshaft_cond_rhs(plan.handle, NZ, NCOL, n, dev(cloudy, u0).ptr, c["s_dev"].ptr, 0.0, XI, DZ,
+                                                  flux_n.ptr, rhs_n.ptr, None))
+    assert np.array_equal(rhs_p.to_numpy()[:, :n], rhs_n.to_numpy()) and np.all(pad(rhs_p.to_numpy()) == SENTINEL)
+    assert np.array_equal(flux_p.to_numpy()[:, :n], flux_n.to_numpy()) and np.all(pad(flux_p.to_numpy()) == SENTINEL)
+    assert np.array_equal(u_in.to_numpy().view(np.uint64), buf.view(np.uint64))
+
+
+def test_refusals(gpu_cloudy, oracle):
+    """the refusals of the existing column entries, and the plans these entries do not serve"""
+    cloudy = gpu_cloudy
+    L, E = cloudy.lib(), cloudy._lib
+    c = shared(cloudy, oracle, "single_gamma")
+    par = c["par"]
+    with_vel = par.coal_data.plan([1], vel=VEL)
+    no_vel = par.coal_data.plan([1])
+    fast = par.coal_data.plan([1], vel=VEL, dtype=2)
+    u, w, f = (cloudy.DeviceArray.zeros(3, 40) for _ in range(3))
+    nan = float("nan")
+    st = L.cloudy_rainshaft_cond_ssprk33_steps
+    assert st(with_vel.handle, 20, 2, 40, u.ptr, u.ptr, None, 0.01, XI, 150.0, nan, 1, None) == E.EINVAL
+    assert st(with_vel.handle, 20, 2, 40, u.ptr, u.ptr, None, 0.01, nan, 150.0, 1.0, 1, None) == E.EINVAL
+    assert st(with_vel.handle, 20, 2, 40, u.ptr, u.ptr, None, 0.01, XI, 150.0, 1.0, -1, None) == E.EINVAL
+    assert st(with_vel.handle, 0, 2, 40, u.ptr, u.ptr, None, 0.01, XI, 150.0, 1.0, 1, None) == E.EINVAL
+    assert st(with_vel.handle, 20, 2, 39, u.ptr, u.ptr, None, 0.01, XI, 150.0, 1.0, 1, None) == E.EINVAL
+    assert st(no_vel.handle, 20, 2, 40, u.ptr, u.ptr, None, 0.01, XI, 150.0, 1.0, 1, None) == E.EINVAL
+    assert st(fast.handle, 20, 2, 40, u.ptr, u.ptr, None, 0.01, XI, 150.0, 1.0, 1, None) == E.EUNSUPPORTED
+    assert st(with_vel.handle, 20, 0, 0, None, None, None, 0.01, XI, 150.0, 1.0, 1, None) == 0
+    rh = L.cloudy_rainshaft_cond_rhs
+    assert rh(with_vel.handle, 20, 2, 40, u.ptr, None, 0.01, nan, 150.0, w.ptr, f.ptr, None) == E.EINVAL
+    assert rh(with_vel.handle, 20, 2, 40, u.ptr, None, 0.01, XI, 150.0, None, f.ptr, None) == E.EINVAL
+    assert rh(no_vel.handle, 20, 2, 40, u.ptr, None, 0.01, XI, 150.0, w.ptr, f.ptr, None) == E.EINVAL
+    assert rh(fast.handle, 20, 2, 40, u.ptr, None, 0.01, XI, 150.0, w.ptr, f.ptr, None) == E.EUNSUPPORTED
+    # a NumericalCoalStyle plan has no column body
+    qpar = bench.cfg4q_par(cloudy)
+    from cloudy_jl_amd.box_model import _numerical_plan_for
+
+    qplan = _numerical_plan_for(qpar, 0)
+    u9 = cloudy.DeviceArray.zeros(9, 40)
+    assert st(qplan.handle, 20, 2, 40, u9.ptr, u9.ptr, None, 0.01, XI, 150.0, 1.0, 1, None) == E.EUNSUPPORTED
+    # without plan-time compilation there is no kernel: refused with the reason, not stepped some other way
+    aot = par.coal_data.plan([1], vel=VEL, specialize=-1)
+    assert st(aot.handle, 20, 2, 40, u.ptr, u.ptr, None, 0.01, XI, 150.0, 1.0, 1, None) == E.EUNSUPPORTED
+    assert b"compiled for the plan" in L.cloudy_last_error()
+
+
+@pytest.mark.parametrize("case", ["gamma_mixture", "single_gamma"])
+def test_float_planes_with_the_source_on(gpu_cloudy, oracle, case):
+    """(6) CLOUDY_F32 planes against fp64 planes on the same float-rounded input, max |f32 - f64| / max|plane|, for the existing
+    cloudy_rainshaft_ssprk33_steps (s = 0) and for the new entry with the profile of (1): the new figure within 8 x the existing
+    one (the new term adds roundings of the same size per stage and the state moves a few per cent more).
+    Measured on an MI355X (gamma_mixture / single_gamma): existing integrator 5.674e-08 / 3.591e-08, with condensation
+    5.317e-08 / 3.948e-08 of the plane maxima (also in DESIGN 3.5)."""
+    cloudy = gpu_cloudy
+    c = shared(cloudy, oracle, case)
+    par = c["par"]
+    u32 = c["u0"].astype(np.float32)
+    nm, n = u32.shape
+    res = {}
+    for dtype in (np.float32, np.float64):
+        ud = dev(cloudy, u32.astype(dtype))
+        a, b = cloudy.DeviceArray.zeros(nm, n, dtype), cloudy.DeviceArray.zeros(nm, n, dtype)
+        cloudy.solve_rainshaft_ssprk33(par, ud, N_STEPS, out=a)
+        cloudy.solve_rainshaft_cond_ssprk33(par, ud, N_STEPS, XI, c["s_dev"], out=b)
+        res[dtype] = (a.to_numpy().astype(np.float64), b.to_numpy().astype(np.float64))
+    fig = []
+    for k in (0, 1):
+        ref = np.abs(res[np.float64][k]).max(axis=1, keepdims=True) + 1e-300
+        fig.append((np.abs(res[np.float32][k] - res[np.float64][k]) / ref).max())
+    print(f"float planes {case}: existing integrator {fig[0]:.3e}, with condensation {fig[1]:.3e} of the plane maxima")
+    assert np.isfinite(res[np.float32][1]).all() and res[np.float32][1].min() >= 0.0
+    assert fig[0] > 0.0 and fig[1] <= 8.0 * fig[0]

@@ -2,7 +2,7 @@
 """Register / scratch / LDS use of the plan-specialised (hiprtc) kernels of named bench workloads, without a GPU:
 cloudy_jit_selfcheck compiles the plan's translation unit for gfx950, CLOUDY_HIP_JIT_DUMP keeps the code object, and
 the figures are read from its metadata notes.
-usage: python tools/jit_resources.py [--keep DIR] cfg3b cfg4 moving4 cfg4q ..."""
+usage: python tools/jit_resources.py [--keep DIR] cfg3b cfg4 moving4 cfg4q rainshaft_gamma_mixture rainshaft_single_gamma ..."""
 import argparse
 import ctypes as C
 import glob
@@ -51,6 +51,12 @@ def main():
                                             8 if conv else 10, kernel_func_is_normalized=False,
                                             quad_mode=pkg.QUAD_CONVERGED if conv else pkg.QUAD_FIXED)
             keep = None
+        elif name in ("rainshaft_gamma_mixture", "rainshaft_single_gamma"):
+            # the reference's 20-cell column plans (rainshaft_gamma_mixture.jl:15-60: two Gamma modes, Golovin b = 5, thr (2e-10, Inf);
+            # rainshaft_single_gamma.jl: one mode, thr Inf), one velocity term: the column units, with and without condensation
+            nm = 2 if name.endswith("mixture") else 1
+            d, keep = pkg.Plan.make_desc([1] * nm, np.array([[2.220446049250313e-22, 5.0], [5.0, 0.0]]),
+                                         (2e-10, float("inf"))[2 - nm:], bench.NORMS, 0, vel=((50.0, 1.0 / 6),))
         else:
             spec = bench.workload_spec(name)
             # (one sedimentation velocity term, so that the fused column integrator is compiled as well)

@@ -10,6 +10,9 @@ every experiment switch of the library is an environment variable, so an A/B run
         three launches; --fixed NQ: the fixed Gauss rule instead of converged mode
   python tools/timeit.py columns [--nz NZ] [--cells N] [--workload cfg3b] [--steps S]
         cloudy_rainshaft_ssprk33_steps and cloudy_rainshaft_rhs (ms per 1e7 cells)
+  python tools/timeit.py colcond [--nz NZ] [--cells N] [--workload cfg3b] [--steps S]
+        cloudy_rainshaft_cond_ssprk33_steps on the bench's column batch: (a) cloudy_rainshaft_ssprk33_steps, (b) the three sources
+        fused, (c) the sequence (b) replaces -- cloudy_rainshaft_rhs + cloudy_cond_evap + torch updates per stage
   python tools/timeit.py integrators [--parcels P]
         cloudy_ssprk33_steps / cloudy_tsit5_steps of the tensor plans cfg3a, cfg3b, cfg2
   python tools/timeit.py box [--parcels P] [--steps S]
@@ -102,6 +105,71 @@ def cmd_columns(a, pkg, L):
     print(f"{a.workload} columns nz={nz} x {ncol}: integrator {ms_i:.3f} ms per call of {a.steps} step(s) = {ms_i / (3 * a.steps) * 1e7 / n:.3f} ms "
           f"per evaluation of 1e7 cells; cloudy_rainshaft_rhs {ms_r * 1e7 / n:.3f} ms per 1e7 cells  (CLOUDY_HIP_RS_BLOCK="
           f"{os.environ.get('CLOUDY_HIP_RS_BLOCK', 'auto')})", flush=True)
+
+
+def cmd_colcond(a, pkg, L):
+    """ms per call of S steps on nz-cell columns with a supersaturation per cell: (a) the existing column integrator (no third
+    source), (b) cloudy_rainshaft_cond_ssprk33_steps, (c) the same steps stage by stage: the clamp, two right-hand-side launches and
+    the update on the planes (torch, on the same stream) per stage"""
+    here = os.path.dirname(os.path.abspath(__file__))   # torch imports the standard library's timeit: this file must not shadow it
+    sys.path[:] = [p for p in sys.path if os.path.abspath(p or ".") != here]
+    import torch
+
+    nz, ncol = a.nz, max(a.cells // a.nz, 1)
+    n, steps, xi, dz, h = nz * ncol, a.steps, 1e-8, 150.0, 1e-3
+    wl = bench.make_workload(a.workload, n, seed=7)
+    plan = wl["coal_data"].plan(wl["dist_types"], vel=((50.0, 1.0 / 6),))
+    u0, out = pkg.DeviceArray.from_numpy(wl["mom"]), pkg.DeviceArray.zeros(*wl["mom"].shape)
+    z = (np.arange(nz) + 0.5) * dz
+    s = pkg.DeviceArray.from_numpy(np.tile(np.where(z >= 0.45 * z.max(), 0.03, -0.2), ncol)[None, :])
+    ms_a = bench._sustained_ms(pkg, lambda: pkg._lib.check(
+        L.cloudy_rainshaft_ssprk33_steps(plan.handle, nz, ncol, n, u0.ptr, out.ptr, dz, h, steps, None)), min_reps=3)
+    ms_b = bench._sustained_ms(pkg, lambda: pkg._lib.check(
+        L.cloudy_rainshaft_cond_ssprk33_steps(plan.handle, nz, ncol, n, u0.ptr, out.ptr, s.ptr, 0.0, xi, dz, h, steps, None)), min_reps=3)
+    t0 = torch.from_numpy(wl["mom"]).cuda()
+    u, up, f, g, w = (torch.empty_like(t0) for _ in range(5))
+
+    def staged():
+        u.copy_(t0)
+        for _ in range(steps):
+            for stage in range(3):
+                u.clamp_(min=0.0)
+                if stage == 0:
+                    up.copy_(u)
+                pkg._lib.check(L.cloudy_rainshaft_rhs(plan.handle, nz, ncol, n, u.data_ptr(), dz, w.data_ptr(), f.data_ptr(), None))
+                pkg._lib.check(L.cloudy_cond_evap(plan.handle, n, n, u.data_ptr(), s.ptr, 0.0, xi, g.data_ptr(), None))
+                f.add_(g)
+                if stage == 0:
+                    torch.add(up, f, alpha=h, out=u)
+                elif stage == 1:
+                    u.add_(f, alpha=h).add_(up, alpha=3.0).mul_(0.25)
+                else:
+                    u.mul_(2.0).add_(f, alpha=2.0 * h).add_(up).div_(3.0)
+        u.clamp_(min=0.0)
+
+    ms_c = bench._sustained_ms(pkg, staged, min_reps=3)
+    # What the timed calls computed.  The stepped states of this synthetic batch are not compared: random parcels stacked as
+    # columns hold zero-variance cells whose closure flips under one ulp, and the existing integrator and the oracle themselves
+    # move by many orders of magnitude there under a 1e-15 perturbation (DESIGN 3.5).  One evaluation is well conditioned: the
+    # fused right-hand side with the source against cloudy_rainshaft_rhs + cloudy_cond_evap, entry by entry, and with s = 0
+    # the new integrator against the existing one, bit for bit.
+    x = pkg.DeviceArray.from_numpy(np.maximum(wl["mom"], 0.0))
+    fr, base, cond = (pkg.DeviceArray.zeros(*wl["mom"].shape) for _ in range(3))
+    pkg._lib.check(L.cloudy_rainshaft_cond_rhs(plan.handle, nz, ncol, n, x.ptr, s.ptr, 0.0, xi, dz, w.data_ptr(), fr.ptr, None))
+    pkg._lib.check(L.cloudy_rainshaft_rhs(plan.handle, nz, ncol, n, x.ptr, dz, w.data_ptr(), base.ptr, None))
+    pkg._lib.check(L.cloudy_cond_evap(plan.handle, n, n, x.ptr, s.ptr, 0.0, xi, cond.ptr, None))
+    fr, base, cond = fr.to_numpy(), base.to_numpy(), cond.to_numpy()
+    same_nan = bool(np.array_equal(np.isfinite(fr), np.isfinite(base + cond)))
+    fin = np.isfinite(fr) & np.isfinite(base + cond)
+    dev = float((np.abs(fr - (base + cond))[fin] / np.maximum((np.abs(base) + np.abs(cond))[fin], 1e-300)).max())
+    o0 = pkg.DeviceArray.zeros(*wl["mom"].shape)
+    pkg._lib.check(L.cloudy_rainshaft_ssprk33_steps(plan.handle, nz, ncol, n, u0.ptr, out.ptr, dz, h, steps, None))
+    pkg._lib.check(L.cloudy_rainshaft_cond_ssprk33_steps(plan.handle, nz, ncol, n, u0.ptr, o0.ptr, None, 0.0, xi, dz, h, steps, None))
+    bits = bool(np.array_equal(out.to_numpy(), o0.to_numpy(), equal_nan=True))
+    print(f"{a.workload} columns nz={nz} x {ncol}, {steps} steps per call: (a) cloudy_rainshaft_ssprk33_steps {ms_a:.3f} ms | (b) with "
+          f"condensation, fused {ms_b:.3f} ms | (c) rainshaft_rhs + cond_evap + torch updates per stage {ms_c:.3f} ms | b/a "
+          f"{ms_b / ms_a:.3f} | c/b {ms_c / ms_b:.2f} | one evaluation, fused vs rhs + cond_evap: same finite pattern {same_nan}, max "
+          f"{dev:.1e} of |rhs| + |cond| per entry | s = 0 steps equal the existing integrator's: {bits}", flush=True)
 
 
 def cmd_host(a, pkg, L):
@@ -209,6 +277,11 @@ def main():
     r.add_argument("--cells", type=int, default=10_000_000)
     r.add_argument("--workload", default="cfg3b")
     r.add_argument("--steps", type=int, default=2)
+    cc = sub.add_parser("colcond")
+    cc.add_argument("--nz", type=int, default=20)
+    cc.add_argument("--cells", type=int, default=10_000_000)
+    cc.add_argument("--workload", default="cfg3b")
+    cc.add_argument("--steps", type=int, default=2)
     i = sub.add_parser("integrators")
     i.add_argument("--parcels", type=int, default=0)
     b = sub.add_parser("box")
@@ -218,7 +291,7 @@ def main():
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
-    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "integrators": cmd_integrators, "box": cmd_box, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
+    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
 if __name__ == "__main__":
