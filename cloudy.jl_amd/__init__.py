@@ -26,6 +26,7 @@ from .Coalescence import (CoalescenceData, NumericalPlan, Plan, get_coal_ints, g
 from .Sedimentation import (get_sedimentation_flux, make_rainshaft_cond_rhs, make_rainshaft_rhs, rainshaft_sources,
                             rhs_condensation, solve_rainshaft_cond_ssprk33, solve_rainshaft_ssprk33)
 from .box_model import ODEParameters, make_box_model_rhs, rhs_coal, solve_box_ssprk33, solve_ssprk33, solve_tsit5
+from .parcel import ParcelParams, parcel_rhs, solve_parcel_ssprk33
 from .sharding import Communicator, allreduce_sums, mode_sums, moment_sums, shard_range
 
 __all__ = [n for n in dir() if not n.startswith("_")]

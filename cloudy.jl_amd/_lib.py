@@ -52,6 +52,12 @@ class PlanDesc(C.Structure):
     ]
 
 
+class ParcelParamsC(C.Structure):
+    """cloudy_parcel_params"""
+    _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_double) for n in (
+        "R_d", "R_v", "cp_d", "cp_v", "cp_l", "LH_v0", "T_0", "press_triple", "T_triple", "grav", "K_therm", "D_vapor", "rho_l")]
+
+
 # every symbol include/cloudy_hip.h declares: (restype, argtypes)
 _vp, _sz, _i, _dp = C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)
 SYMBOLS = {
@@ -73,6 +79,10 @@ SYMBOLS = {
     "cloudy_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, _i, _vp]),
     "cloudy_tsit5_steps": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, _i, _vp]),
     "cloudy_box_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, _i, _vp]),
+    "cloudy_parcel_params_init": (None, [C.POINTER(ParcelParamsC)]),
+    "cloudy_parcel_rhs": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(ParcelParamsC), _i, _vp, _vp]),
+    "cloudy_parcel_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.POINTER(ParcelParamsC), C.c_double, _i, _vp]),
+    "cloudy_parcel_thermo_host": (_i, [C.POINTER(ParcelParamsC), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp]),
     "cloudy_update_dist_from_moments": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "cloudy_closure_stats": (_i, [_vp, _sz, _sz, _vp, C.POINTER(C.c_uint64), _vp]),
     "cloudy_finite_2d_integrals": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),

@@ -14,7 +14,10 @@
 
 namespace cloudy {
 
+#ifndef CLOUDY_SRC_BITS   // (parcel.hpp defines the same two)
+#define CLOUDY_SRC_BITS
 enum { SRC_COAL = 1, SRC_COND = 2 };  // CLOUDY_SRC_* of include/cloudy_hip.h
+#endif
 
 // n_steps SSPRK33 steps of du/dt = [coal](u) + [cond](u; s) for one parcel per lane; SRC: SRC_COND or SRC_COAL | SRC_COND
 // (coalescence alone is ssprk33_body).  State and u_prev stay in registers over all stages and steps, the state is read once

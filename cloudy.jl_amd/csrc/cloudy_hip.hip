@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include "jit.hpp"
 #include "box_sources.hpp"
+#include "parcel.hpp"
 #include "reduce_kernels.hpp"
 
 using namespace cloudy;
@@ -216,6 +217,8 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
         return h.mode == MODE_ALLINF && h.coal_style != CLOUDY_NUMERICAL_COAL ? JIT_MAIN : JIT_INTEGRATOR;
     case OP_TSIT5: return JIT_TSIT5;
     case OP_BOX_SSPRK33: return JIT_BOX;
+    case OP_PARCEL_SSPRK33:
+    case OP_PARCEL_RHS: return JIT_PARCEL;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
@@ -240,6 +243,10 @@ JitShape jit_shape(const HostPlan &h, JitUnit u, const LaunchReq &r) {
         const bool coal = (r.sources & SRC_COAL) != 0;
         const unsigned bs = coal && h.mode != MODE_ALLINF ? (unsigned)jit_sorted_block_size(h) : (unsigned)kBlock;
         return {coal ? K_BOX_COAL_COND : K_BOX_COND, bs, bs};
+    }
+    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS) {  // parcel_kernel() of jit.hpp
+        const bool coal = (r.sources & SRC_COAL) != 0;
+        return {r.op == OP_PARCEL_RHS ? (coal ? K_PARCEL_RHS_COAL : K_PARCEL_RHS) : (coal ? K_PARCEL_COAL_COND : K_PARCEL_COND), kBlock, kBlock};
     }
     if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         const unsigned bs = (unsigned)jit_rainshaft_block(u);   // whole columns per workgroup, as launch_int_io()
@@ -288,6 +295,9 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
         if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) push({&coef, &s_scalar, &s_dev});
     } else if (r.op == OP_BOX_SSPRK33) {
         push({&nodes, &n, &ld, &in, &out, &coef, &s_scalar, &s_dev, &dt, &n_steps});
+    } else if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS) {   // (the ParcelParams by value: the pointer to them)
+        push({const_cast<void *>(r.parcel), &n, &ld, &in, &out, &coef, &s_scalar, &s_dev});
+        if (r.op == OP_PARCEL_SSPRK33) push({&dt, &n_steps});
     } else {
         if (!numerical && (h.mode != MODE_ALLINF || r.op == OP_TSIT5)) push({&nodes});
         push({&n, &ld, &in, &out});
@@ -494,6 +504,9 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_ssprk33_steps with the condensation source runs the kernel compiled for the plan "
                                          "(hiprtc); plan-time compilation is off or failed: %s",
                     plan->jit_on ? jit_unit(plan, JIT_BOX).log.c_str() : plan->jit[JIT_MAIN].log.c_str());
+    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS)
+        return fail(CLOUDY_EUNSUPPORTED, "the parcel kernels are compiled for the plan (hiprtc); plan-time compilation is off or "
+                                         "failed: %s", plan->jit_on ? jit_unit(plan, JIT_PARCEL).log.c_str() : plan->jit[JIT_MAIN].log.c_str());
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
@@ -568,6 +581,19 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
             coal.n_steps = r.n_steps;
             return run(plan, coal);
         }
+    }
+    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS) {
+        static const char kStaged[] = "step such a parcel stage by stage: cloudy_cond_evap (and cloudy_coal_rhs) per stage with the "
+                                      "thermodynamics of cloudy_parcel_thermo_host on the host's side";
+        if (plan->h.dtype != CLOUDY_F64)
+            return fail(CLOUDY_EUNSUPPORTED, "the parcel integrator serves CLOUDY_F64 and CLOUDY_F64_RELAXED plans (S - 1 of 1e-3 does "
+                                             "not survive a float plane); %s", kStaged);
+        if ((r.sources & SRC_COAL) && plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
+            return fail(CLOUDY_EUNSUPPORTED, "the parcel kernel with coalescence is not built for quadrature (NumericalCoalStyle) "
+                                             "plans: pass CLOUDY_SRC_COND alone, or %s", kStaged);
+        if ((r.sources & SRC_COAL) && plan->h.mode != MODE_ALLINF)
+            return fail(CLOUDY_EUNSUPPORTED, "the parcel kernel with coalescence is built for plans whose thresholds are all Inf (the "
+                                             "ranked variant is not): pass CLOUDY_SRC_COND alone, or %s", kStaged);
     }
     if (r.n == 0) return CLOUDY_OK;
     DeviceGuard guard(plan->h.device);
@@ -1124,6 +1150,103 @@ int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const
     r.dt = dt;
     r.n_steps = n_steps;
     return run(plan, r);
+}
+
+void cloudy_parcel_params_init(cloudy_parcel_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->R_d = 8.3144598 / 0.02897;
+    p->R_v = 8.3144598 / 0.018015;
+    p->cp_d = p->R_d * 7 / 2;
+    p->cp_v = 1859;
+    p->cp_l = 4181;
+    p->LH_v0 = 2.5008e6;
+    p->T_0 = 273.16;
+    p->press_triple = 611.657;
+    p->T_triple = 273.16;
+    p->grav = 9.81;
+    p->K_therm = 2.4e-2;
+    p->D_vapor = 2.26e-5;
+    p->rho_l = 1000;
+}
+
+// the descriptor's checks (every constant positive, hence not NaN) and its constants as the kernels take them
+static int parcel_params(const cloudy_parcel_params *p, ParcelParams &c) {
+    if (!p) return fail(CLOUDY_EINVAL, "params is NULL");
+    if (p->struct_size != sizeof(cloudy_parcel_params))
+        return fail(CLOUDY_EINVAL, "params.struct_size (%u) is not sizeof(cloudy_parcel_params) (%zu): call cloudy_parcel_params_init",
+                    (unsigned)p->struct_size, sizeof(cloudy_parcel_params));
+    c = {p->R_d, p->R_v, p->cp_d, p->cp_v, p->cp_l, p->LH_v0, p->T_0, p->press_triple, p->T_triple, p->grav, p->K_therm, p->D_vapor,
+         p->rho_l};
+    static const char *const names[] = {"R_d", "R_v", "cp_d", "cp_v", "cp_l", "LH_v0", "T_0", "press_triple", "T_triple", "grav",
+                                        "K_therm", "D_vapor", "rho_l"};
+    const double *v = &c.R_d;
+    for (int i = 0; i < 13; ++i)
+        if (!(v[i] > 0.0)) return fail(CLOUDY_EINVAL, "params.%s (%g) must be positive", names[i], v[i]);
+    return CLOUDY_OK;
+}
+static_assert(sizeof(ParcelParams) == 13 * sizeof(double), "ParcelParams is 13 doubles");
+
+// what the two parcel entry points share: the checks that need no device.  The plan comes last, so that every other check is
+// reachable -- and tested -- without one.
+static int parcel_request(const cloudy_plan *plan, size_t n, size_t ld, const void *in, void *out, const cloudy_parcel_params *p,
+                          int sources, bool steps, double dt, int n_steps, ParcelParams &c) {
+    int rc = parcel_params(p, c);
+    if (rc) return rc;
+    if (sources != SRC_COND && sources != (SRC_COAL | SRC_COND))
+        return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COND or CLOUDY_SRC_COAL | CLOUDY_SRC_COND (coalescence alone is "
+                                   "not a parcel: cloudy_ssprk33_steps)", sources);
+    if (steps && (n_steps < 0 || !(dt == dt))) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
+    if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
+    return check_batch(plan, n, ld, in, out);
+}
+// coef0 of parcel.hpp: the folded coefficient of get_cond_evap without xi, which the kernel forms per stage
+static double parcel_coef0(const cloudy_plan *plan, const ParcelParams &c) {
+    return 3 * std::pow(4 * M_PI / 3, 2.0 / 3.0) / (std::cbrt(c.rho_l) * std::pow(plan->h.norms[1], 2.0 / 3.0));
+}
+
+int cloudy_parcel_rhs(const cloudy_plan *plan, size_t n, size_t ld, const void *y_dev, const double *w_dev, double w,
+                      const cloudy_parcel_params *params, int sources, void *dy_dev, void *stream) {
+    ParcelParams c;
+    int rc = parcel_request(plan, n, ld, y_dev, dy_dev, params, sources, false, 0.0, 0, c);
+    if (rc) return rc;
+    LaunchReq r(OP_PARCEL_RHS, n, ld, y_dev, dy_dev, stream);
+    r.sources = sources;
+    r.parcel = &c;
+    r.coef = parcel_coef0(plan, c);
+    r.s_scalar = w;
+    r.s_dev = w_dev;
+    return run(plan, r);
+}
+
+int cloudy_parcel_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const void *y_in_dev, void *y_out_dev, int sources,
+                                const double *w_dev, double w, const cloudy_parcel_params *params, double dt, int n_steps,
+                                void *stream) {
+    ParcelParams c;
+    int rc = parcel_request(plan, n, ld, y_in_dev, y_out_dev, params, sources, true, dt, n_steps, c);
+    if (rc) return rc;
+    LaunchReq r(OP_PARCEL_SSPRK33, n, ld, y_in_dev, y_out_dev, stream);
+    r.sources = sources;
+    r.parcel = &c;
+    r.coef = parcel_coef0(plan, c);
+    r.s_scalar = w;
+    r.s_dev = w_dev;
+    r.dt = dt;
+    r.n_steps = n_steps;
+    return run(plan, r);
+}
+
+int cloudy_parcel_thermo_host(const cloudy_parcel_params *params, double S, double p, double T, double q_v, double m_liq,
+                              double out[8]) {
+    ParcelParams c;
+    int rc = parcel_params(params, c);
+    if (rc) return rc;
+    if (!out) return fail(CLOUDY_EINVAL, "out is NULL");
+    const ParcelThermo x = parcel_thermo(c, S, p, T, q_v, m_liq);
+    const double v[8] = {x.rho, x.R, x.cp, x.L, x.p_vs, x.xi, x.a1, x.a3};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return CLOUDY_OK;
 }
 
 int cloudy_update_dist_from_moments(const cloudy_plan *plan, size_t n, size_t ld, const void *mom_dev,

@@ -52,7 +52,9 @@ enum Op {
     OP_RAINSHAFT_RHS = 10 /* one evaluation of the column right-hand side (cloudy_rainshaft_rhs) */,
     OP_BOX_SSPRK33 = 11 /* fused SSPRK33 steps with the condensation source (cloudy_box_ssprk33_steps, box_sources.hpp) */,
     OP_RAINSHAFT_COND_SSPRK33 = 12 /* the column integrator with the condensation source (cloudy_rainshaft_cond_ssprk33_steps) */,
-    OP_RAINSHAFT_COND_RHS = 13 /* one evaluation of the column right-hand side with it (cloudy_rainshaft_cond_rhs) */
+    OP_RAINSHAFT_COND_RHS = 13 /* one evaluation of the column right-hand side with it (cloudy_rainshaft_cond_rhs) */,
+    OP_PARCEL_SSPRK33 = 14 /* fused SSPRK33 steps of the adiabatic parcel (cloudy_parcel_ssprk33_steps, parcel.hpp) */,
+    OP_PARCEL_RHS = 15 /* one evaluation of its right-hand side (cloudy_parcel_rhs) */
 };
 
 struct LaunchReq {
@@ -70,7 +72,8 @@ struct LaunchReq {
     int n_steps = 0;  // likewise
     double coef = 0.0, s_scalar = 0.0;  // OP_COND, OP_BOX_SSPRK33, OP_RAINSHAFT_COND_*
     const double *s_dev = nullptr;      // OP_COND, OP_BOX_SSPRK33, OP_RAINSHAFT_COND_* (optional per-parcel supersaturation)
-    int sources = 0;                    // OP_BOX_SSPRK33: CLOUDY_SRC_* bits
+    int sources = 0;                    // OP_BOX_SSPRK33, OP_PARCEL_*: CLOUDY_SRC_* bits
+    const void *parcel = nullptr;       // OP_PARCEL_*: the ParcelParams (parcel.hpp); coef = coef0, s_scalar / s_dev = w / w_dev
     size_t nz = 0;    // OP_RAINSHAFT_*: cells per column (n = nz * n_columns)
     double dz = 0.0;  // OP_RAINSHAFT_*
     LaunchReq(int op_, size_t n_, size_t ld_, const void *in_, void *out_, void *stream_)

@@ -41,6 +41,9 @@
  *   cloudy_box_ssprk33_steps      <- solve(ODEProblem(rhs!, ...), SSPRK33(), dt = ...) with rhs! = rhs_condensation! (or the sum
  *                                    of rhs_coal! and it), test/examples/Analytical/condensation_single_gamma.jl:28,
  *                                    condensation_exp_gamma.jl:31
+ *   cloudy_parcel_rhs             <- parcel_model_cloudy(dY, Y, p, t), test/examples/Analytical/parcel_example.jl:15-85, with the
+ *                                    distributions updated from the current moments (see the entry point)
+ *   cloudy_parcel_ssprk33_steps   <- solve(ODEProblem(parcel_model_cloudy, Yinit, tspan, p), SSPRK33(), dt = const_dt), :104-111
  *   cloudy_rainshaft_cond_rhs     <- rhs(m, p, t) of make_rainshaft_rhs (test/examples/utils/rainshaft_helpers.jl:45-89) plus
  *                                    get_cond_evap of each cell (src/Sources/Condensation.jl:22-37, as rhs_condensation!,
  *                                    test/examples/utils/box_model_helpers.jl:55-67): the three sources of a column
@@ -304,6 +307,58 @@ int cloudy_tsit5_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, con
  * CLOUDY_EUNSUPPORTED.  u_out_dev may equal u_in_dev; n_steps = 0 copies the input to the output. */
 int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
                              int sources, const double *s_dev, double s, double xi, double dt, int n_steps, void *stream);
+
+/* The adiabatic parcel of test/examples/Analytical/parcel_example.jl: Y = (S, p, T, q_v, mom[0..nmom)) -- saturation ratio over
+ * liquid water, pressure, temperature, vapour specific humidity and the plan's moments (physical units, the plan's plane order) --
+ * rising at speed w.  With the constants below:
+ *   R_m(q_t, q_l)  = R_d (1 + (R_v/R_d - 1) q_t - (R_v/R_d) q_l)          cp_m(q_t, q_l) = cp_d + (cp_v - cp_d) q_t + (cp_l - cp_v) q_l
+ *   L(T)           = LH_v0 + (cp_v - cp_l)(T - T_0)
+ *   p_vs(T)        = press_triple (T/T_triple)^((cp_v-cp_l)/R_v) exp((LH_v0 - (cp_v-cp_l) T_0)/R_v (1/T_triple - 1/T))
+ *   xi(T)          = 1 / ( L/(K_therm T) (L/(R_v T) - 1) + R_v T / (D_vapor p_vs) )
+ *   rho0 = p / (R_m(q_v, 0) T);  q_l = sum_modes M1_mode / rho0;  R = R_m(q_v + q_l, q_l);  cp = cp_m(q_v + q_l, q_l);  rho = p / (R T)
+ *   a1 = L g/(cp T^2 R_v) - g/(R T);  a2 = 1/q_v;  a3 = L^2/(R_v T^2 cp)
+ *   dmom = get_cond_evap(update_dist_from_moments(mom), S - 1, xi(T), rho_l);  dq_l = sum_modes dmom[M1_mode] / rho
+ *   dS = a1 w S - (a2 + a3) S dq_l;  dp = -p g w/(R T);  dT = -g w/cp + L dq_l/cp;  dq_v = -dq_l
+ * (Thermodynamics.jl / CloudMicrophysics.jl, which the driver takes these from, are not part of the reference tree: the closure
+ * is stated here in full.)  The driver as written binds `pdists` (:19) before it rebuilds p.pdists (:55-61), so its get_cond_evap
+ * sees the INITIAL distributions at every call; these entry points use the distributions updated from the current moments, as
+ * every other right-hand side of the reference does.
+ * The defaults of cloudy_parcel_params_init are ClimaParams' values as recalled -- ClimaParams is not part of the reference tree,
+ * so they could not be verified against it: R_d = 8.3144598/0.02897, R_v = 8.3144598/0.018015, cp_d = R_d 7/2, cp_v = 1859,
+ * cp_l = 4181, LH_v0 = 2.5008e6, T_0 = 273.16, press_triple = 611.657, T_triple = 273.16, grav = 9.81, K_therm = 2.4e-2,
+ * D_vapor = 2.26e-5, rho_l = 1000. */
+typedef struct cloudy_parcel_params {
+    uint32_t struct_size; /* sizeof(cloudy_parcel_params), set by cloudy_parcel_params_init */
+    double R_d, R_v, cp_d, cp_v, cp_l, LH_v0, T_0, press_triple, T_triple, grav, K_therm, D_vapor, rho_l;
+} cloudy_parcel_params;
+void cloudy_parcel_params_init(cloudy_parcel_params *params);
+
+/* y: 4 + nmom fp64 planes of leading dimension ld -- planes 0..3 are S, p, T, q_v, plane 4 + q is the plan's moment plane q.
+ * w_dev: one updraft speed per parcel (fp64), or NULL to use the scalar `w`.
+ *   sources = CLOUDY_SRC_COND: every plan cloudy_cond_evap serves, Monodisperse and NumericalCoalStyle plans included (nothing
+ *     of the coalescence data is read);
+ *   sources = CLOUDY_SRC_COAL | CLOUDY_SRC_COND: the coalescence tendency added to the moments' (AnalyticalCoalStyle plans
+ *     whose thresholds are all Inf), from the same closure inversion.
+ * cloudy_parcel_rhs: one evaluation of dY into dy_dev (same layout).  cloudy_parcel_ssprk33_steps: n_steps SSPRK33 steps with
+ * fixed dt, fused like cloudy_box_ssprk33_steps -- state in registers over all stages and steps, read once and written once, w
+ * loaded once, xi(T) formed per stage on the device; y_out_dev may equal y_in_dev, n_steps = 0 copies, n_parcels = 0 returns
+ * CLOUDY_OK at once.
+ * Argument checks precede any device work (CLOUDY_EINVAL): params NULL or of another struct_size, a constant that is not
+ * positive (NaN included), sources without CLOUDY_SRC_COND, n_steps < 0, dt NaN, ld < n_parcels, plan NULL.
+ * Deliberate limits (CLOUDY_EUNSUPPORTED; step such a parcel stage by stage with cloudy_cond_evap / cloudy_coal_rhs and
+ * cloudy_parcel_thermo_host): COAL | COND on plans with finite or moving thresholds and on NumericalCoalStyle plans; CLOUDY_F32 /
+ * CLOUDY_F32_FAST planes (S - 1 of 1e-3 does not survive a float plane).  CLOUDY_SRC_COAL alone is CLOUDY_EINVAL: it is not a
+ * parcel, cloudy_ssprk33_steps exists for it.  The kernels are compiled for the plan on first use (cloudy_jit_parcel_*); without
+ * plan-time compilation the calls answer CLOUDY_EUNSUPPORTED with the compiler's log, as cloudy_box_ssprk33_steps does. */
+int cloudy_parcel_rhs(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *y_dev, const double *w_dev, double w,
+                      const cloudy_parcel_params *params, int sources, void *dy_dev, void *stream);
+int cloudy_parcel_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *y_in_dev, void *y_out_dev,
+                                int sources, const double *w_dev, double w, const cloudy_parcel_params *params, double dt,
+                                int n_steps, void *stream);
+/* the closure alone, on the host (the same source as the kernels'): out = (rho, R, cp, L, p_vs, xi, a1, a3) for a state
+ * (S, p, T, q_v) and m_liq = the sum of the modes' mass moments in physical units */
+int cloudy_parcel_thermo_host(const cloudy_parcel_params *params, double S, double p, double T, double q_v, double m_liq,
+                              double out[8]);
 
 /* inner operator on given distributions: params = 3N planes (n, theta, k) per mode, normalised units
  * (k plane ignored for exponential modes); out = nmom planes, normalised units. */

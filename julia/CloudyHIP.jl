@@ -387,6 +387,76 @@ function solve_box_ssprk33!(u, plan::Plan, dt, n_steps, xi, s; coal::Bool = true
 end
 
 """
+    ParcelParams()
+
+`cloudy_parcel_params` with the defaults of `cloudy_parcel_params_init` (ClimaParams' values as recalled): the constants of the
+adiabatic parcel's closure (include/cloudy_hip.h states it in full).  Fields may be changed before a call.
+"""
+mutable struct ParcelParams
+    struct_size::UInt32
+    R_d::Float64
+    R_v::Float64
+    cp_d::Float64
+    cp_v::Float64
+    cp_l::Float64
+    LH_v0::Float64
+    T_0::Float64
+    press_triple::Float64
+    T_triple::Float64
+    grav::Float64
+    K_therm::Float64
+    D_vapor::Float64
+    rho_l::Float64
+    function ParcelParams()
+        p = new()
+        ccall((:cloudy_parcel_params_init, lib), Cvoid, (Ref{ParcelParams},), p)
+        return p
+    end
+end
+
+# w: a number, or a device Vector{Float64} with one updraft speed per parcel
+parcel_updraft(w) = w isa Number ? (Ptr{Cdouble}(C_NULL), Float64(w)) : (Ptr{Cdouble}(pointer(w)), 0.0)
+
+"""
+    parcel_rhs!(dy, y, plan, w; params = ParcelParams(), coal = false, stream = nothing, sync = true)
+
+`parcel_model_cloudy(dY, Y, p, t)` of test/examples/Analytical/parcel_example.jl:15-85 for a batch `y[parcel, 4 + nmom]`
+(columns S, p, T, q_v, then the plan's moments), with the distributions updated from the current moments; `coal`: `rhs_coal!`
+added to the moments' tendency.
+"""
+function parcel_rhs!(dy, y, plan::Plan, w; params::ParcelParams = ParcelParams(), coal::Bool = false, stream = nothing,
+                     sync::Bool = true)
+    n, ld = batch_shape(y, plan.nmom + 4)
+    batch_shape(dy, plan.nmom + 4) == (n, ld) || error("dy must have the shape and leading dimension of y")
+    st = stream === nothing ? current_stream() : stream
+    w_dev, w_val = parcel_updraft(w)
+    check(ccall((:cloudy_parcel_rhs, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Ref{ParcelParams}, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
+                plan.handle, n, ld, pointer(y), w_dev, w_val, params, SRC_COND | (coal ? SRC_COAL : 0), pointer(dy), st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return dy
+end
+
+"""
+    solve_parcel_ssprk33!(y, plan, w, dt, n_steps; params = ParcelParams(), coal = false, stream = nothing, sync = true)
+
+`solve(ODEProblem(parcel_model_cloudy, Yinit, tspan, p), SSPRK33(), dt = const_dt)` (parcel_example.jl:104-111) for `n_steps`
+fixed steps on the device, final state only: one launch, the state in registers, xi(T) formed per stage.
+"""
+function solve_parcel_ssprk33!(y, plan::Plan, w, dt, n_steps; params::ParcelParams = ParcelParams(), coal::Bool = false,
+                               stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(y, plan.nmom + 4)
+    st = stream === nothing ? current_stream() : stream
+    w_dev, w_val = parcel_updraft(w)
+    check(ccall((:cloudy_parcel_ssprk33_steps, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cdouble, Ref{ParcelParams}, Cdouble, Cint,
+                 Ptr{Cvoid}),
+                plan.handle, n, ld, pointer(y), pointer(y), SRC_COND | (coal ? SRC_COAL : 0), w_dev, w_val, params, dt, n_steps, st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return y
+end
+
+"""
     solve_rainshaft_ssprk33!(u, plan, nz, dz, dt, n_steps; stream = nothing, sync = true)
 
 `solve(ODEProblem(make_rainshaft_rhs(AnalyticalCoalStyle()), m, tspan, p), SSPRK33(), dt = p.dt)` of

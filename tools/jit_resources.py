@@ -2,7 +2,8 @@
 """Register / scratch / LDS use of the plan-specialised (hiprtc) kernels of named bench workloads, without a GPU:
 cloudy_jit_selfcheck compiles the plan's translation unit for gfx950, CLOUDY_HIP_JIT_DUMP keeps the code object, and
 the figures are read from its metadata notes.
-usage: python tools/jit_resources.py [--keep DIR] cfg3b cfg4 moving4 cfg4q rainshaft_gamma_mixture rainshaft_single_gamma ..."""
+usage: python tools/jit_resources.py [--keep DIR] cfg3b cfg4 moving4 cfg4q rainshaft_gamma_mixture rainshaft_single_gamma
+       parcel_monodisperse parcel_gamma parcel_mixture ..."""
 import argparse
 import ctypes as C
 import glob
@@ -57,6 +58,11 @@ def main():
             nm = 2 if name.endswith("mixture") else 1
             d, keep = pkg.Plan.make_desc([1] * nm, np.array([[2.220446049250313e-22, 5.0], [5.0, 0.0]]),
                                          (2e-10, float("inf"))[2 - nm:], bench.NORMS, 0, vel=((50.0, 1.0 / 6),))
+        elif name.startswith("parcel_"):
+            # the three initial conditions of parcel_example.jl (one Monodisperse mode; one Gamma mode; Exponential + Gamma), norms
+            # (1e8, 1e-12), thresholds Inf: the parcel unit (cloudy_jit_parcel_*) among the plan's units
+            types = {"parcel_monodisperse": [2], "parcel_gamma": [1], "parcel_mixture": [0, 1]}[name]
+            d, keep = pkg.Plan.make_desc(types, np.array([[1.0]]), (float("inf"),) * len(types), (1e8, 1e-12), 0)
         else:
             spec = bench.workload_spec(name)
             # (one sedimentation velocity term, so that the fused column integrator is compiled as well)

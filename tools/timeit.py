@@ -18,6 +18,10 @@ every experiment switch of the library is an environment variable, so an A/B run
   python tools/timeit.py box [--parcels P] [--steps S]
         cloudy_box_ssprk33_steps on cfg3a and cfg3b: (a) cloudy_ssprk33_steps, (b) coalescence + condensation fused, (c) condensation
         alone, (d) the unfused sequence (b) replaces -- cloudy_coal_rhs + cloudy_cond_evap + torch updates per stage
+  python tools/timeit.py parcel [--parcels P] [--steps S]
+        cloudy_parcel_ssprk33_steps on a batch of the driver's mixture case (Exponential + Gamma): (a) the fused call, (b) the
+        sequence it replaces -- cloudy_cond_evap per stage plus torch thermodynamics and updates, (c) cloudy_box_ssprk33_steps with
+        CLOUDY_SRC_COND on the same moments (constant supersaturation: the floor)
   python tools/timeit.py host [--parcels P]
         cloudy_coal_rhs_host on cfg3a: the PCIe-inclusive rate (host arrays staged through the device)
 
@@ -255,6 +259,83 @@ def cmd_box(a, pkg, L):
         del u, up, f, g, t0, u0, out
 
 
+def cmd_parcel(a, pkg, L):
+    """ms per call of S steps of the adiabatic parcel (parcel_example.jl's mixture case, N and m0 scaled per parcel)"""
+    here = os.path.dirname(os.path.abspath(__file__))   # (as cmd_box)
+    sys.path[:] = [p for p in sys.path if os.path.abspath(p or ".") != here]
+    import torch
+
+    n, steps, dt, w = a.parcels or 10_000_000, a.steps, 0.5, 10.0
+    norms, types = (1e8, 1e-12), [0, 1]
+    cd = pkg.CoalescenceData(pkg.CoalescenceTensor([[1.0]]), (2, 3), (float("inf"),) * 2, norms)
+    plan = cd.plan(types)
+    c = pkg.ParcelParams()
+    rng = np.random.default_rng(0)
+    N, m0 = 2e8 * rng.uniform(0.5, 2, n), 4 / 3 * np.pi * 8e-6**3 * 1000.0 * rng.uniform(0.5, 2, n)
+    T, p, S = rng.uniform(270, 290, n), rng.uniform(6e4, 9e4, n), rng.uniform(0.99, 1.01, n)
+    dcp = c.cp_v - c.cp_l
+
+    def p_vs(T, exp=np.exp):
+        return c.press_triple * (T / c.T_triple) ** (dcp / c.R_v) * exp((c.LH_v0 - dcp * c.T_0) / c.R_v * (1 / c.T_triple - 1 / T))
+
+    th = (N * m0 / 2) / (N / 10) / 2
+    y_host = np.stack([S, p, T, 0.622 * S * p_vs(T) / p, 0.9 * N, N * m0 / 2, 0.1 * N, N * m0 / 2, 0.1 * N * th * th * 6])
+    y0, out = pkg.DeviceArray.from_numpy(y_host), pkg.DeviceArray.zeros(*y_host.shape)
+    cc = c.to_c()
+    fused = lambda: pkg._lib.check(L.cloudy_parcel_ssprk33_steps(plan.handle, n, n, y0.ptr, out.ptr, pkg.SRC_COND, None, w, C.byref(cc),   # noqa: E731
+                                                                 dt, steps, None))
+    ms_a = bench._sustained_ms(pkg, fused)
+    u0, uo = pkg.DeviceArray.from_numpy(y_host[4:]), pkg.DeviceArray.zeros(5, n)
+    ms_c = bench._sustained_ms(pkg, lambda: pkg._lib.check(
+        L.cloudy_box_ssprk33_steps(plan.handle, n, n, u0.ptr, uo.ptr, pkg.SRC_COND, None, 0.01, 8e-8, dt, steps, None)))
+    t0 = torch.from_numpy(y_host).cuda()
+    y, yp, f = (torch.empty_like(t0) for _ in range(3))
+    s_eff = torch.empty(n, dtype=torch.float64, device="cuda")
+    rvd, g = c.R_v / c.R_d, c.grav
+
+    def rhs():   # f = dY(y): torch thermodynamics, cloudy_cond_evap with xi = 1 and s = xi(T) (S - 1) (1000 / rho_l)^(1/3) per parcel
+        S_, p_, T_, q_ = y[0], y[1], y[2], y[3]
+        m_liq = y[5] + y[7]
+        q_l = m_liq * (c.R_d * (1 + (rvd - 1) * q_) * T_) / p_
+        q_t = q_ + q_l
+        R = c.R_d * (1 + (rvd - 1) * q_t - rvd * q_l)
+        cp = c.cp_d + (c.cp_v - c.cp_d) * q_t + (c.cp_l - c.cp_v) * q_l
+        Lv = c.LH_v0 + dcp * (T_ - c.T_0)
+        xi = 1 / (Lv / (c.K_therm * T_) * (Lv / (c.R_v * T_) - 1) + c.R_v * T_ / (c.D_vapor * p_vs(T_, torch.exp)))
+        torch.mul(xi, S_ - 1, out=s_eff)
+        s_eff.mul_((1000.0 / c.rho_l) ** (1 / 3))
+        pkg._lib.check(L.cloudy_cond_evap(plan.handle, n, n, y[4:].data_ptr(), s_eff.data_ptr(), 0.0, 1.0, f[4:].data_ptr(), None))
+        dq = (f[5] + f[7]) * (R * T_) / p_
+        f[0] = (Lv * g / (cp * T_ * T_ * c.R_v) - g / (R * T_)) * w * S_ - (1 / q_ + Lv * Lv / (c.R_v * T_ * T_ * cp)) * S_ * dq
+        f[1] = -p_ * g * w / (R * T_)
+        f[2] = (Lv * dq - g * w) / cp
+        f[3] = -dq
+
+    def staged():
+        y.copy_(t0)
+        for _ in range(steps):
+            yp.copy_(y)
+            for stage in range(3):
+                rhs()
+                if stage == 0:
+                    torch.add(yp, f, alpha=dt, out=y)
+                elif stage == 1:
+                    y.add_(f, alpha=dt).add_(yp, alpha=3.0).mul_(0.25)
+                else:
+                    y.mul_(2.0).add_(f, alpha=2.0 * dt).add_(yp).div_(3.0)
+
+    ms_b = bench._sustained_ms(pkg, staged, min_reps=3)
+    fused()
+    staged()
+    got, want = out.columns_to_numpy(20000), y[:, :20000].cpu().numpy()
+    dev = np.abs(got - want) / (np.abs(y_host[:, :20000]) + np.abs(want))
+    dev[0] = np.abs(got[0] - want[0]) / np.maximum(np.abs(want[0] - 1), np.abs(y_host[0, :20000] - 1))
+    print(f"parcel (Exponential + Gamma), {n} parcels, {steps} steps per call: (a) cloudy_parcel_ssprk33_steps {ms_a:.3f} ms | (b) staged "
+          f"cloudy_cond_evap + torch thermodynamics and updates {ms_b:.3f} ms | (c) cloudy_box_ssprk33_steps COND {ms_c:.3f} ms | "
+          f"b/a {ms_b / ms_a:.2f} | a/c {ms_a / ms_c:.2f} | (a) = {3 * steps * n / ms_a * 1e3:.3e} parcel-RHS/s | fused vs staged state, "
+          f"first 20000 parcels: {float(dev.max()):.1e}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -287,11 +368,14 @@ def main():
     b = sub.add_parser("box")
     b.add_argument("--parcels", type=int, default=0)
     b.add_argument("--steps", type=int, default=4)
+    pc = sub.add_parser("parcel")
+    pc.add_argument("--parcels", type=int, default=0)
+    pc.add_argument("--steps", type=int, default=2)
     hh = sub.add_parser("host")
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
-    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
+    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
 if __name__ == "__main__":
