@@ -168,19 +168,19 @@ const JitSlot &jit_unit(const cloudy_plan *plan, JitUnit u) {
     return s;
 }
 
-// The column unit that serves columns of nz cells: the one jit_rainshaft_part prefers, then every smaller one that
-// still holds a column and fits the LDS -- a unit that does not compile or load is not the end of the call while another can
-// serve it.  Loads on first use.  JIT_UNITS: none (the caller steps stage by stage, or runs the ahead-of-time integrator).
+// The column unit that serves columns of nz cells: the one of the workgroup size jit_rainshaft_part prefers, then every
+// smaller one that still holds a column and fits the LDS -- a unit that does not compile or load is not the end of the call while
+// another can serve it.  Loads on first use.  JIT_UNITS: none (the caller steps stage by stage, or runs the ahead-of-time integrator).
 // rhs_only: a unit with the one-evaluation kernel (cloudy_rainshaft_rhs).  cond: the same pick among the units with the
-// condensation source (cloudy_rainshaft_cond_*: the same workgroup sizes, the same LDS); the unit returned is then that one.
+// condensation source (cloudy_rainshaft_cond_*: the same workgroup sizes, the same LDS).
 JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, bool rhs_only, bool cond = false) {
     if (!plan->jit_on || nz < 1 || nz > 1024) return JIT_UNITS;
-    const JitUnit pref = jit_rainshaft_part(plan->h, nz, n_columns);
+    const int pref = jit_rainshaft_part(plan->h, nz, n_columns);
     bool reached = false;
-    for (JitUnit u : {JIT_COL1024, JIT_COL512, JIT_COL256}) {
-        reached = reached || u == pref;
-        const JitUnit v = cond ? jit_cond_unit(u) : u;
-        if (reached && jit_rainshaft_fits(plan->h, u, nz) && jit_unit(plan, v).fn[rhs_only ? K_COL_RHS : 0] != nullptr) return v;
+    for (int bs : {1024, 512, 256}) {
+        reached = reached || bs == pref;
+        const JitUnit u = jit_column_unit(bs, cond);
+        if (reached && jit_rainshaft_fits(plan->h, bs, nz) && jit_unit(plan, u).k[rhs_only ? COL_RHS : COL_STEPS].fn != nullptr) return u;
     }
     return JIT_UNITS;
 }
@@ -191,8 +191,8 @@ JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, boo
 // ahead-of-time instances).
 bool rainshaft_cond_staged(const HostPlan &h, size_t nz) {
     if (h.mode == MODE_MOVING || nz > 1024) return true;
-    for (JitUnit u : {JIT_COL1024, JIT_COL512, JIT_COL256})
-        if (jit_rainshaft_fits(h, u, nz)) return false;
+    for (int bs : {1024, 512, 256})
+        if (jit_rainshaft_fits(h, bs, nz)) return false;
     return true;
 }
 
@@ -206,9 +206,14 @@ bool rainshaft_staged(const cloudy_plan *plan, size_t nz, size_t n_columns) {
     return plan->h.mode == MODE_MOVING || pick_rainshaft(plan, nz, n_columns, false) == JIT_UNITS;
 }
 
-// Which unit compiled for the plan serves this call (JIT_UNITS: none -- the ahead-of-time kernels, or the diagnostics below)
+// Which unit compiled for the plan serves this call (JIT_UNITS: none -- the ahead-of-time kernels)
 JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     const HostPlan &h = plan->h;
+    // no ahead-of-time kernel exists for the (N, P) of a plan beyond the families: the diagnostics and the parameter-plane entry
+    // points run the bodies of their ahead-of-time kernels compiled for the plan (the diagnostics unit, on first use)
+    if (plan_beyond_aot(h) && !r.rainshaft && (r.op == OP_UPDATE_DIST || r.op == OP_FINITE_2D || r.op == OP_SEDI || r.op == OP_COND ||
+                                               r.op == OP_NQ || (r.op == OP_COAL && r.input_kind == IN_PARAMS)))
+        return JIT_DIAG;
     if (!plan->jit_on || r.input_kind != IN_MOMENTS || !r.physical_out) return JIT_UNITS;
     switch (r.op) {
     case OP_COAL: return r.rainshaft ? JIT_CELL : JIT_MAIN;
@@ -231,49 +236,33 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     }
 }
 
-// How a call served by unit u of the plan (serving_unit) launches: which of the unit's kernels (K_*), its workgroup size and the
-// parcels (cells) one workgroup takes
-struct JitShape {
-    int k = 0;
-    unsigned block = kBlock;
-    size_t per_wg = kBlock;
-};
-JitShape jit_shape(const HostPlan &h, JitUnit u, const LaunchReq &r) {
-    if (r.op == OP_BOX_SSPRK33) {  // box_kernel() of jit.hpp: the threshold kernels' workgroup only where the parcels are ranked
-        const bool coal = (r.sources & SRC_COAL) != 0;
-        const unsigned bs = coal && h.mode != MODE_ALLINF ? (unsigned)jit_sorted_block_size(h) : (unsigned)kBlock;
-        return {coal ? K_BOX_COAL_COND : K_BOX_COND, bs, bs};
+// Which kernel of unit u (serving_unit) a call launches: its position in the unit's list (jit.hpp).  Every unit not named here has
+// one kernel.
+int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
+    const bool coal = (r.sources & SRC_COAL) != 0;
+    switch (u) {
+    case JIT_MAIN: {
+        if (h.coal_style == CLOUDY_NUMERICAL_COAL || h.mode != MODE_ALLINF) return 0;
+        if (r.op == OP_SSPRK33) return MAIN_SSPRK33;
+        const int ppl = allinf_parcels_per_lane(h, r, h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double), jit_allinf_f32_fast(h));
+        return ppl == 4 ? MAIN_ALLINF4 : ppl == 2 ? MAIN_ALLINF2 : MAIN_PPL1;
     }
-    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS) {  // parcel_kernel() of jit.hpp
-        const bool coal = (r.sources & SRC_COAL) != 0;
-        return {r.op == OP_PARCEL_RHS ? (coal ? K_PARCEL_RHS_COAL : K_PARCEL_RHS) : (coal ? K_PARCEL_COAL_COND : K_PARCEL_COND), kBlock, kBlock};
+    case JIT_BOX: return coal ? BOX_COALCOND : BOX_COND;
+    case JIT_PARCEL: return r.op == OP_PARCEL_RHS ? (coal ? PARCEL_RHS_COAL : PARCEL_RHS) : (coal ? PARCEL_COALCOND : PARCEL_COND);
+    case JIT_DIAG:
+        return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
+               : r.op == OP_COND      ? DIAG_COND_EVAP   : r.op == OP_NQ        ? DIAG_STANDARD_NQ : DIAG_COAL_INTS;
+    default: return jit_is_column(u) && (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) ? COL_RHS : 0;
     }
-    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
-        const unsigned bs = (unsigned)jit_rainshaft_block(u);   // whole columns per workgroup, as launch_int_io()
-        return {r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS ? K_COL_RHS : 0, bs, bs / r.nz * r.nz};
-    }
-    if (h.coal_style == CLOUDY_NUMERICAL_COAL) {
-        const bool conv = h.q.mode == QUAD_CONVERGED;
-        const unsigned qb = conv ? (unsigned)jit_conv_block_size(h) : (unsigned)quad_block(h.q.nq);
-        return {0, qb, (size_t)qb * (r.op == OP_COAL && conv ? h.jit_conv_rounds : 1)};
-    }
-    if (h.mode != MODE_ALLINF && r.op != OP_TSIT5) {  // the threshold kernels: RHS, cell body, SSPRK33 integrator
-        const unsigned bs = (unsigned)jit_sorted_block_size(h);
-        return {0, bs, bs};
-    }
-    if (r.op == OP_TSIT5 || r.rainshaft) return {};
-    if (r.op == OP_SSPRK33) return {K_SSPRK33};
-    const size_t esz = h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double);
-    const int ppl = allinf_parcels_per_lane(h, r, esz, jit_allinf_f32_fast(h));
-    return {ppl == 4 ? K_ALLINF4 : ppl == 2 ? 0 : K_PPL1, kBlock, (size_t)ppl * kBlock};
 }
 
+// One launch of a kernel compiled for the plan: the arguments by the tags of its signature, the grid by its workgroup size and the
+// parcels a lane takes (a column kernel: whole columns per workgroup, as launch_int_io())
 hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
     const HostPlan &h = plan->h;
-    const JitShape s = jit_shape(h, u, r);
-    const bool numerical = h.coal_style == CLOUDY_NUMERICAL_COAL;
-    ConvHints hints = numerical && h.q.mode == QUAD_CONVERGED ? conv_hints(plan, r.n, r.stream) : ConvHints{};
-    // the kernel's arguments in the order of its signature (jit.hpp)
+    const JitSlot::Kernel &k = jit_unit(plan, u).k[jit_position(h, u, r)];
+    if (!k.fn) return hipErrorInvalidValue;
+    ConvHints hints;
     const double *nodes = h.nodes_dev;
     size_t n = r.n, ld = r.ld, n_columns = r.nz ? r.n / r.nz : 0;
     const void *in = r.in;
@@ -283,78 +272,36 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
     int aligned16 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     double coef = r.coef, s_scalar = r.s_scalar;
     const double *s_dev = r.s_dev;
-    void *args[12];
-    int na = 0;
-    const auto push = [&](std::initializer_list<void *> a) {
-        for (void *p : a) args[na++] = p;
-    };
-    if (r.op == OP_RAINSHAFT_SSPRK33 || r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
-        push({&nodes, &nz, &n_columns, &ld, &in, &out});
-        if (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) push({&out2, &dz});
-        else push({&dt, &dz, &n_steps});
-        if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) push({&coef, &s_scalar, &s_dev});
-    } else if (r.op == OP_BOX_SSPRK33) {
-        push({&nodes, &n, &ld, &in, &out, &coef, &s_scalar, &s_dev, &dt, &n_steps});
-    } else if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS) {   // (the ParcelParams by value: the pointer to them)
-        push({const_cast<void *>(r.parcel), &n, &ld, &in, &out, &coef, &s_scalar, &s_dev});
-        if (r.op == OP_PARCEL_SSPRK33) push({&dt, &n_steps});
-    } else {
-        if (!numerical && (h.mode != MODE_ALLINF || r.op == OP_TSIT5)) push({&nodes});
-        push({&n, &ld, &in, &out});
-        if (r.op != OP_COAL) push({&dt, &n_steps});
-        if (numerical) push({&hints.p1, &hints.p2});
-        else if (r.rainshaft) push({&out2});  // the cell body: the sedimentation flux planes, or null
-        else if (s.k == K_ALLINF4) push({&aligned16});  // 16-B accesses where the planes allow them, scalar ones otherwise
-    }
-    return hipModuleLaunchKernel(jit_unit(plan, u).fn[s.k], (unsigned)((n + s.per_wg - 1) / s.per_wg), 1, 1, s.block, 1, 1, 0,
-                                 r.stream, args, nullptr);
-}
-
-// the diagnostics of a plan beyond the ahead-of-time families: argument lists as the kernels of launch_impl.hpp take them,
-// minus the constant block (a compile-time object of the module)
-hipError_t launch_diag(const cloudy_plan *plan, const LaunchReq &r) {
-    const HostPlan &h = plan->h;
-    size_t n = r.n, ld = r.ld;
-    const void *in = r.in;
-    void *out = r.out, *out2 = r.out2;
-    const double *nodes = h.nodes_dev;
-    const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
-    const hipFunction_t *fns = jit_unit(plan, JIT_DIAG).fn;
-    hipFunction_t fn = nullptr;
-    void *args[8];
-    int na = 0;
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-    const double *s_dev = r.s_dev;
-    switch (r.op) {
-    case OP_UPDATE_DIST:
-        fn = fns[K_UPDATE_DIST];
-        args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
-        break;
-    case OP_FINITE_2D:
-        fn = fns[K_FINITE_2D];
-        args[na++] = &nodes, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out, args[na++] = &out2;
-        break;
-    case OP_SEDI:
-        fn = fns[K_SEDI_FLUX];
-        args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
-        break;
-    case OP_COND:
-        fn = fns[K_COND_EVAP];
-        d0 = r.coef, d1 = r.s_scalar;
-        args[na++] = &d0, args[na++] = &d1, args[na++] = &s_dev, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
-        break;
-    case OP_NQ:
-        fn = fns[K_STANDARD_NQ];
-        d0 = r.s_scalar / h.norms[1], d1 = h.norms[0], d2 = h.norms[1];
-        args[na++] = &d0, args[na++] = &d1, args[na++] = &d2, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
-        break;
-    case OP_COAL:
-        fn = fns[K_COAL_INTS];
-        args[na++] = &nodes, args[na++] = &n, args[na++] = &ld, args[na++] = &in, args[na++] = &out;
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipModuleLaunchKernel(fn, g, 1, 1, kBlock, 1, 1, 0, r.stream, args, nullptr);
+    double nq_cutoff = r.s_scalar / h.norms[1], nq_n0 = h.norms[0], nq_m0 = h.norms[1];
+    void *args[kJitMaxArgs];
+    for (int i = 0; i < k.n_args; ++i) switch (k.args[i]) {
+        case A_NODES: args[i] = &nodes; break;
+        case A_N: args[i] = &n; break;
+        case A_LD: args[i] = &ld; break;
+        case A_IN: args[i] = &in; break;
+        case A_OUT: args[i] = &out; break;
+        case A_OUT2: args[i] = &out2; break;   // (the cell body: the sedimentation flux planes, or null)
+        case A_DT: args[i] = &dt; break;
+        case A_DZ: args[i] = &dz; break;
+        case A_NSTEPS: args[i] = &n_steps; break;
+        case A_NZ: args[i] = &nz; break;
+        case A_NCOLUMNS: args[i] = &n_columns; break;
+        case A_COEF: args[i] = &coef; break;
+        case A_SSCALAR: args[i] = &s_scalar; break;
+        case A_SDEV: args[i] = &s_dev; break;
+        case A_HINT1:   // the cost hints of the converged mode, fetched (allocated on first use) once per launch
+            if (h.q.mode == QUAD_CONVERGED) hints = conv_hints(plan, r.n, r.stream);
+            args[i] = &hints.p1;
+            break;
+        case A_HINT2: args[i] = &hints.p2; break;
+        case A_ALIGNED16: args[i] = &aligned16; break;
+        case A_PARCEL: args[i] = const_cast<void *>(r.parcel); break;   // (by value: the pointer to them)
+        case A_NQ_CUTOFF: args[i] = &nq_cutoff; break;
+        case A_NQ_N0: args[i] = &nq_n0; break;
+        case A_NQ_M0: args[i] = &nq_m0; break;
+        }
+    const size_t per_wg = k.per_lane ? (size_t)k.block * k.per_lane : (size_t)k.block / r.nz * r.nz;
+    return hipModuleLaunchKernel(k.fn, (unsigned)((n + per_wg - 1) / per_wg), 1, 1, (unsigned)k.block, 1, 1, 0, r.stream, args, nullptr);
 }
 
 int launch(const cloudy_plan *plan, const LaunchReq &r);
@@ -491,29 +438,34 @@ int rainshaft_cond_rhs_unfused(const cloudy_plan *plan, const LaunchReq &r) {
     return CLOUDY_OK;
 }
 
+// A call that only kernels compiled for the plan serve, and unit u is not there: the refusal, with the unit's log (the main unit's
+// where plan-time compilation is off altogether).  what: "... compiled for the plan (hiprtc)".
+int refuse_without_unit(const cloudy_plan *plan, JitUnit u, const char *what) {
+    return fail(CLOUDY_EUNSUPPORTED, "%s; plan-time compilation is off or failed: %s", what,
+                (plan->jit_on ? jit_unit(plan, u) : plan->jit[JIT_MAIN]).log.c_str());
+}
+
 // One request on the plan's device (run() selected it): the kernels compiled for the plan where a unit serves the call, the calls
 // that take several launches, then the ahead-of-time kernels where they exist
 int launch(const cloudy_plan *plan, const LaunchReq &r) {
     const JitUnit u = serving_unit(plan, r);
     if (u != JIT_UNITS && jit_unit(plan, u).ok) {
         hipError_t e = launch_jit(plan, u, r);
-        if (e != hipSuccess) return fail_hip(e, r.op == OP_RAINSHAFT_RHS ? "column right-hand side launch" : "specialised kernel launch");
+        if (e != hipSuccess)
+            return fail_hip(e, u == JIT_DIAG ? "diagnostic kernel launch" : r.op == OP_RAINSHAFT_RHS ? "column right-hand side launch"
+                                                                                                       : "specialised kernel launch");
         return CLOUDY_OK;
     }
     if (r.op == OP_BOX_SSPRK33)
-        return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_ssprk33_steps with the condensation source runs the kernel compiled for the plan "
-                                         "(hiprtc); plan-time compilation is off or failed: %s",
-                    plan->jit_on ? jit_unit(plan, JIT_BOX).log.c_str() : plan->jit[JIT_MAIN].log.c_str());
+        return refuse_without_unit(plan, JIT_BOX, "cloudy_box_ssprk33_steps with the condensation source runs the kernel compiled for "
+                                                  "the plan (hiprtc)");
     if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS)
-        return fail(CLOUDY_EUNSUPPORTED, "the parcel kernels are compiled for the plan (hiprtc); plan-time compilation is off or "
-                                         "failed: %s", plan->jit_on ? jit_unit(plan, JIT_PARCEL).log.c_str() : plan->jit[JIT_MAIN].log.c_str());
+        return refuse_without_unit(plan, JIT_PARCEL, "the parcel kernels are compiled for the plan (hiprtc)");
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
-        return fail(CLOUDY_EUNSUPPORTED, "the column kernels with the condensation source are compiled for the plan (hiprtc); "
-                                         "plan-time compilation is off or failed: %s",
-                    plan->jit_on ? jit_unit(plan, jit_cond_unit(jit_rainshaft_part(plan->h, r.nz, r.n / r.nz))).log.c_str()
-                                 : plan->jit[JIT_MAIN].log.c_str());
+        return refuse_without_unit(plan, jit_column_unit(jit_rainshaft_part(plan->h, r.nz, r.n / r.nz), true),
+                                   "the column kernels with the condensation source are compiled for the plan (hiprtc)");
     }
     if (r.op == OP_RAINSHAFT_RHS) return rainshaft_rhs_unfused(plan, r);
     if (r.op == OP_RAINSHAFT_SSPRK33 && rainshaft_staged(plan, r.nz, r.n / r.nz)) return rainshaft_staged_steps(plan, r);
@@ -529,27 +481,18 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         return rc ? rc : launch(plan, sedi);
     }
     if (r.op == OP_TSIT5 && plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
-        return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_steps of a NumericalCoalStyle plan runs the kernel compiled for the plan "
-                                         "(hiprtc); plan-time compilation is off or failed: %s", jit_unit(plan, JIT_TSIT5).log.c_str());
-    if (r.op == OP_RAINSHAFT_SSPRK33 && r.nz > (size_t)kRainshaftBlock)
-        return fail(CLOUDY_EUNSUPPORTED, "columns of %zu cells run the column integrator compiled for the plan (hiprtc, up to 1024 "
-                                         "cells); plan-time compilation is off or failed: %s", r.nz,
-                    jit_unit(plan, r.nz <= 512 ? JIT_COL512 : JIT_COL1024).log.c_str());
-    if (plan_beyond_aot(plan->h)) {
-        // no ahead-of-time kernel exists for this (N, P): the diagnostics and the parameter-plane entry points run the
-        // bodies of their ahead-of-time kernels compiled for the plan (the diagnostics unit, on first use)
-        const bool diag_op = !r.rainshaft && (r.op == OP_UPDATE_DIST || r.op == OP_FINITE_2D || r.op == OP_SEDI || r.op == OP_COND ||
-                                              r.op == OP_NQ || (r.op == OP_COAL && r.input_kind == IN_PARAMS));
-        const JitSlot *diag = diag_op ? &jit_unit(plan, JIT_DIAG) : nullptr;
-        if (diag && diag->ok) {
-            hipError_t e = launch_diag(plan, r);
-            if (e != hipSuccess) return fail_hip(e, "diagnostic kernel launch");
-            return CLOUDY_OK;
-        }
+        return refuse_without_unit(plan, JIT_TSIT5, "cloudy_tsit5_steps of a NumericalCoalStyle plan runs the kernel compiled for the "
+                                                    "plan (hiprtc)");
+    if (r.op == OP_RAINSHAFT_SSPRK33 && r.nz > (size_t)kRainshaftBlock) {
+        char what[128];
+        std::snprintf(what, sizeof what, "columns of %zu cells run the column integrator compiled for the plan (hiprtc, up to 1024 cells)",
+                      r.nz);
+        return refuse_without_unit(plan, r.nz <= 512 ? JIT_COL512 : JIT_COL1024, what);
+    }
+    if (plan_beyond_aot(plan->h))
         return fail(CLOUDY_EUNSUPPORTED, "plans of more than %d modes or order > %d are served by the kernels compiled for the plan "
                                          "(this call has none, or its compilation failed: %s)",
-                    CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, diag ? diag->log.c_str() : "");
-    }
+                    CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, u == JIT_DIAG ? jit_unit(plan, u).log.c_str() : "");
     hipError_t e = dispatch(plan->h, r);
     if (e != hipSuccess) return fail_hip(e, "kernel launch");
     return CLOUDY_OK;
@@ -1002,9 +945,25 @@ int cloudy_jit_selfcheck(const cloudy_plan_desc *d, const char *arch) {
         const JitUnit u = (JitUnit)i;
         const JitUnitDesc ud = jit_unit_desc(p->h, u);
         if (!ud.exists) continue;
-        for (const JitKernel &k : ud.kernels)
-            if (rc == CLOUDY_OK && !k.optional && !k.name.empty() && ud.src.find(" " + k.name + "(") == std::string::npos)
-                rc = fail(CLOUDY_EUNSUPPORTED, "plan-time %s unit: kernel %s is not defined in its source", jit_unit_name(u), k.name.c_str());
+        if (ud.kernels.size() > (size_t)kJitMaxKernels)
+            rc = fail(CLOUDY_EUNSUPPORTED, "plan-time %s unit: more kernels than a unit's slot holds", jit_unit_name(u));
+        for (const JitKernel &k : ud.kernels) {
+            if (rc != CLOUDY_OK || k.name.empty()) continue;
+            const size_t at = ud.src.find(" " + k.name + "(");
+            if (at == std::string::npos) {
+                if (!k.optional)
+                    rc = fail(CLOUDY_EUNSUPPORTED, "plan-time %s unit: kernel %s is not defined in its source", jit_unit_name(u), k.name.c_str());
+                continue;
+            }
+            // the launch fills one argument per tag: as many tags as the signature's text has parameters, no more than a launch holds
+            const size_t open = at + k.name.size() + 2, close = ud.src.find(')', open);
+            size_t n_params = close == std::string::npos ? 0 : 1;
+            for (size_t c = open; c < close && close != std::string::npos; ++c) n_params += ud.src[c] == ',';
+            if (n_params != k.params.size() || n_params > (size_t)kJitMaxArgs || k.block < 64 || k.block > 1024 || k.per_lane < 0)
+                rc = fail(CLOUDY_EUNSUPPORTED, "plan-time %s unit: kernel %s is declared with %zu argument tags, its text has %zu parameters "
+                                               "(a launch holds %d; workgroup %d)", jit_unit_name(u), k.name.c_str(), k.params.size(), n_params,
+                          kJitMaxArgs, k.block);
+        }
         std::string log;
         std::vector<char> code;
         if (rc == CLOUDY_OK && a != "source-only" && !jit_compile(ud.src, a, ud.licm_off, code, log))

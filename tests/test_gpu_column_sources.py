@@ -474,3 +474,45 @@ def test_float_planes_with_the_source_on(gpu_cloudy, oracle, case):
     print(f"float planes {case}: existing integrator {fig[0]:.3e}, with condensation {fig[1]:.3e} of the plane maxima")
     assert np.isfinite(res[np.float32][1]).all() and res[np.float32][1].min() >= 0.0
     assert fig[0] > 0.0 and fig[1] <= 8.0 * fig[0]
+
+
+@pytest.mark.parametrize("case", ["gamma_mixture", "single_gamma"])
+def test_the_256_thread_units_with_a_partly_filled_second_workgroup(gpu_cloudy, oracle, case, monkeypatch):
+    """The batches above are served by the 512- and 1024-thread units.  The first 13 columns of (1) at CLOUDY_HIP_RS_BLOCK=256: twelve
+    columns per 256-thread workgroup and a second workgroup with one, in buffers with ld = 320 > n = 260 (sentinel padding,
+    untouched).  Columns do not interact, so the oracle end state of (1) restricted to these columns is their reference, at the
+    bound of (1); one evaluation of the right-hand side against cloudy_rainshaft_rhs + cloudy_cond_evap at the bound of
+    test_degenerate_cells_with_the_source_on (the same two roundings: 1e-13 of |rhs| + |cond|)."""
+    cloudy = gpu_cloudy
+    L = cloudy.lib()
+    c = shared(cloudy, oracle, case)
+    ncol, ld = 13, 320
+    n = NZ * ncol
+    nm = c["u0"].shape[0]
+    buf = np.zeros((nm, ld))
+    buf.view(np.uint64)[:] = SENTINEL
+    buf[:, :n] = c["u0"][:, :n]
+    plan = c["par"].coal_data.plan(c["dist_types"], vel=VEL)
+    s_dev = dev(cloudy, np.ascontiguousarray(c["s"][:n])[None, :])
+    u_in, u_out = dev(cloudy, buf), dev(cloudy, buf)
+    monkeypatch.setenv("CLOUDY_HIP_RS_BLOCK", "256")
+    cloudy._lib.check(L.cloudy_rainshaft_cond_ssprk33_steps(plan.handle, NZ, ncol, ld, u_in.ptr, u_out.ptr, s_dev.ptr, 0.0, XI, DZ, DT,
+                                                            N_STEPS, None))
+    got, want = u_out.to_numpy(), c["want"][:, :n]
+    assert np.all(got.view(np.uint64)[:, n:] == SENTINEL)
+    err = np.abs(got[:, :n] - want) / (np.abs(want).max(axis=1, keepdims=True) + 1e-300)
+    print(f"256-thread column unit with condensation, {case}: {N_STEPS} steps, max |hip-oracle| / max|plane| = {err.max():.2e}")
+    assert err.max() < 1e-9 and got[:, :n].min() >= 0.0
+    assert np.abs(got[:, :n] - c["plain"][:, :n]).max() > 1e-3 * np.abs(c["plain"][:, :n]).max()   # the source acted
+    # one evaluation on the clamped initial state
+    x = dev(cloudy, np.maximum(buf, 0.0))
+    fused, work, base, cond = (dev(cloudy, buf) for _ in range(4))
+    cloudy._lib.check(L.cloudy_rainshaft_cond_rhs(plan.handle, NZ, ncol, ld, x.ptr, s_dev.ptr, 0.0, XI, DZ, work.ptr, fused.ptr, None))
+    cloudy._lib.check(L.cloudy_rainshaft_rhs(plan.handle, NZ, ncol, ld, x.ptr, DZ, work.ptr, base.ptr, None))
+    cloudy._lib.check(L.cloudy_cond_evap(plan.handle, n, ld, x.ptr, s_dev.ptr, 0.0, XI, cond.ptr, None))
+    fused, base, cond = fused.to_numpy(), base.to_numpy()[:, :n], cond.to_numpy()[:, :n]
+    assert np.all(fused.view(np.uint64)[:, n:] == SENTINEL)
+    assert np.isfinite(fused[:, :n]).all() and np.isfinite(base + cond).all() and np.abs(cond).max() > 0.0
+    err = np.abs(fused[:, :n] - (base + cond)) / np.maximum(np.abs(base) + np.abs(cond), 1e-300)
+    print(f"256-thread column unit with condensation, {case}: max |fused - (rhs + cond)| / (|rhs| + |cond|) = {err.max():.2e}")
+    assert err.max() <= 1e-13

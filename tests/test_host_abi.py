@@ -417,17 +417,17 @@ def test_polyfit_reference_kats(cloudy):
     assert h.c[0, 0] == np.finfo(np.float64).eps / 1e6
 
 
-@pytest.mark.parametrize("case", ["cfg2", "cfg3a", "cfg3a_f32", "cfg3b", "cfg3b_f32fast", "cfg3_moving", "cfg4",
-                                  "n4p5_mixed", "n6p2_beyond_aot", "n5p3_fixed_beyond_aot", "n2p8_fixed_beyond_aot",
-                                  "n6p2_moving_beyond_aot"])
-def test_plan_time_translation_units_compile_without_a_gpu(cloudy, case):
-    """cloudy_jit_selfcheck: the kernel sources embedded in libcloudy_hip.so plus the generated constexpr plan compile
-    with hiprtc for gfx950 here, on the CPU -- the build check of the plan-time specialisation (jit.hpp).  Thresholded
-    plans compile two units (single-pass kernel; fused integrator)."""
+SELFCHECK_CASES = ["cfg2", "cfg3a", "cfg3a_f32", "cfg3b", "cfg3b_f32fast", "cfg3_moving", "cfg4", "n4p5_mixed", "n6p2_beyond_aot",
+                   "n5p3_fixed_beyond_aot", "n2p8_fixed_beyond_aot", "n6p2_moving_beyond_aot"]
+
+
+def _selfcheck_desc(cloudy, case):
     import bench
 
-    L = cloudy.lib()
     moving, dtype = 0, 0
+    if case == "column_two_mode":   # the reference's two-mode column plan (rainshaft_gamma_mixture.jl): Golovin, one velocity term
+        return cloudy.Plan.make_desc([1, 1], np.array([[2.220446049250313e-22, 5.0], [5.0, 0.0]]), (2e-10, INF), bench.NORMS, 0,
+                                     vel=((50.0, 1.0 / 6),))
     if case == "n4p5_mixed":
         rng = np.random.default_rng(7)
         N, P = 4, 5
@@ -454,10 +454,30 @@ def test_plan_time_translation_units_compile_without_a_gpu(cloudy, case):
         dtype = {"cfg3a_f32": 1, "cfg3b_f32fast": 2}.get(case, 0)
         if case == "cfg3_moving":
             moving, thr = 1, (0.9, 1.0)
-    d, keep = cloudy.Plan.make_desc(dist_types, kc, thr, bench.NORMS, moving, dtype=dtype)
+    return cloudy.Plan.make_desc(dist_types, kc, thr, bench.NORMS, moving, dtype=dtype)
+
+
+@pytest.mark.parametrize("case", SELFCHECK_CASES)
+def test_plan_time_translation_units_compile_without_a_gpu(cloudy, case):
+    """cloudy_jit_selfcheck: the kernel sources embedded in libcloudy_hip.so plus the generated constexpr plan compile
+    with hiprtc for gfx950 here, on the CPU -- the build check of the plan-time specialisation (jit.hpp).  Thresholded
+    plans compile two units (single-pass kernel; fused integrator)."""
+    L = cloudy.lib()
+    d, keep = _selfcheck_desc(cloudy, case)
     rc = L.cloudy_jit_selfcheck(C.byref(d), b"gfx950")
     assert rc == 0, L.cloudy_last_error().decode()
     assert keep is not None
+
+
+@pytest.mark.parametrize("case", SELFCHECK_CASES + ["column_two_mode"])
+def test_every_plan_time_kernel_has_one_argument_tag_per_parameter(cloudy, case):
+    """A launch fills one argument per tag of the kernel's description (jit.hpp, JitKernel::params).  cloudy_jit_selfcheck
+    refuses a unit in which a kernel's name, the parameter list of its text and its tag count disagree (beside its "is not
+    defined in its source" check): for every unit that exists for these plans -- the six column units of the reference's
+    two-mode column plan among them -- it finds nothing.  "source-only": the text alone, nothing is compiled."""
+    L = cloudy.lib()
+    d, keep = _selfcheck_desc(cloudy, case)
+    assert L.cloudy_jit_selfcheck(C.byref(d), b"source-only") == 0, L.cloudy_last_error().decode()
 
 
 def test_jit_selfcheck_reports_descriptor_errors(cloudy):
