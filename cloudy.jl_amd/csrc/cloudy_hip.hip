@@ -13,6 +13,7 @@
 #include <vector>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -121,6 +122,52 @@ int fail_hip(hipError_t e, const char *what) {
 
 constexpr int kSumBlocks = 1024;
 
+// A plan on its way to the caller: destroyed on every return that does not release it (cloudy_plan_destroy skips the device
+// resources a plan does not have yet, so a plan without a device is deleted without a HIP call)
+struct PlanDestroy {
+    void operator()(cloudy_plan *p) const { cloudy_plan_destroy(p); }
+};
+using PlanHandle = std::unique_ptr<cloudy_plan, PlanDestroy>;
+
+// One plain hipMalloc allocation, freed on return.  hipFree waits for the device: the kernels launched on the allocation are done
+// when the function that owns it returns.
+struct DeviceScratch {
+    char *p = nullptr;
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    ~DeviceScratch() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc((void **)&p, bytes); }
+};
+
+// A HIP event, destroyed on return if it was created (or adopted) and not released
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    explicit Event(hipEvent_t adopted) : ev(adopted) {}
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    hipError_t create() { return hipEventCreate(&ev); }
+    hipEvent_t release() { return std::exchange(ev, nullptr); }
+};
+
+// Bytes per element of the plan's planes
+size_t plane_bytes(const HostPlan &h) { return h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double); }
+
+// One launch of a kernel templated on the plan's plane type: launch(T{}) with T = float or double issues it, the launch's error
+// comes back
+template <class Launch>
+hipError_t with_plane_type(const HostPlan &h, Launch &&launch) {
+    if (h.dtype != CLOUDY_F64) launch(float{});
+    else launch(double{});
+    return hipGetLastError();
+}
+
 hipError_t dispatch(const HostPlan &h, const LaunchReq &r) {
     using Fn = hipError_t (*)(const HostPlan &, const LaunchReq &);
     static const Fn table[CLOUDY_AOT_MAX_MODES][CLOUDY_AOT_MAX_P] = {
@@ -159,6 +206,32 @@ int check_batch(const cloudy_plan *plan, size_t n, size_t ld, const void *a, con
     if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
     if (n > 0 && (!a || !b)) return fail(CLOUDY_EINVAL, "device buffer is NULL");
     return CLOUDY_OK;
+}
+
+// What the entry points share beyond check_batch, each in the order the entry point names them: the steps of an integrator ...
+int check_steps(int n_steps, double dt) {
+    if (n_steps < 0 || !(dt == dt)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
+    return CLOUDY_OK;
+}
+// ... the batch of a column call (n = nz * n_columns cells) and its grid ...
+int check_columns(const cloudy_plan *plan, size_t nz, size_t n, size_t ld, const void *a, const void *b, double dz) {
+    if (int rc = check_batch(plan, n, ld, a, b)) return rc;
+    if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
+    return CLOUDY_OK;
+}
+// ... and the plan of a call that forms the sedimentation flux (fixed: one of make_rainshaft_rhs's, which uses FixedThreshold)
+int check_velocity(const cloudy_plan *plan, bool fixed) {
+    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
+    if (fixed && plan->h.threshold_style != CLOUDY_FIXED_THRESHOLD)
+        return fail(CLOUDY_EINVAL, "make_rainshaft_rhs uses FixedThreshold (rainshaft_helpers.jl:70)");
+    return CLOUDY_OK;
+}
+
+// the folded coefficient of get_cond_evap (rhs_condensation!): xi_normalized = p.xi / norms[2]^(2/3) (box_model_helpers.jl:65);
+// rho_l = 1000 (Condensation.jl:26)
+double cond_coef(const cloudy_plan *plan, double xi) {
+    const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
+    return 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
 }
 
 // Unit u of the plan, compiled and loaded on first use (the main unit at plan creation); never ok when plan-time compilation is off.
@@ -244,7 +317,7 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
     case JIT_MAIN: {
         if (h.coal_style == CLOUDY_NUMERICAL_COAL || h.mode != MODE_ALLINF) return 0;
         if (r.op == OP_SSPRK33) return MAIN_SSPRK33;
-        const int ppl = allinf_parcels_per_lane(h, r, h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double), jit_allinf_f32_fast(h));
+        const int ppl = allinf_parcels_per_lane(h, r, plane_bytes(h), jit_allinf_f32_fast(h));
         return ppl == 4 ? MAIN_ALLINF4 : ppl == 2 ? MAIN_ALLINF2 : MAIN_PPL1;
     }
     case JIT_BOX: return coal ? BOX_COALCOND : BOX_COND;
@@ -311,16 +384,14 @@ int launch(const cloudy_plan *plan, const LaunchReq &r);
 int rainshaft_rhs_unfused(const cloudy_plan *plan, const LaunchReq &r) {
     LaunchReq src = r;
     src.op = OP_COAL;
-    const int rc = launch(plan, src);
-    if (rc) return rc;
+    if (int rc = launch(plan, src)) return rc;
     const unsigned g = (unsigned)((r.n + kBlock - 1) / kBlock);
-    if (plan->h.dtype != CLOUDY_F64)
-        hipLaunchKernelGGL(rainshaft_divergence_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, r.n, r.ld, plan->h.nmom, r.nz,
-                           r.dz, (const float *)r.out2, (float *)r.out);
-    else
-        hipLaunchKernelGGL(rainshaft_divergence_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, r.n, r.ld, plan->h.nmom, r.nz,
-                           r.dz, (const double *)r.out2, (double *)r.out);
-    HIP_TRY(hipGetLastError());
+    const hipError_t e = with_plane_type(plan->h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(rainshaft_divergence_kernel<T>, dim3(g), dim3(kBlock), 0, r.stream, r.n, r.ld, plan->h.nmom, r.nz, r.dz,
+                           (const T *)r.out2, (T *)r.out);
+    });
+    if (e != hipSuccess) return fail_hip(e, "hipGetLastError()");
     return CLOUDY_OK;
 }
 
@@ -338,13 +409,13 @@ int rainshaft_rhs_unfused(const cloudy_plan *plan, const LaunchReq &r) {
 int rainshaft_staged_steps(const cloudy_plan *plan, const LaunchReq &r) {
     const HostPlan &h = plan->h;
     const bool cond = r.op == OP_RAINSHAFT_COND_SSPRK33;
-    const size_t n = r.n, ld = r.ld, bytes = (size_t)h.nmom * ld * (h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double));
+    const size_t n = r.n, ld = r.ld, bytes = (size_t)h.nmom * ld * plane_bytes(h);
     hipError_t e = hipSuccess;
     if (r.out != r.in) e = hipMemcpyAsync(r.out, r.in, bytes, hipMemcpyDeviceToDevice, r.stream);
-    char *ws = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void **)&ws, (cond ? 4 : 3) * bytes);
+    DeviceScratch ws;   // (freed on return, which waits for the steps)
+    if (e == hipSuccess) e = ws.alloc((cond ? 4 : 3) * bytes);
     if (e != hipSuccess) return fail_hip(e, "scratch of the stage-by-stage column integrator");
-    void *up = ws, *f = ws + bytes, *flux = ws + 2 * bytes, *g_cond = ws + 3 * bytes;
+    void *up = ws.p, *f = ws.p + bytes, *flux = ws.p + 2 * bytes, *g_cond = ws.p + 3 * bytes;
     LaunchReq ce(OP_COND, n, ld, r.out, g_cond, r.stream);
     ce.coef = r.coef;
     ce.s_scalar = r.s_scalar;
@@ -356,38 +427,32 @@ int rainshaft_staged_steps(const cloudy_plan *plan, const LaunchReq &r) {
     rhs.dz = r.dz;
     const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
     const int planes = h.nmom;
-    const auto stage = [&](int sidx) -> hipError_t {
-        if (h.dtype != CLOUDY_F64)
-            hipLaunchKernelGGL(rainshaft_stage_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, sidx, n, ld, planes, (float *)up,
-                               (float *)r.out, (const float *)f, r.dt);
-        else
-            hipLaunchKernelGGL(rainshaft_stage_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, sidx, n, ld, planes, (double *)up,
-                               (double *)r.out, (const double *)f, r.dt);
-        return hipGetLastError();
+    const auto status = [](hipError_t e) { return e == hipSuccess ? (int)CLOUDY_OK : fail_hip(e, "stage-by-stage column integrator"); };
+    const auto stage = [&](int sidx) {
+        return status(with_plane_type(h, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(rainshaft_stage_kernel<T>, dim3(g), dim3(kBlock), 0, r.stream, sidx, n, ld, planes, (T *)up, (T *)r.out,
+                               (const T *)f, r.dt);
+        }));
     };
-    const auto add_cond = [&]() -> hipError_t {
-        if (h.dtype != CLOUDY_F64)
-            hipLaunchKernelGGL(rainshaft_add_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, planes, (float *)f,
-                               (const float *)g_cond);
-        else
-            hipLaunchKernelGGL(rainshaft_add_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, planes, (double *)f,
-                               (const double *)g_cond);
-        return hipGetLastError();
+    const auto add_cond = [&] {
+        return status(with_plane_type(h, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(rainshaft_add_kernel<T>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, planes, (T *)f, (const T *)g_cond);
+        }));
     };
-    int rc = CLOUDY_OK;
-    for (int step = 0; step < r.n_steps && rc == CLOUDY_OK && e == hipSuccess; ++step)
-        for (int sidx = 0; sidx < 3 && rc == CLOUDY_OK && e == hipSuccess; ++sidx) {
-            if (cond) e = stage(3);
-            if (e == hipSuccess) rc = launch(plan, rhs);
-            if (cond && rc == CLOUDY_OK && e == hipSuccess) rc = launch(plan, ce);
-            if (cond && rc == CLOUDY_OK && e == hipSuccess) e = add_cond();
-            if (rc == CLOUDY_OK && e == hipSuccess) e = stage(sidx);
+    for (int step = 0; step < r.n_steps; ++step)
+        for (int sidx = 0; sidx < 3; ++sidx) {
+            if (cond)
+                if (int rc = stage(3)) return rc;
+            if (int rc = launch(plan, rhs)) return rc;
+            if (cond) {
+                if (int rc = launch(plan, ce)) return rc;
+                if (int rc = add_cond()) return rc;
+            }
+            if (int rc = stage(sidx)) return rc;
         }
-    if (rc == CLOUDY_OK && e == hipSuccess && r.n_steps > 0) e = stage(3);
-    (void)hipFree(ws);   // (waits for the steps)
-    if (rc != CLOUDY_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "stage-by-stage column integrator");
-    return CLOUDY_OK;
+    return r.n_steps > 0 ? stage(3) : (int)CLOUDY_OK;
 }
 
 // cloudy_rainshaft_cond_rhs without a column unit: rainshaft_rhs_unfused + cond_evap + an add.  The column RHS clamps its
@@ -395,46 +460,34 @@ int rainshaft_staged_steps(const cloudy_plan *plan, const LaunchReq &r) {
 // rainshaft_staged_steps says.
 int rainshaft_cond_rhs_unfused(const cloudy_plan *plan, const LaunchReq &r) {
     const HostPlan &h = plan->h;
-    const bool f32 = h.dtype != CLOUDY_F64;
-    const size_t n = r.n, ld = r.ld, bytes = (size_t)h.nmom * ld * (f32 ? sizeof(float) : sizeof(double));
-    char *ws = nullptr;
-    hipError_t e = hipMalloc((void **)&ws, 2 * bytes);
+    const size_t n = r.n, ld = r.ld, bytes = (size_t)h.nmom * ld * plane_bytes(h);
+    DeviceScratch ws;   // (freed on return, which waits for the launches)
+    hipError_t e = ws.alloc(2 * bytes);
     if (e != hipSuccess) return fail_hip(e, "scratch of the unfused column right-hand side with condensation");
-    void *uc = ws, *g_cond = ws + bytes;
+    static const char kWhat[] = "unfused column right-hand side with condensation";
+    void *uc = ws.p, *g_cond = ws.p + bytes;
     const unsigned g = (unsigned)((n + kBlock - 1) / kBlock);
     e = hipMemcpyAsync(uc, r.in, bytes, hipMemcpyDeviceToDevice, r.stream);
-    if (e == hipSuccess) {   // (stage 3 of the update kernel is the clamp)
-        if (f32)
-            hipLaunchKernelGGL(rainshaft_stage_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, 3, n, ld, h.nmom, (float *)nullptr,
-                               (float *)uc, (const float *)nullptr, 0.0);
-        else
-            hipLaunchKernelGGL(rainshaft_stage_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, 3, n, ld, h.nmom, (double *)nullptr,
-                               (double *)uc, (const double *)nullptr, 0.0);
-        e = hipGetLastError();
-    }
-    int rc = CLOUDY_OK;
-    if (e == hipSuccess) {
-        LaunchReq ce(OP_COND, n, ld, uc, g_cond, r.stream);
-        ce.coef = r.coef;
-        ce.s_scalar = r.s_scalar;
-        ce.s_dev = r.s_dev;
-        rc = launch(plan, ce);
-        LaunchReq rhs = r;
-        rhs.op = OP_RAINSHAFT_RHS;
-        if (rc == CLOUDY_OK) rc = launch(plan, rhs);
-        if (rc == CLOUDY_OK) {
-            if (f32)
-                hipLaunchKernelGGL(rainshaft_add_kernel<float>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, h.nmom, (float *)r.out,
-                                   (const float *)g_cond);
-            else
-                hipLaunchKernelGGL(rainshaft_add_kernel<double>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, h.nmom, (double *)r.out,
-                                   (const double *)g_cond);
-            e = hipGetLastError();
-        }
-    }
-    (void)hipFree(ws);   // (waits for the launches)
-    if (rc != CLOUDY_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "unfused column right-hand side with condensation");
+    if (e == hipSuccess)   // (stage 3 of the update kernel is the clamp)
+        e = with_plane_type(h, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(rainshaft_stage_kernel<T>, dim3(g), dim3(kBlock), 0, r.stream, 3, n, ld, h.nmom, (T *)nullptr, (T *)uc,
+                               (const T *)nullptr, 0.0);
+        });
+    if (e != hipSuccess) return fail_hip(e, kWhat);
+    LaunchReq ce(OP_COND, n, ld, uc, g_cond, r.stream);
+    ce.coef = r.coef;
+    ce.s_scalar = r.s_scalar;
+    ce.s_dev = r.s_dev;
+    if (int rc = launch(plan, ce)) return rc;
+    LaunchReq rhs = r;
+    rhs.op = OP_RAINSHAFT_RHS;
+    if (int rc = launch(plan, rhs)) return rc;
+    e = with_plane_type(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(rainshaft_add_kernel<T>, dim3(g), dim3(kBlock), 0, r.stream, n, ld, h.nmom, (T *)r.out, (const T *)g_cond);
+    });
+    if (e != hipSuccess) return fail_hip(e, kWhat);
     return CLOUDY_OK;
 }
 
@@ -588,11 +641,10 @@ void cloudy_plan_desc_init(cloudy_plan_desc *d) {
 
 namespace {
 
-// Host half of cloudy_plan_create: validation and every derived constant (no device involved).  On success *out owns
-// a plan without device resources and `nodes` holds the Simpson node tables.
-int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<double> &nodes) {
-    if (!d || !out) return fail(CLOUDY_EINVAL, "desc/out is NULL");
-    *out = nullptr;
+// Host half of cloudy_plan_create: validation and every derived constant (no device involved).  On success `out` owns
+// a plan without device resources and `nodes` holds the Simpson node tables; a refusal leaves `out` empty.
+int build_host_plan(const cloudy_plan_desc *d, PlanHandle &out, std::vector<double> &nodes) {
+    if (!d) return fail(CLOUDY_EINVAL, "desc/out is NULL");
     if (d->struct_size != sizeof(cloudy_plan_desc))
         return fail(CLOUDY_EINVAL, "struct_size %u != %zu (call cloudy_plan_desc_init)", d->struct_size,
                     sizeof(cloudy_plan_desc));
@@ -627,7 +679,7 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
     if (!(d->k_range[0] > 0) || !(d->k_range[1] >= d->k_range[0])) return fail(CLOUDY_EINVAL, "bad k_range");
     if (d->n_vel < 0 || d->n_vel > CLOUDY_MAX_VEL) return fail(CLOUDY_EUNSUPPORTED, "n_vel outside 0..%d", CLOUDY_MAX_VEL);
 
-    cloudy_plan *p = new (std::nothrow) cloudy_plan();
+    PlanHandle p(new (std::nothrow) cloudy_plan());
     if (!p) return fail(CLOUDY_ENOMEM, "out of host memory");
     HostPlan &h = p->h;
     h.N = N;
@@ -646,10 +698,8 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
             h.np[i] = 2;
         else if (d->dist_type[i] == CLOUDY_DIST_GAMMA || d->dist_type[i] == CLOUDY_DIST_LOGNORMAL)
             h.np[i] = 3;
-        else {
-            delete p;
+        else
             return fail(CLOUDY_EINVAL, "dist_type[%d] = %d is not a closure family", i, d->dist_type[i]);
-        }
         h.dist_type[i] = d->dist_type[i];
         h.off[i] = off;
         off += h.np[i];
@@ -660,6 +710,14 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
         h.mom_norm[i][2] = d->norms[0] * (d->norms[1] * d->norms[1]);
     }
     h.nmom = off;
+    // sedimentation velocity, rescaled as the rainshaft caller does (rainshaft_helpers.jl:74-76)
+    h.n_vel = d->n_vel;
+    for (int v = 0; v < d->n_vel; ++v) {
+        h.vel[v][0] = d->vel[v][0];
+        h.vel[v][1] = d->vel[v][1];
+        h.vel_n[v][0] = d->vel[v][0] * std::pow(d->norms[1], d->vel[v][1]);
+        h.vel_n[v][1] = d->vel[v][1];
+    }
 
     if (numerical) {
         // get_normalized_kernel_func, KernelFunctions.jl:124-154
@@ -678,10 +736,7 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
             h.q.kf[2] = kp[2] * n0 * m0;
         }
         for (int k = 0; k < 3; ++k)
-            if (std::isnan(h.q.kf[k])) {
-                delete p;
-                return fail(CLOUDY_EINVAL, "kernel_func_params[%d] is NaN", k);
-            }
+            if (std::isnan(h.q.kf[k])) return fail(CLOUDY_EINVAL, "kernel_func_params[%d] is NaN", k);
         const int quad_order = d->quad_order ? d->quad_order : (d->quad_mode == CLOUDY_QUAD_CONVERGED ? 8 : 10);
         if (d->quad_mode == CLOUDY_QUAD_CONVERGED) {
             // quad_conv.hpp: quad_order Gauss-Legendre points per panel of the inner rule of a Lognormal mode's T_m (the
@@ -695,10 +750,8 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
         } else {
             // start-value table of the per-parcel Gauss-Laguerre rules over k in (0, max(k_range[1], 1)] (Exponential: k = 1)
             std::string msg;
-            if (!quad_host::build_table(quad_order, std::fmax(d->k_range[1], 1.0), h.q, h.qtab, msg)) {
-                delete p;
+            if (!quad_host::build_table(quad_order, std::fmax(d->k_range[1], 1.0), h.q, h.qtab, msg))
                 return fail(CLOUDY_EUNSUPPORTED, "%s", msg.c_str());
-            }
             h.q.mode = QUAD_FIXED;
         }
         h.n_mom_max = np_max;
@@ -707,17 +760,10 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
             h.thr[i] = INFINITY;
         }
         h.mode = MODE_ALLINF;
-        h.n_vel = d->n_vel;
-        for (int v = 0; v < d->n_vel; ++v) {
-            h.vel[v][0] = d->vel[v][0];
-            h.vel[v][1] = d->vel[v][1];
-            h.vel_n[v][0] = d->vel[v][0] * std::pow(d->norms[1], d->vel[v][1]);
-            h.vel_n[v][1] = d->vel[v][1];
-        }
         nodes.clear();
         h.jit_conv_bs = jit_conv_block_size_resolve(h);
         h.jit_conv_rounds = jit_conv_rounds_resolve(h);
-        *out = p;
+        out = std::move(p);
         return CLOUDY_OK;
     }
     // kernels: check_symmetry (KernelTensors.jl:157-171) + get_normalized_kernel_tensor (:189-199)
@@ -727,10 +773,7 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
                 d->kernel_layout == CLOUDY_KERNEL_MATRIX ? d->kernel_c + (size_t)(j * N + k) * P * P : d->kernel_c;
             for (int a = 0; a < P; ++a)
                 for (int b = a + 1; b < P; ++b)
-                    if (c[a * P + b] != c[b * P + a]) {
-                        delete p;
-                        return fail(CLOUDY_ENOTSYMMETRIC, "array not symmetric.");
-                    }
+                    if (c[a * P + b] != c[b * P + a]) return fail(CLOUDY_ENOTSYMMETRIC, "array not symmetric.");
             for (int a = 0; a < P; ++a)
                 for (int b = 0; b < P; ++b)
                     h.c[j][k][a][b] = d->kernel_is_normalized
@@ -746,10 +789,7 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
         h.thr[i] = (d->threshold_style == CLOUDY_FIXED_THRESHOLD && !d->thresholds_are_normalized)
                        ? d->dist_thresholds[i] / d->norms[1]
                        : d->dist_thresholds[i];
-        if (std::isnan(h.thr[i])) {
-            delete p;
-            return fail(CLOUDY_EINVAL, "dist_thresholds[%d] is NaN", i);
-        }
+        if (std::isnan(h.thr[i])) return fail(CLOUDY_EINVAL, "dist_thresholds[%d] is NaN", i);
     }
 
     // Simpson node tables for FixedThreshold (ParticleDistributions.jl:604-610): the grid depends only on
@@ -760,10 +800,7 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
         for (int i = 0; i < N - 1; ++i) {
             const double xt = h.thr[i];
             if (std::isinf(xt) && xt > 0) continue;
-            if (!(xt > 0)) {
-                delete p;
-                return fail(CLOUDY_EINVAL, "dist_thresholds[%d] must be positive or +Inf", i);
-            }
+            if (!(xt > 0)) return fail(CLOUDY_EINVAL, "dist_thresholds[%d] must be positive or +Inf", i);
             if (h.dist_type[i] == CLOUDY_DIST_MONODISPERSE ||  // analytic, no Simpson grid (:557-564)
                 h.dist_type[i] == CLOUDY_DIST_LOGNORMAL) {      // :614-625 by msh_lognormal's own rule (kernels.hpp)
                 h.finite[i] = 1;
@@ -772,10 +809,7 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
             }
             const double x_lb = std::fmin(1e-5, 1e-5 * xt);
             const int n_bins = (int)std::floor(h.nbpl * std::log10(xt / x_lb));
-            if (n_bins < 3) {
-                delete p;
-                return fail(CLOUDY_EINVAL, "n_bins must be at least 3");  // ParticleDistributions.jl:699
-            }
+            if (n_bins < 3) return fail(CLOUDY_EINVAL, "n_bins must be at least 3");  // ParticleDistributions.jl:699
             const double x_min = std::log(x_lb);
             const double dx = (std::log(xt) - std::log(x_lb)) / n_bins;
             h.finite[i] = 1;
@@ -796,17 +830,10 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
     } else {
         h.mode = (N > 1) ? MODE_MOVING : MODE_ALLINF;
         for (int i = 0; i < N - 1; ++i) {
-            if (!(h.thr[i] >= 0.0 && h.thr[i] <= 1.0)) {
-                delete p;
-                return fail(CLOUDY_EINVAL, "MovingThreshold percentile %d outside [0, 1]", i);
-            }
-            if (h.dist_type[i] != CLOUDY_DIST_EXPONENTIAL && h.dist_type[i] != CLOUDY_DIST_GAMMA) {
-                // compute_threshold has methods for Exponential and Gamma only (:747-761)
-                // (round 6, found by the host sanitizer build: the message used to read h.dist_type[i] AFTER `delete p`)
-                const int dti = h.dist_type[i];
-                delete p;
-                return fail(CLOUDY_EINVAL, "no method compute_threshold for dist_type[%d] = %d", i, dti);
-            }
+            if (!(h.thr[i] >= 0.0 && h.thr[i] <= 1.0)) return fail(CLOUDY_EINVAL, "MovingThreshold percentile %d outside [0, 1]", i);
+            // compute_threshold has methods for Exponential and Gamma only (:747-761)
+            if (h.dist_type[i] != CLOUDY_DIST_EXPONENTIAL && h.dist_type[i] != CLOUDY_DIST_GAMMA)
+                return fail(CLOUDY_EINVAL, "no method compute_threshold for dist_type[%d] = %d", i, h.dist_type[i]);
         }
         // start values of the per-parcel inversion gamma_inc_inv(k, p_i, 1 - p_i) (:760): ln x as a polynomial in ln k
         // over k in [0.03, kmax], one per Gamma mode; kept only if every fit is good to 1e-3 (two Halley steps then
@@ -823,17 +850,9 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
         h.inv_klo = k_lo;
     }
 
-    // sedimentation velocity, rescaled as the rainshaft caller does (rainshaft_helpers.jl:74-76)
-    h.n_vel = d->n_vel;
-    for (int v = 0; v < d->n_vel; ++v) {
-        h.vel[v][0] = d->vel[v][0];
-        h.vel[v][1] = d->vel[v][1];
-        h.vel_n[v][0] = d->vel[v][0] * std::pow(d->norms[1], d->vel[v][1]);
-        h.vel_n[v][1] = d->vel[v][1];
-    }
     h.n_nodes = (int)(nodes.size() / kNodeStride);
     h.jit_sorted_bs = jit_sorted_block_size_resolve(h);
-    *out = p;
+    out = std::move(p);
     return CLOUDY_OK;
 }
 
@@ -842,9 +861,9 @@ int build_host_plan(const cloudy_plan_desc *d, cloudy_plan **out, std::vector<do
 extern "C" {
 
 int cloudy_plan_create(const cloudy_plan_desc *d, cloudy_plan **out) {
-    cloudy_plan *p = nullptr;
+    PlanHandle p;   // (destroyed, with the device resources it has by then, on every return but the last)
     std::vector<double> nodes;
-    int rc0 = build_host_plan(d, &p, nodes);
+    int rc0 = build_host_plan(d, p, nodes);
     if (out) *out = nullptr;
     if (rc0 != CLOUDY_OK) return rc0;
     HostPlan &h = p->h;
@@ -852,57 +871,31 @@ int cloudy_plan_create(const cloudy_plan_desc *d, cloudy_plan **out) {
     // device-side constants
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1) {
-        delete p;
+    if (e != hipSuccess || ndev < 1)
         return fail(CLOUDY_ENODEVICE, "no HIP device: %s", e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
-    }
     if (d->device >= 0) {
-        if (d->device >= ndev) {
-            delete p;
-            return fail(CLOUDY_EINVAL, "device %d out of range (%d devices)", d->device, ndev);
-        }
+        if (d->device >= ndev) return fail(CLOUDY_EINVAL, "device %d out of range (%d devices)", d->device, ndev);
         h.device = d->device;
     } else {
         (void)hipGetDevice(&h.device);
     }
     DeviceGuard guard(h.device);  // the caller's current device is restored on every return path
-    if (guard.err != hipSuccess) {
-        delete p;
-        return fail_hip(guard.err, "hipSetDevice");
-    }
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
     {
         const char *e = std::getenv("CLOUDY_HIP_PPL1");
         h.force_ppl1 = (e && e[0] == '1') ? 1 : 0;
     }
-    if (h.n_nodes > 0) {
-        e = hipMalloc((void **)&h.nodes_dev, nodes.size() * sizeof(double));
-        if (e == hipSuccess)
-            e = hipMemcpy(h.nodes_dev, nodes.data(), nodes.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            cloudy_plan_destroy(p);
-            return fail_hip(e, "node table upload");
-        }
-    }
-    if (!h.qtab.empty()) {
-        e = hipMalloc((void **)&h.qtab_dev, h.qtab.size() * sizeof(double));
-        if (e == hipSuccess)
-            e = hipMemcpy(h.qtab_dev, h.qtab.data(), h.qtab.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            cloudy_plan_destroy(p);
-            return fail_hip(e, "rule table upload");
-        }
-    }
+    const auto upload = [](double *&dev, const std::vector<double> &host) {
+        const hipError_t e = hipMalloc((void **)&dev, host.size() * sizeof(double));
+        return e != hipSuccess ? e : hipMemcpy(dev, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+    };
+    if (h.n_nodes > 0 && (e = upload(h.nodes_dev, nodes)) != hipSuccess) return fail_hip(e, "node table upload");
+    if (!h.qtab.empty() && (e = upload(h.qtab_dev, h.qtab)) != hipSuccess) return fail_hip(e, "rule table upload");
     e = hipMalloc((void **)&h.partial_dev, sizeof(double) * kSumBlocks * (CLOUDY_MAX_MOMENTS + 64));
-    if (e != hipSuccess) {
-        cloudy_plan_destroy(p);
-        return fail_hip(e, "workspace allocation");
-    }
+    if (e != hipSuccess) return fail_hip(e, "workspace allocation");
     if (!plan_beyond_aot(h)) {  // (the kernels compiled for the plan carry its constants as literals)
         e = dispatch(h, LaunchReq(OP_PREPARE, 0, 0, nullptr, &h.kargs_dev, nullptr));
-        if (e != hipSuccess) {
-            cloudy_plan_destroy(p);
-            return fail_hip(e, "constant block upload");
-        }
+        if (e != hipSuccess) return fail_hip(e, "constant block upload");
     }
     // plan-time specialisation (jit.hpp): 0 = when available, 1 = required, -1 = off
     const char *env = std::getenv("CLOUDY_HIP_JIT");
@@ -913,14 +906,12 @@ int cloudy_plan_create(const cloudy_plan_desc *d, cloudy_plan **out) {
         else m.log = "switched off (desc.specialize < 0 or CLOUDY_HIP_JIT=0)";
     });
     p->jit_on = m.ok;
-    if (!p->jit_on && (d->specialize > 0 || plan_beyond_aot(h))) {
-        const int rc = on ? fail(CLOUDY_EUNSUPPORTED, "plan-time specialisation failed: %.400s", m.log.c_str())
-                          : fail(CLOUDY_EUNSUPPORTED, "plans of more than %d modes or order > %d need plan-time compilation, which is %s",
-                                 CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, m.log.c_str());
-        cloudy_plan_destroy(p);
-        return rc;
-    }
-    *out = p;
+    if (!p->jit_on && (d->specialize > 0 || plan_beyond_aot(h)))
+        return on ? fail(CLOUDY_EUNSUPPORTED, "plan-time specialisation failed: %.400s", m.log.c_str())
+                  : fail(CLOUDY_EUNSUPPORTED, "plans of more than %d modes or order > %d need plan-time compilation, which is %s",
+                         CLOUDY_AOT_MAX_MODES, CLOUDY_AOT_MAX_P - 1, m.log.c_str());
+    if (!out) return fail(CLOUDY_EINVAL, "desc/out is NULL");
+    *out = p.release();
     return CLOUDY_OK;
 }
 
@@ -932,9 +923,9 @@ int cloudy_plan_specialized(const cloudy_plan *plan) {
 const char *cloudy_plan_jit_log(const cloudy_plan *plan) { return plan ? plan->jit[JIT_MAIN].log.c_str() : "plan is NULL"; }
 
 int cloudy_jit_selfcheck(const cloudy_plan_desc *d, const char *arch) {
-    cloudy_plan *p = nullptr;
+    PlanHandle p;
     std::vector<double> nodes;
-    int rc = build_host_plan(d, &p, nodes);
+    int rc = build_host_plan(d, p, nodes);
     if (rc != CLOUDY_OK) return rc;
     // the units the runtime could request for the plan, with their compile options.  "source-only" (tests/test_host_sanitizers.py:
     // the string assembly of an N = 8 / P = 8 plan without the minutes of hiprtc its kernels take) compiles nothing.  Either way
@@ -969,7 +960,6 @@ int cloudy_jit_selfcheck(const cloudy_plan_desc *d, const char *arch) {
         if (rc == CLOUDY_OK && a != "source-only" && !jit_compile(ud.src, a, ud.licm_off, code, log))
             rc = fail(CLOUDY_EUNSUPPORTED, "plan-time compilation failed: %.440s", log.c_str());
     }
-    delete p;
     return rc;
 }
 
@@ -1074,7 +1064,7 @@ int cloudy_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const voi
                          int n_steps, void *stream) {
     int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
     if (rc) return rc;
-    if (n_steps < 0 || !(dt == dt)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
+    if ((rc = check_steps(n_steps, dt))) return rc;
     LaunchReq r(OP_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
     r.dt = dt;
     r.n_steps = n_steps;
@@ -1085,7 +1075,7 @@ int cloudy_tsit5_steps(const cloudy_plan *plan, size_t n, size_t ld, const void 
                        int n_steps, void *stream) {
     int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
     if (rc) return rc;
-    if (n_steps < 0 || !(dt == dt)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
+    if ((rc = check_steps(n_steps, dt))) return rc;
     if (plan->h.dtype == CLOUDY_F32_FAST)
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_steps serves CLOUDY_F64 and CLOUDY_F32 plans (the fused integrators keep "
                                          "the state in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode)");
@@ -1101,9 +1091,7 @@ int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const
     if (rc) return rc;
     LaunchReq r(OP_BOX_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
     r.sources = sources;
-    // as cloudy_cond_evap: xi_normalized = p.xi / norms[2]^(2/3) (box_model_helpers.jl:65); rho_l = 1000 (Condensation.jl:26)
-    const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
-    r.coef = 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
+    r.coef = cond_coef(plan, xi);
     r.s_scalar = s;
     r.s_dev = s_dev;
     r.dt = dt;
@@ -1156,7 +1144,7 @@ static int parcel_request(const cloudy_plan *plan, size_t n, size_t ld, const vo
     if (sources != SRC_COND && sources != (SRC_COAL | SRC_COND))
         return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COND or CLOUDY_SRC_COAL | CLOUDY_SRC_COND (coalescence alone is "
                                    "not a parcel: cloudy_ssprk33_steps)", sources);
-    if (steps && (n_steps < 0 || !(dt == dt))) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
+    if (steps && (rc = check_steps(n_steps, dt))) return rc;
     if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
     return check_batch(plan, n, ld, in, out);
 }
@@ -1252,20 +1240,19 @@ int cloudy_closure_stats(const cloudy_plan *plan, size_t n, size_t ld, const voi
     // short -- the stores of the kernel not seen by the copy.  The other reductions use plain allocations and never did.
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counter width");
     std::vector<uint64_t> rows(blocks * (size_t)nc);
-    unsigned long long *dev = nullptr;
-    HIP_TRY(hipMalloc((void **)&dev, sizeof(unsigned long long) * rows.size()));
-    if (h.dtype != CLOUDY_F64)
-        hipLaunchKernelGGL(closure_stats_kernel<float>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a, n, ld, (const float *)mom_dev, dev);
-    else
-        hipLaunchKernelGGL(closure_stats_kernel<double>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a, n, ld, (const double *)mom_dev, dev);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(rows.data(), dev, sizeof(uint64_t) * rows.size(), hipMemcpyDeviceToHost, st);
+    DeviceScratch dev;
+    hipError_t e = dev.alloc(sizeof(unsigned long long) * rows.size());
+    if (e != hipSuccess) return fail_hip(e, "hipMalloc((void **)&dev, sizeof(unsigned long long) * rows.size())");
+    e = with_plane_type(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(closure_stats_kernel<T>, dim3((unsigned)blocks), dim3(kBlock), 0, st, a, n, ld, (const T *)mom_dev,
+                           (unsigned long long *)dev.p);
+    });
+    if (e == hipSuccess) e = hipMemcpyAsync(rows.data(), dev.p, sizeof(uint64_t) * rows.size(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dev);
-    if (e == hipSuccess)
-        for (size_t b = 0; b < blocks; ++b)
-            for (int q = 0; q < nc; ++q) counts_host[q] += rows[b * (size_t)nc + q];
     if (e != hipSuccess) return fail_hip(e, "cloudy_closure_stats");
+    for (size_t b = 0; b < blocks; ++b)
+        for (int q = 0; q < nc; ++q) counts_host[q] += rows[b * (size_t)nc + q];
     return CLOUDY_OK;
 }
 
@@ -1293,8 +1280,7 @@ int cloudy_compute_thresholds(const cloudy_plan *plan, size_t n, size_t ld, cons
 int cloudy_sedimentation_flux(const cloudy_plan *plan, size_t n, size_t ld, const void *mom_dev, void *flux_dev,
                               void *stream) {
     int rc = check_batch(plan, n, ld, mom_dev, flux_dev);
-    if (rc) return rc;
-    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
+    if (rc || (rc = check_velocity(plan, false))) return rc;
     return run(plan, LaunchReq(OP_SEDI, n, ld, mom_dev, flux_dev, stream));
 }
 
@@ -1303,9 +1289,7 @@ int cloudy_cond_evap(const cloudy_plan *plan, size_t n, size_t ld, const void *m
     int rc = check_batch(plan, n, ld, mom_dev, dmom_dev);
     if (rc) return rc;
     LaunchReq r(OP_COND, n, ld, mom_dev, dmom_dev, stream);
-    // rhs_condensation!: xi_normalized = p.xi / norms[2]^(2/3) (box_model_helpers.jl:65); rho_l = 1000 (Condensation.jl:26)
-    const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
-    r.coef = 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
+    r.coef = cond_coef(plan, xi);
     r.s_scalar = s;
     r.s_dev = s_dev;
     return run(plan, r);
@@ -1326,9 +1310,7 @@ int cloudy_rainshaft_sources(const cloudy_plan *plan, size_t n, size_t ld, const
     int rc = check_batch(plan, n, ld, mom_dev, coal_source_dev);
     if (rc) return rc;
     if (n > 0 && !sedi_flux_dev) return fail(CLOUDY_EINVAL, "device buffer is NULL");
-    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
-    if (plan->h.threshold_style != CLOUDY_FIXED_THRESHOLD)
-        return fail(CLOUDY_EINVAL, "make_rainshaft_rhs uses FixedThreshold (rainshaft_helpers.jl:70)");
+    if ((rc = check_velocity(plan, true))) return rc;
     // the cell body compiled for the plan writes the sedimentation flux in the same launch (one read of the moments, one closure
     // inversion); the ahead-of-time path is two launches (launch())
     LaunchReq r(OP_COAL, n, ld, mom_dev, coal_source_dev, stream);
@@ -1340,18 +1322,15 @@ int cloudy_rainshaft_sources(const cloudy_plan *plan, size_t n, size_t ld, const
 int cloudy_rainshaft_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *mom_dev, double dz,
                          void *flux_work_dev, void *rhs_dev, void *stream) {
     const size_t n = nz * n_columns;
-    int rc = check_batch(plan, n, ld, mom_dev, rhs_dev);
+    int rc = check_columns(plan, nz, n, ld, mom_dev, rhs_dev, dz);
     if (rc) return rc;
-    if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
     // Round 5: one launch when the plan has the column kernels compiled for it and a workgroup holds a column (nz <= 1024):
     // the RHS_ONLY instance of the column integrator's body -- sources, flux, exchange through LDS, divergence, sum -- writes
     // rhs and the cell fluxes; fp64 planes: the same bits as the two launches of rainshaft_rhs_unfused (test).
     // CLOUDY_HIP_RS_FUSED_RHS=0: off.  (the argument checks come first -- whether a call is valid must not depend on
     // whether the kernels compiled for the plan are on)
     if (!flux_work_dev && n > 0) return fail(CLOUDY_EINVAL, "device buffer is NULL");
-    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
-    if (plan->h.threshold_style != CLOUDY_FIXED_THRESHOLD)
-        return fail(CLOUDY_EINVAL, "make_rainshaft_rhs uses FixedThreshold (rainshaft_helpers.jl:70)");
+    if ((rc = check_velocity(plan, true))) return rc;
     LaunchReq r(OP_RAINSHAFT_RHS, n, ld, mom_dev, rhs_dev, stream);
     r.rainshaft = 1;
     r.out2 = flux_work_dev;
@@ -1363,13 +1342,8 @@ int cloudy_rainshaft_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, s
 int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev,
                                    void *u_out_dev, double dz, double dt, int n_steps, void *stream) {
     const size_t n = nz * n_columns;
-    int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
-    if (rc) return rc;
-    if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
-    if (n_steps < 0 || !(dt == dt)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
-    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
-    if (plan->h.threshold_style != CLOUDY_FIXED_THRESHOLD)
-        return fail(CLOUDY_EINVAL, "make_rainshaft_rhs uses FixedThreshold (rainshaft_helpers.jl:70)");
+    int rc = check_columns(plan, nz, n, ld, u_in_dev, u_out_dev, dz);
+    if (rc || (rc = check_steps(n_steps, dt)) || (rc = check_velocity(plan, true))) return rc;
     if (n == 0) return CLOUDY_OK;
     LaunchReq r(OP_RAINSHAFT_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
     r.rainshaft = 1;
@@ -1380,26 +1354,18 @@ int cloudy_rainshaft_ssprk33_steps(const cloudy_plan *plan, size_t nz, size_t n_
     return run(plan, r);
 }
 
-// the folded coefficient of get_cond_evap, as cloudy_cond_evap forms it: xi_normalized = p.xi / norms[2]^(2/3)
-// (box_model_helpers.jl:65); rho_l = 1000 (Condensation.jl:26)
-static double cond_coef(const cloudy_plan *plan, double xi) {
-    const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
-    return 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
-}
-
 // (a quadrature plan carries no velocity terms: told what it lacks first, not that)
 static const char kNoNumericalColumns[] = "the column body belongs to AnalyticalCoalStyle plans: NumericalCoalStyle plans are not served";
 
 int cloudy_rainshaft_cond_rhs(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *mom_dev,
                               const double *s_dev, double s, double xi, double dz, void *flux_work_dev, void *rhs_dev, void *stream) {
     const size_t n = nz * n_columns;
-    int rc = check_batch(plan, n, ld, mom_dev, rhs_dev);
+    int rc = check_columns(plan, nz, n, ld, mom_dev, rhs_dev, dz);
     if (rc) return rc;
-    if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
     if (!(xi == xi)) return fail(CLOUDY_EINVAL, "xi must not be NaN");
     if (!flux_work_dev && n > 0) return fail(CLOUDY_EINVAL, "device buffer is NULL");
     if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL) return fail(CLOUDY_EUNSUPPORTED, kNoNumericalColumns);
-    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
+    if ((rc = check_velocity(plan, false))) return rc;
     LaunchReq r(OP_RAINSHAFT_COND_RHS, n, ld, mom_dev, rhs_dev, stream);
     r.rainshaft = 1;
     r.out2 = flux_work_dev;
@@ -1415,12 +1381,11 @@ int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size
                                         void *u_out_dev, const double *s_dev, double s, double xi, double dz, double dt, int n_steps,
                                         void *stream) {
     const size_t n = nz * n_columns;
-    int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
+    int rc = check_columns(plan, nz, n, ld, u_in_dev, u_out_dev, dz);
     if (rc) return rc;
-    if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
     if (n_steps < 0 || !(dt == dt) || !(xi == xi)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0, dt and xi not NaN");
     if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL) return fail(CLOUDY_EUNSUPPORTED, kNoNumericalColumns);
-    if (plan->h.n_vel < 1) return fail(CLOUDY_EINVAL, "plan has no terminal-velocity coefficients (n_vel = 0)");
+    if ((rc = check_velocity(plan, false))) return rc;
     // (deliberately no FixedThreshold check here or in cloudy_rainshaft_cond_rhs: cloudy_rainshaft_ssprk33_steps refuses
     // MovingThreshold plans because the reference has no such driver; these entries serve them stage by stage, see the header)
     if (n == 0) return CLOUDY_OK;   // (as cloudy_rainshaft_ssprk33_steps; run() would return here as well, before any unit is loaded)
@@ -1455,12 +1420,12 @@ int cloudy_moment_sums_ws(const cloudy_plan *plan, size_t n, size_t ld, int plan
     if (blocks > (size_t)kSumBlocks) blocks = kSumBlocks;
     if (blocks < 1) blocks = 1;
     double *partial = static_cast<double *>(workspace_dev);
-    if (plan->h.dtype != CLOUDY_F64)
-        hipLaunchKernelGGL(plane_partial_sums_kernel<float>, dim3((unsigned)blocks), dim3(kBlock), 0,
-                           (hipStream_t)stream, n, ld, planes, (const float *)arr_dev, partial);
-    else
-        hipLaunchKernelGGL(plane_partial_sums_kernel<double>, dim3((unsigned)blocks), dim3(kBlock), 0,
-                           (hipStream_t)stream, n, ld, planes, (const double *)arr_dev, partial);
+    const hipError_t e = with_plane_type(plan->h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(plane_partial_sums_kernel<T>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, n, ld, planes,
+                           (const T *)arr_dev, partial);
+    });
+    if (e != hipSuccess) return fail_hip(e, "hipGetLastError()");
     hipLaunchKernelGGL(plane_final_sums_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, (int)blocks, planes,
                        (const double *)partial, sums_dev);
     HIP_TRY(hipGetLastError());
@@ -1479,37 +1444,35 @@ int cloudy_coal_rhs_host(const cloudy_plan *plan, size_t n, size_t ld, const voi
     int rc = check_batch(plan, n, ld, mom_host, dmom_host);
     if (rc) return rc;
     if (n == 0) return CLOUDY_OK;
-    const size_t bytes = (size_t)plan->h.nmom * ld * (plan->h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double));
+    const size_t bytes = (size_t)plan->h.nmom * ld * plane_bytes(plan->h);
     DeviceGuard guard(plan->h.device);
     if (guard.err != hipSuccess) return fail_hip(guard.err, "selecting the plan's device");
-    char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, 2 * bytes));
-    hipError_t e = hipMemcpy(buf, mom_host, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = cloudy_coal_rhs(plan, n, ld, buf, buf + bytes, nullptr);
-        if (rc == CLOUDY_OK) e = hipMemcpy(dmom_host, buf + bytes, bytes, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(buf);
+    DeviceScratch buf;
+    hipError_t e = buf.alloc(2 * bytes);
+    if (e != hipSuccess) return fail_hip(e, "hipMalloc((void **)&buf, 2 * bytes)");
+    e = hipMemcpy(buf.p, mom_host, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail_hip(e, "host staging copy");
-    return rc;
+    if ((rc = cloudy_coal_rhs(plan, n, ld, buf.p, buf.p + bytes, nullptr))) return rc;
+    e = hipMemcpy(dmom_host, buf.p + bytes, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, "host staging copy");
+    return CLOUDY_OK;
 }
 
 int cloudy_time_coal_rhs(const cloudy_plan *plan, size_t n, size_t ld, const void *mom_dev, void *dmom_dev,
                          void *stream, int iters, float *ms_per_launch) {
     if (iters < 1 || !ms_per_launch) return fail(CLOUDY_EINVAL, "iters must be >= 1 and ms_per_launch non-NULL");
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    hipError_t he = e0.create();
+    if (he != hipSuccess) return fail_hip(he, "hipEventCreate(&e0)");
+    if ((he = e1.create()) != hipSuccess) return fail_hip(he, "hipEventCreate(&e1)");
     int rc = CLOUDY_OK;
-    hipError_t he = hipEventRecord(e0, (hipStream_t)stream);
+    he = hipEventRecord(e0.ev, (hipStream_t)stream);
     for (int i = 0; i < iters && rc == CLOUDY_OK && he == hipSuccess; ++i)
         rc = cloudy_coal_rhs(plan, n, ld, mom_dev, dmom_dev, stream);
-    if (he == hipSuccess) he = hipEventRecord(e1, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    if (he == hipSuccess) he = hipEventRecord(e1.ev, (hipStream_t)stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1.ev);
     float ms = 0.f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0.ev, e1.ev);
     if (rc != CLOUDY_OK) return rc;
     if (he != hipSuccess) return fail_hip(he, "event timing");
     *ms_per_launch = ms / (float)iters;
@@ -1518,29 +1481,27 @@ int cloudy_time_coal_rhs(const cloudy_plan *plan, size_t n, size_t ld, const voi
 
 int cloudy_timer_begin(void *stream, void **timer_out) {
     if (!timer_out) return fail(CLOUDY_EINVAL, "timer_out is NULL");
-    hipEvent_t *ev = new (std::nothrow) hipEvent_t[2];
-    if (!ev) return fail(CLOUDY_ENOMEM, "out of host memory");
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], (hipStream_t)stream);
-    if (e != hipSuccess) {
-        delete[] ev;
-        return fail_hip(e, "cloudy_timer_begin");
-    }
-    *timer_out = ev;
+    std::unique_ptr<hipEvent_t[]> pair(new (std::nothrow) hipEvent_t[2]);   // the opaque timer: the two events
+    if (!pair) return fail(CLOUDY_ENOMEM, "out of host memory");
+    Event e0, e1;
+    hipError_t e = e0.create();
+    if (e == hipSuccess) e = e1.create();
+    if (e == hipSuccess) e = hipEventRecord(e0.ev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "cloudy_timer_begin");
+    pair[0] = e0.release();
+    pair[1] = e1.release();
+    *timer_out = pair.release();
     return CLOUDY_OK;
 }
 
 int cloudy_timer_end(void *timer, void *stream, float *ms_total) {
     if (!timer || !ms_total) return fail(CLOUDY_EINVAL, "timer / ms_total is NULL");
-    hipEvent_t *ev = static_cast<hipEvent_t *>(timer);
-    hipError_t e = hipEventRecord(ev[1], (hipStream_t)stream);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+    std::unique_ptr<hipEvent_t[]> pair(static_cast<hipEvent_t *>(timer));   // (the timer ends here, whatever the events answer)
+    Event e0(pair[0]), e1(pair[1]);
+    hipError_t e = hipEventRecord(e1.ev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipEventSynchronize(e1.ev);
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-    delete[] ev;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0.ev, e1.ev);
     if (e != hipSuccess) return fail_hip(e, "cloudy_timer_end");
     *ms_total = ms;
     return CLOUDY_OK;

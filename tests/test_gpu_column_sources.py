@@ -516,3 +516,63 @@ def test_the_256_thread_units_with_a_partly_filled_second_workgroup(gpu_cloudy, 
     err = np.abs(fused[:, :n] - (base + cond)) / np.maximum(np.abs(base) + np.abs(cond), 1e-300)
     print(f"256-thread column unit with condensation, {case}: max |fused - (rhs + cond)| / (|rhs| + |cond|) = {err.max():.2e}")
     assert err.max() <= 1e-13
+
+
+# max |f32 plan - fp64 host sequence| of the two comparisons below, measured on the parent commit's library, and 4 x that
+FLOAT_TALL_MEASURED = {"steps": 1.027e-07, "rhs": 8.817e-08}
+FLOAT_TALL_BOUND = {"steps": 4.108e-07, "rhs": 3.527e-07}
+
+
+def test_float_planes_step_a_tall_column_stage_by_stage(gpu_cloudy, oracle):
+    """CLOUDY_F32 planes on the stage-by-stage forms inside the library: one column of 1500 cells, taller than a workgroup, so
+    that cloudy_rainshaft_cond_ssprk33_steps runs its clamp, update and add launches and cloudy_rainshaft_cond_rhs its clamp and
+    add launches on float planes.  Two steps against the host-driven sequence of (3) on an fp64 plan, evaluated on the
+    float-rounded input, as max |diff| / max|plane|; then one evaluation of the right-hand side on the float state the steps end
+    in against the fp64 column right-hand side + cloudy_cond_evap, per plane of max (|coal| + |divergence| + |cond|) as in (4).
+    Bounds: 4 x the figure the parent commit's library gives on this case on an MI355X (three runs, the same figure each time):
+    steps 1.027e-07 measured, 4.108e-07 allowed; right-hand side 8.817e-08 measured, 3.527e-07 allowed (FLOAT_TALL_MEASURED,
+    FLOAT_TALL_BOUND above).  The source moves the state by 6.8e-05 of the plane maxima, 165 x what the comparison allows."""
+    cloudy = gpu_cloudy
+    L = cloudy.lib()
+    par, dist_types, u0, _ = _tall(cloudy, oracle, 1500)
+    nz, nm = par.nz, u0.shape[0]
+    u32 = np.ascontiguousarray(u0[:, :nz].astype(np.float32))
+    s = supersaturation(nz, par.dz, 1)
+    s_dev = dev(cloudy, s[None, :])
+    p64, p32 = par.coal_data.plan(dist_types, vel=VEL), par.coal_data.plan(dist_types, vel=VEL, dtype=1)
+    want = host_sequence(cloudy, par, p64, u32.astype(np.float64), s, 2, par.dt)
+    assert np.isfinite(want).all()
+    ref = np.abs(want).max(axis=1, keepdims=True) + 1e-300
+    res = {}
+    ud = dev(cloudy, u32)
+    for tag, s_ptr in (("source", s_dev.ptr), ("plain", None)):
+        out = cloudy.DeviceArray.zeros(nm, nz, np.float32)
+        cloudy._lib.check(L.cloudy_rainshaft_cond_ssprk33_steps(p32.handle, nz, 1, nz, ud.ptr, out.ptr, s_ptr, 0.0, XI, par.dz, par.dt, 2,
+                                                                None))
+        res[tag] = out.to_numpy()
+    got = res["source"].astype(np.float64)
+    assert np.isfinite(got).all() and got.min() >= 0.0
+    err = (np.abs(got - want) / ref).max()
+    moved = (np.abs(res["plain"].astype(np.float64) - got) / ref).max()
+    print(f"float planes, nz = {nz} stage by stage: max |f32 - fp64 host sequence| / max|plane| = {err:.3e}; the source moves the "
+          f"state by {moved:.3e}")
+    assert err <= FLOAT_TALL_BOUND["steps"]
+    assert moved > 10.0 * FLOAT_TALL_BOUND["steps"]   # the source acted, visibly beyond what the comparison allows
+    # one evaluation of the right-hand side on that float state
+    x32 = res["source"]
+    x = x32.astype(np.float64)
+    m64 = dev(cloudy, x)
+    coal, div = rhs_parts(cloudy, par, p64, x, m64)
+    base = cloudy.make_rainshaft_rhs()(m64, par, 0.0).to_numpy()
+    cond = cloudy.DeviceArray.zeros(nm, nz)
+    cloudy.rhs_condensation(p64, cond, m64, XI, s_dev)
+    cond = cond.to_numpy()
+    m32 = dev(cloudy, x32)
+    g, work = cloudy.DeviceArray.zeros(nm, nz, np.float32), cloudy.DeviceArray.zeros(nm, nz, np.float32)
+    cloudy._lib.check(L.cloudy_rainshaft_cond_rhs(p32.handle, nz, 1, nz, m32.ptr, s_dev.ptr, 0.0, XI, par.dz, work.ptr, g.ptr, None))
+    g = g.to_numpy().astype(np.float64)
+    assert np.isfinite(g).all() and np.abs(cond).max() > 0.0 and np.array_equal(m32.to_numpy(), x32)
+    scale = (np.abs(coal) + np.abs(div) + np.abs(cond)).max(axis=1, keepdims=True)
+    err = (np.abs(g - (base + cond)) / np.maximum(scale, 1e-300)).max()
+    print(f"float planes, nz = {nz} unfused right-hand side: max |f32 - (rhs + cond) fp64| / plane scale = {err:.3e}")
+    assert err <= FLOAT_TALL_BOUND["rhs"]

@@ -544,6 +544,43 @@ def test_shapes_ragged_sizes_and_padding(gpu_cloudy, oracle):
     assert np.array_equal(host_out, out[:, :n])
 
 
+# max |sum - fsum| / sum|x| of the test below with the parent commit's library on an MI355X, and 4 x that: the 300 float values of
+# a plane add up without a rounding in fp64, whatever the order (the kernel's order is fixed: no atomics)
+FLOAT_SUMS_MEASURED, FLOAT_SUMS_BOUND = 0.0, 0.0
+
+
+def test_float_planes_moment_sums_and_host_staging_with_padding(gpu_cloudy):
+    """cloudy_moment_sums and cloudy_coal_rhs_host on a CLOUDY_F32 plan, n = 300 in ld = 320 (a partly filled second workgroup,
+    padding of 1e30 that no sum may read).  The sums against math.fsum of the float values (exact), relative to sum |x| of the
+    plane: measured 0.000e+00 with the parent commit's library (FLOAT_SUMS_MEASURED), bound 4 x that = 0 (FLOAT_SUMS_BOUND): the
+    exact sums.  The host-staging entry against cloudy_coal_rhs on the same planes, bit for bit as the fp64 case of
+    test_shapes_ragged_sizes_and_padding (measured with the parent commit's library: 0 values differ)."""
+    cloudy = gpu_cloudy
+    L = cloudy.lib()
+    n, ld = 300, 320
+    wl = bench.make_workload("cfg3a", n, seed=5)
+    plan = wl["coal_data"].plan(wl["dist_types"], dtype=1)
+    buf = np.full((6, ld), 1e30, np.float32)
+    buf[:, :n] = wl["mom"].astype(np.float32)
+    m = cloudy.DeviceArray.from_numpy(buf)
+    sums = cloudy.DeviceArray.zeros(6, 1)
+    cloudy._lib.check(L.cloudy_moment_sums(plan.handle, n, ld, 6, m.ptr, sums.ptr, None))
+    x = buf[:, :n].astype(np.float64)
+    want = np.array([math.fsum(row) for row in x])
+    err = (np.abs(sums.to_numpy().reshape(-1) - want) / np.abs(x).sum(axis=1)).max()
+    print(f"float planes, moment sums of {n} in ld {ld}: max |sum - fsum| / sum|x| = {err:.3e}")
+    assert err <= FLOAT_SUMS_BOUND
+    dm = cloudy.DeviceArray.from_numpy(np.full((6, ld), -3.0, np.float32))
+    cloudy._lib.check(L.cloudy_coal_rhs(plan.handle, n, ld, m.ptr, dm.ptr, None))
+    want_rhs = dm.to_numpy()
+    assert np.all(want_rhs[:, n:] == -3.0) and np.nanmax(np.abs(want_rhs[:, :n])) > 0.0
+    host_out = np.full((6, ld), -3.0, np.float32)
+    assert L.cloudy_coal_rhs_host(plan.handle, n, ld, buf.ctypes.data, host_out.ctypes.data) == 0
+    differ = int((~((host_out[:, :n] == want_rhs[:, :n]) | (np.isnan(host_out[:, :n]) & np.isnan(want_rhs[:, :n])))).sum())
+    print(f"float planes, cloudy_coal_rhs_host of {n} in ld {ld}: {differ} values differ from cloudy_coal_rhs")
+    assert differ == 0
+
+
 def test_error_behaviour_on_device(gpu_cloudy):
     cloudy = gpu_cloudy
     wl = bench.make_workload("cfg3a", 8)
