@@ -58,6 +58,12 @@ class ParcelParamsC(C.Structure):
         "R_d", "R_v", "cp_d", "cp_v", "cp_l", "LH_v0", "T_0", "press_triple", "T_triple", "grav", "K_therm", "D_vapor", "rho_l")]
 
 
+class AdaptiveOptsC(C.Structure):
+    """cloudy_adaptive_opts"""
+    _fields_ = [("struct_size", C.c_uint32), ("reltol", C.c_double), ("abstol", C.c_double), ("dt_init", C.c_double),
+                ("max_steps", C.c_int32)]
+
+
 # every symbol include/cloudy_hip.h declares: (restype, argtypes)
 _vp, _sz, _i, _dp = C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)
 SYMBOLS = {
@@ -78,6 +84,8 @@ SYMBOLS = {
     "cloudy_get_coal_ints": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "cloudy_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, _i, _vp]),
     "cloudy_tsit5_steps": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, _i, _vp]),
+    "cloudy_adaptive_opts_init": (None, [C.POINTER(AdaptiveOptsC)]),
+    "cloudy_tsit5_adaptive": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp]),
     "cloudy_box_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, _i, _vp]),
     "cloudy_parcel_params_init": (None, [C.POINTER(ParcelParamsC)]),
     "cloudy_parcel_rhs": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(ParcelParamsC), _i, _vp, _vp]),

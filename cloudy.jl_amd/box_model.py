@@ -114,6 +114,56 @@ def solve_tsit5(par, u, dt, n_steps, out=None, stream=None, coal_type=None):
     return o
 
 
+ADAPTIVE_STATUS = ("reached t_span", "max_steps attempts", "dt below 1e-14 t_span or not finite")
+
+
+def solve_tsit5_adaptive(par, u, t_span, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000, out=None, dt_dev=None, info=False,
+                         stream=None, coal_type=None):
+    """Every parcel of `u` from t = 0 to t = t_span with adaptive Tsit5 under a step-size controller of its own, on the device
+    (cloudy_tsit5_adaptive): the PI controller, error norm and statuses of include/cloudy_hip.h.  `reltol` is relative, `abstol` in
+    normalised units (mom ./ norms); `dt`: the first step of every parcel (None: Hairer's first guess per parcel); `max_steps`
+    bounds accepted + rejected steps per parcel.  `dt_dev`: an (1, n) fp64 device array, in/out -- the first step per parcel where
+    positive, the next proposed step on return (a host model calling once per model step starts warm).  `u` is advanced in place
+    unless `out` is given.  Returns the state; with info=True returns (accepted, rejected, status, t_reached) as numpy arrays
+    (this synchronises) and raises RuntimeError naming the count and the first index if any status is not 0 -- AFTER the call: `u`
+    (or `out`) and `dt_dev` already hold what every parcel reached, the stopped ones their state at the time they stopped.
+    AnalyticalCoalStyle
+    plans, fp64 or float planes; NumericalCoalStyle plans are refused (solve_tsit5 steps them with a fixed dt)."""
+    import ctypes as C
+
+    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
+        raise ValueError("Invalid coal style!")
+    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
+    uptr, planes, n, ld = as_device(u)
+    o = out if out is not None else u
+    optr, oplanes, on, old = as_device(o)
+    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
+        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    dptr = None
+    if dt_dev is not None:
+        dptr, dplanes, dn, _ = as_device(dt_dev)
+        if dplanes != 1 or dn != n or dtype_code(dt_dev) != 0:
+            raise ValueError("dt_dev must be an (1, n) fp64 device array")
+    L = _lib.lib()
+    opts = _lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
+    t_arr = DeviceArray.zeros(1, n) if info else None
+    i_arr = DeviceArray.zeros(3, ld, dtype=np.int32) if info else None
+    _lib.check(L.cloudy_tsit5_adaptive(plan.handle, n, ld, uptr, optr, float(t_span), C.byref(opts), dptr,
+                                       t_arr.ptr if info else None, i_arr.ptr if info else None, stream))
+    if not info:
+        return o
+    _lib.check(L.cloudy_stream_synchronize(stream))
+    counts = i_arr.to_numpy()[:, :n]
+    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise RuntimeError(f"solve_tsit5_adaptive: {bad.size} of {n} parcels did not reach t_span; the first is parcel {int(bad[0])} "
+                           f"(status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
+    return accepted, rejected, status, t_arr.to_numpy()[0]
+
+
 def solve_box_ssprk33(par, u, dt, n_steps, xi, s, coal=True, cond=True, out=None, stream=None, coal_type=None):
     """solve(ODEProblem(rhs!, u, tspan, par), SSPRK33(), dt = dt) for n_steps fixed steps on the device, with rhs! the sum of
     the selected sources: rhs_coal! (`coal`) and rhs_condensation!(dm, m, par, s) (`cond`; condensation_single_gamma.jl:24-28,

@@ -1,0 +1,249 @@
+// adaptive.hpp -- per-parcel adaptive Tsit5 (cloudy_tsit5_adaptive): every parcel of a batch is its own ODE and carries its own
+// time, step size and error estimate from t = 0 to t = t_span.
+//
+// The fused integrators of kernels.hpp take one dt and one n_steps for the whole batch.  A host model advances 1e6-1e7 boxes whose
+// number concentrations span decades by ONE model time step; collision rates scale with n, so a dt that is safe for the densest box
+// wastes work on nearly every other one.  Here a lane steps its parcel with the 5(4) pair of the Tsit5 tableau (tsit5:: of
+// kernels.hpp, the stage arithmetic of tsit5_advance) under a step-size controller of its own, and reports what happened.
+//
+//   stages     k1 .. k6 as tsit5_advance, u_new from the 5th-order weights a71 .. a76, then k7 = f(u_new): the error estimate needs
+//              it and an accepted step hands it on as the next k1 (FSAL); a rejected step keeps k1.  6 evaluations per attempted
+//              step + 1 at the start.
+//   estimate   err_i = h sum_j bt_j k_j,i with bt = b - b^ (the embedded 4th-order weights), h the step tried;
+//              sc_i = abstol_i + reltol max(|u_i|, |u_new,i|);  EEst = sqrt(mean_i (err_i / sc_i)^2) over the parcel's prognostic
+//              moments (the padded third slot of a two-moment mode does not count).  abstol is in the plan's NORMALISED units
+//              (mom ./ norms): all-Inf plans keep their state normalised (abstol_i = abstol), thresholded plans keep it physical
+//              (abstol_i = abstol norm_i).
+//   controller a PI controller with these constants (stated here, not taken from a run of any other solver, and no bit identity
+//              with one is claimed): beta1 = 7/50, beta2 = 2/25, gamma = 9/10, qmin = 1/5, qmax = 10, qold_0 = 1e-4;
+//              q11 = EEst^beta1, q = clamp(q11 / qold^beta2 / gamma, 1/qmax, 1/qmin) (EEst = 0: q = 1/qmax).
+//              EEst <= 1: accept -- t += h, dt <- max(h / q, min(dt, dt / q)), qold <- max(EEst, qold_0);
+//              otherwise reject -- dt <- h / min(1/qmin, q11 / gamma); an EEst that is not finite rejects with dt <- h / 5.
+//              The powers are exp_fin(beta log_pos(.)) of device_math.hpp.
+//   last step  t + dt >= t_span (1 - 4 eps): the step tried is h = t_span - t and t lands on t_span exactly; otherwise h = dt, and
+//              the accept rule reads dt <- dt / q.  For a clamped step (h < dt) the proposal that goes out is the UNCLAMPED one: dt
+//              shrinks as the estimate of the shorter step asks (dt / q, q >= 1) but does not grow past what that step supports
+//              (max(h / q, dt), q < 1) -- a caller that comes back with dt_dev for the next model step starts warm, not from the
+//              remainder of the last one.
+//   first step the caller's dt where it is positive and finite (dt_dev[i], else opts.dt_init); otherwise Hairer's first guess
+//              0.01 ||u||_sc / ||f(u)||_sc with sc_i = abstol_i + reltol |u_i| (||f|| = 0: t_span); capped at t_span.
+//   stop       t = t_span (status 0); accepted + rejected = max_steps (status 1); dt < 1e-14 t_span or not finite (status 2).
+//              max_steps bounds the loop whatever the input.
+//
+// All-Inf plans: a plain per-lane loop; the lanes of a wave finish at different times (the cost of per-parcel control; the entry
+// point's info planes give the active-lane fraction).  Thresholded plans: rhs_physical re-ranks the workgroup at barriers in
+// every evaluation, so every lane makes the same sequence of calls: the loop runs while ANY lane of the workgroup is active
+// (__syncthreads_or), a finished or out-of-range lane passes valid = false and discards the result, and nothing returns before
+// the loop ends.
+//
+// Registers: u, k1 .. k6 and the stage state are eight [N][3] arrays as in tsit5_advance; the k1 .. k6 part of the error estimate
+// is accumulated into k2 (dead once u_new exists) and k7 goes into k3, so no further array is live.
+//
+// This header includes kernels.hpp alone and kernels.hpp does not know it: the text of every other plan-time unit stays as it is.
+#pragma once
+#include "kernels.hpp"
+
+namespace cloudy {
+
+namespace tsit5 {
+// btilde = b - b^ ; sum_j bt_j c_j^p = 0 for p = 0 .. 3 with c = (0, 0.161, 0.327, 0.9, 0.9800255409045097, 1, 1)
+constexpr double bt1 = -0.00178001105222577714, bt2 = -0.0008164344596567469, bt3 = 0.007880878010261995,
+                 bt4 = -0.1447110071732629, bt5 = 0.5823571654525552, bt6 = -0.45808210592918697, bt7 = 0.015151515151515152;
+}  // namespace tsit5
+
+// cloudy_adaptive_opts without its struct_size: a kernel argument
+struct AdaptiveOpts {
+    double reltol, abstol, dt_init;
+    int max_steps;
+};
+enum { ADAPT_DONE = 0, ADAPT_MAX_STEPS = 1, ADAPT_DT_MIN = 2 };   // the status plane
+
+namespace adaptive {
+constexpr double kBeta1 = 7.0 / 50.0, kBeta2 = 2.0 / 25.0, kSafety = 9.0 / 10.0 /* gamma */, kQmin = 1.0 / 5.0, kQmax = 10.0, kQold0 = 1e-4;
+__device__ __forceinline__ bool is_finite(double x) { return fabs(x) < INFINITY; }   // (false for NaN)
+}  // namespace adaptive
+
+// u_in / u_out: the plan's planes (they may alias); dt_dev (in/out, one double per parcel: the next proposed dt), t_dev (out: the
+// time reached) and info_dev (out, int32 [3][ld]: accepted, rejected, status) may each be null.
+template <int N, int P, int MODE, typename TIO, bool SPEC = false, int BS = kBlock>
+__device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restrict__ Ag, const double *__restrict__ nodes, size_t n,
+                                                    size_t ld, const TIO *u_in, TIO *u_out, double t_span, AdaptiveOpts o,
+                                                    double *dt_dev, double *t_dev, int *info_dev) {
+    using namespace tsit5;
+    const KArgs<N, P> &A = *Ag;
+    const size_t i = (size_t)blockIdx.x * BS + threadIdx.x;
+    const bool valid = i < n;
+    constexpr bool kRanked = MODE != MODE_ALLINF;
+    constexpr bool kNormalisedState = !kRanked;  // see rhs_normalised
+    if (!(t_span > 0.0)) {   // (wave- and workgroup-uniform: a kernel argument) nothing to integrate, the planes as they are
+        if (!valid) return;
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (q < 2 || A.np[m] == 3) {
+                    const TIO v = u_in[(size_t)(A.off[m] + q) * ld + i];
+                    u_out[(size_t)(A.off[m] + q) * ld + i] = v;
+                }
+        if (t_dev) t_dev[i] = 0.0;
+        if (info_dev) info_dev[i] = 0, info_dev[ld + i] = 0, info_dev[2 * ld + i] = ADAPT_DONE;
+        return;
+    }
+    if (!kRanked && !valid) return;
+    double u[N][3], atol[N][3];
+    int count = 0;
+#pragma unroll
+    for (int m = 0; m < N; ++m) {
+        const int off = A.off[m];
+        u[m][0] = valid ? (double)u_in[(size_t)(off + 0) * ld + i] : 0.0;
+        u[m][1] = valid ? (double)u_in[(size_t)(off + 1) * ld + i] : 0.0;
+        u[m][2] = (valid && A.np[m] == 3) ? (double)u_in[(size_t)(off + 2) * ld + i] : 0.0;
+        count += A.np[m] == 3 ? 3 : 2;   // (the planes a mode has: the third slot of a two-moment mode is padding)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (kNormalisedState) u[m][q] = div_by_const(u[m][q], A.norm[3 * m + q], A.inv_norm[3 * m + q]);
+            atol[m][q] = kNormalisedState ? o.abstol : o.abstol * A.norm[3 * m + q];
+        }
+    }
+    const double n_moms = (double)count;
+    // the plan constants through an opaque zero offset per RHS evaluation (see ssprk33_body); none when compiled for the plan.
+    // live: the lane's result is wanted (thresholded plans: every lane calls, idle ones sit through the ranking's barriers)
+    bool active = valid;
+    auto rhs = [&](const double (&state)[N][3], double (&deriv)[N][3]) {
+        size_t oz = 0;
+        if (!SPEC) asm volatile("" : "+s"(oz));
+        if (kNormalisedState)
+            rhs_normalised<N, P, SPEC>(*(Ag + oz), state, deriv);
+        else
+            rhs_physical<N, P, MODE, SPEC, BS>(*(Ag + oz), nodes, valid && active, state, deriv);
+    };
+    double k1[N][3], k2[N][3], k3[N][3], k4[N][3], k5[N][3], k6[N][3], w[N][3];
+    rhs(u, k1);
+    // ---- the first step
+    double dt = dt_dev && valid ? dt_dev[i] : o.dt_init;
+    if (!(dt > 0.0 && adaptive::is_finite(dt))) {
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (q < 2 || A.np[m] == 3) {
+                    const double sc = fma(o.reltol, fabs(u[m][q]), atol[m][q]);
+                    const double r0 = u[m][q] / sc, r1 = k1[m][q] / sc;
+                    s0 = fma(r0, r0, s0);
+                    s1 = fma(r1, r1, s1);
+                }
+        const double d0 = sqrt(s0 / n_moms), d1 = sqrt(s1 / n_moms);
+        dt = d1 == 0.0 ? t_span : 0.01 * d0 / d1;
+    }
+    dt = dt > t_span ? t_span : dt;   // (keeps a NaN: status 2 below)
+    double t = 0.0, qold = adaptive::kQold0;
+    int n_acc = 0, n_rej = 0, status = ADAPT_DONE;
+    const double t_last = t_span * (1.0 - 4.0 * kEps), dt_min = 1e-14 * t_span;
+#pragma unroll 1
+    for (;;) {
+        if (active) {
+            if (n_acc + n_rej >= o.max_steps) status = ADAPT_MAX_STEPS, active = false;
+            else if (!(dt >= dt_min) || !adaptive::is_finite(dt)) status = ADAPT_DT_MIN, active = false;
+        }
+        if (kRanked) {
+            if (!__syncthreads_or(active ? 1 : 0)) break;
+        } else if (!active) {
+            break;
+        }
+        const bool last = t + dt >= t_last;
+        const double h = last ? t_span - t : dt;
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) w[m][q] = fma(h * a21, k1[m][q], u[m][q]);
+        rhs(w, k2);
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) w[m][q] = fma(h, fma(a31, k1[m][q], a32 * k2[m][q]), u[m][q]);
+        rhs(w, k3);
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) w[m][q] = fma(h, fma(a41, k1[m][q], fma(a42, k2[m][q], a43 * k3[m][q])), u[m][q]);
+        rhs(w, k4);
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                w[m][q] = fma(h, fma(a51, k1[m][q], fma(a52, k2[m][q], fma(a53, k3[m][q], a54 * k4[m][q]))), u[m][q]);
+        rhs(w, k5);
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                w[m][q] = fma(h, fma(a61, k1[m][q], fma(a62, k2[m][q], fma(a63, k3[m][q], fma(a64, k4[m][q], a65 * k5[m][q])))),
+                              u[m][q]);
+        rhs(w, k6);
+        // u_new into w; the k1 .. k6 part of the error estimate into k2, which is dead from here; then k7 into k3
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                w[m][q] = fma(h, fma(a71, k1[m][q], fma(a72, k2[m][q], fma(a73, k3[m][q], fma(a74, k4[m][q],
+                                                                                            fma(a75, k5[m][q], a76 * k6[m][q]))))),
+                              u[m][q]);
+                k2[m][q] = fma(bt1, k1[m][q], fma(bt2, k2[m][q], fma(bt3, k3[m][q], fma(bt4, k4[m][q],
+                                                                                        fma(bt5, k5[m][q], bt6 * k6[m][q])))));
+            }
+        rhs(w, k3);
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (q < 2 || A.np[m] == 3) {
+                    const double err = h * fma(bt7, k3[m][q], k2[m][q]);
+                    const double sc = fma(o.reltol, fmax(fabs(u[m][q]), fabs(w[m][q])), atol[m][q]);
+                    const double r = err / sc;
+                    s = fma(r, r, s);
+                }
+        const double eest = sqrt(s / n_moms);
+        if (!active) continue;   // (an idle lane of a thresholded plan: it only sat through the barriers)
+        if (!adaptive::is_finite(eest)) {
+            ++n_rej;
+            dt = h / 5.0;
+            continue;
+        }
+        const double q11 = eest > 0.0 ? exp_fin(adaptive::kBeta1 * log_pos(eest)) : 0.0;
+        if (eest <= 1.0) {
+            double q = q11 / exp_fin(adaptive::kBeta2 * log_pos(qold)) / adaptive::kSafety;
+            q = fmin(fmax(q, 1.0 / adaptive::kQmax), 1.0 / adaptive::kQmin);
+            ++n_acc;
+            t = last ? t_span : t + h;
+            dt = fmax(h / q, fmin(dt, dt / q));
+            qold = fmax(eest, adaptive::kQold0);
+#pragma unroll
+            for (int m = 0; m < N; ++m)
+#pragma unroll
+                for (int qq = 0; qq < 3; ++qq) u[m][qq] = w[m][qq], k1[m][qq] = k3[m][qq];
+            if (last) active = false;   // status 0
+        } else {
+            ++n_rej;
+            dt = h / fmin(1.0 / adaptive::kQmin, q11 / adaptive::kSafety);
+        }
+    }
+    if (!valid) return;
+#pragma unroll
+    for (int m = 0; m < N; ++m) {
+        const int off = A.off[m];
+        if (kNormalisedState) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) u[m][q] *= A.norm[3 * m + q];
+        }
+        u_out[(size_t)(off + 0) * ld + i] = (TIO)u[m][0];
+        u_out[(size_t)(off + 1) * ld + i] = (TIO)u[m][1];
+        if (A.np[m] == 3) u_out[(size_t)(off + 2) * ld + i] = (TIO)u[m][2];
+    }
+    if (dt_dev) dt_dev[i] = dt;
+    if (t_dev) t_dev[i] = t;
+    if (info_dev) info_dev[i] = n_acc, info_dev[ld + i] = n_rej, info_dev[2 * ld + i] = status;
+}
+
+}  // namespace cloudy

@@ -25,6 +25,7 @@
 #include "jit.hpp"
 #include "box_sources.hpp"
 #include "parcel.hpp"
+#include "adaptive.hpp"
 #include "reduce_kernels.hpp"
 
 using namespace cloudy;
@@ -297,6 +298,7 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_BOX_SSPRK33: return JIT_BOX;
     case OP_PARCEL_SSPRK33:
     case OP_PARCEL_RHS: return JIT_PARCEL;
+    case OP_TSIT5_ADAPTIVE: return JIT_ADAPTIVE;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
@@ -345,6 +347,8 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
     int aligned16 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     double coef = r.coef, s_scalar = r.s_scalar;
     const double *s_dev = r.s_dev;
+    double *dt_dev = r.dt_dev, *t_dev = r.t_dev;
+    int32_t *info_dev = r.info_dev;
     double nq_cutoff = r.s_scalar / h.norms[1], nq_n0 = h.norms[0], nq_m0 = h.norms[1];
     void *args[kJitMaxArgs];
     for (int i = 0; i < k.n_args; ++i) switch (k.args[i]) {
@@ -369,6 +373,10 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
         case A_HINT2: args[i] = &hints.p2; break;
         case A_ALIGNED16: args[i] = &aligned16; break;
         case A_PARCEL: args[i] = const_cast<void *>(r.parcel); break;   // (by value: the pointer to them)
+        case A_ADAPTIVE: args[i] = const_cast<void *>(r.adaptive); break;   // (likewise)
+        case A_DT_DEV: args[i] = &dt_dev; break;
+        case A_T_DEV: args[i] = &t_dev; break;
+        case A_INFO_DEV: args[i] = &info_dev; break;
         case A_NQ_CUTOFF: args[i] = &nq_cutoff; break;
         case A_NQ_N0: args[i] = &nq_n0; break;
         case A_NQ_M0: args[i] = &nq_m0; break;
@@ -514,6 +522,9 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
                                                   "the plan (hiprtc)");
     if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS)
         return refuse_without_unit(plan, JIT_PARCEL, "the parcel kernels are compiled for the plan (hiprtc)");
+    if (r.op == OP_TSIT5_ADAPTIVE)
+        return refuse_without_unit(plan, JIT_ADAPTIVE, "cloudy_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and has no "
+                                                       "ahead-of-time instance: cloudy_tsit5_steps steps such a plan with a fixed dt");
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
@@ -590,6 +601,15 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
         if ((r.sources & SRC_COAL) && plan->h.mode != MODE_ALLINF)
             return fail(CLOUDY_EUNSUPPORTED, "the parcel kernel with coalescence is built for plans whose thresholds are all Inf (the "
                                              "ranked variant is not): pass CLOUDY_SRC_COND alone, or %s", kStaged);
+    }
+    if (r.op == OP_TSIT5_ADAPTIVE) {
+        if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
+            return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_adaptive is not built for quadrature (NumericalCoalStyle) plans: "
+                                             "cloudy_tsit5_steps steps them with a fixed dt");
+        if (plan->h.dtype == CLOUDY_F32_FAST)
+            return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_adaptive serves CLOUDY_F64, CLOUDY_F64_RELAXED and CLOUDY_F32 plans (state and "
+                                             "step control in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode): the "
+                                             "fixed-step alternative is cloudy_tsit5_steps on a CLOUDY_F32 plan");
     }
     if (r.n == 0) return CLOUDY_OK;
     DeviceGuard guard(plan->h.device);
@@ -1082,6 +1102,52 @@ int cloudy_tsit5_steps(const cloudy_plan *plan, size_t n, size_t ld, const void 
     LaunchReq r(OP_TSIT5, n, ld, u_in_dev, u_out_dev, stream);
     r.dt = dt;
     r.n_steps = n_steps;
+    return run(plan, r);
+}
+
+void cloudy_adaptive_opts_init(cloudy_adaptive_opts *o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (uint32_t)sizeof(*o);
+    o->reltol = 1e-6;
+    o->abstol = 1e-9;
+    o->dt_init = 0.0;
+    o->max_steps = 10000;
+}
+
+// the checks of cloudy_tsit5_adaptive that need no device.  The plan comes last (parcel_request says why).
+static int adaptive_request(const cloudy_plan *plan, size_t n, size_t ld, const void *in, void *out, double t_span,
+                            const cloudy_adaptive_opts *o, AdaptiveOpts &c) {
+    if (!o) return fail(CLOUDY_EINVAL, "opts is NULL");
+    if (o->struct_size != sizeof(cloudy_adaptive_opts))
+        return fail(CLOUDY_EINVAL, "opts.struct_size (%u) is not sizeof(cloudy_adaptive_opts) (%zu): call cloudy_adaptive_opts_init",
+                    (unsigned)o->struct_size, sizeof(cloudy_adaptive_opts));
+    if (!std::isfinite(o->reltol) || !std::isfinite(o->abstol) || !std::isfinite(o->dt_init))
+        return fail(CLOUDY_EINVAL, "opts.reltol (%g), opts.abstol (%g) and opts.dt_init (%g) must be finite", o->reltol, o->abstol,
+                    o->dt_init);
+    if (!(o->reltol > 0.0)) return fail(CLOUDY_EINVAL, "opts.reltol (%g) must be positive", o->reltol);
+    if (o->abstol < 0.0) return fail(CLOUDY_EINVAL, "opts.abstol (%g) must be >= 0", o->abstol);
+    if (o->dt_init < 0.0) return fail(CLOUDY_EINVAL, "opts.dt_init (%g) must be >= 0 (0: automatic)", o->dt_init);
+    if (!std::isfinite(t_span) || t_span < 0.0) return fail(CLOUDY_EINVAL, "t_span (%g) must be finite and >= 0", t_span);
+    if (o->max_steps < 1 || o->max_steps > 1000000)
+        return fail(CLOUDY_EINVAL, "opts.max_steps (%d) must be in [1, 1000000]: it bounds the work of a launch", (int)o->max_steps);
+    if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
+    if (n > 0 && (!in || !out)) return fail(CLOUDY_EINVAL, "device buffer is NULL");
+    c = {o->reltol, o->abstol, o->dt_init, (int)o->max_steps};
+    return check_batch(plan, n, ld, in, out);
+}
+
+int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, double t_span,
+                          const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream) {
+    AdaptiveOpts c;
+    int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c);
+    if (rc) return rc;
+    LaunchReq r(OP_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
+    r.dt = t_span;
+    r.adaptive = &c;
+    r.dt_dev = dt_dev;
+    r.t_dev = t_dev;
+    r.info_dev = info_dev;
     return run(plan, r);
 }
 

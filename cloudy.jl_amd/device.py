@@ -11,13 +11,14 @@ from . import _lib
 
 
 class DeviceArray:
-    """A float64 (or float32, for CLOUDY_F32 plans) (planes, n) buffer in HBM owned through cloudy_malloc/cloudy_free."""
+    """A float64 (or float32, for CLOUDY_F32 plans) (planes, n) buffer in HBM owned through cloudy_malloc/cloudy_free; int32 for
+    the count / status planes of cloudy_tsit5_adaptive (DeviceArray.zeros(3, ld, np.int32))."""
 
     def __init__(self, planes, n, dtype=np.float64):
         self.shape = (int(planes), int(n))
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-            raise TypeError("DeviceArray holds float64 or float32")
+        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.int32)):
+            raise TypeError("DeviceArray holds float64 or float32 (moment planes), or int32 (count planes)")
         self.nbytes = self.dtype.itemsize * self.shape[0] * self.shape[1]
         p = C.c_void_p()
         _lib.check(_lib.lib().cloudy_malloc(C.byref(p), max(self.nbytes, 8)))

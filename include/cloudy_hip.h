@@ -277,8 +277,9 @@ int cloudy_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, c
 /* n_steps explicit steps of the Tsit5 tableau (Tsitouras 2011; OrdinaryDiffEq's Tsit5()) with FIXED dt, fused around the
  * RHS like cloudy_ssprk33_steps (state and the six stage derivatives in registers, 6 RHS evaluations per step, FSAL).
  * BASELINE configs[0] names Tsit5 for the single-box Golovin case; no reference driver uses it (all of them call
- * solve(prob, SSPRK33(), dt = ...)), and OrdinaryDiffEq's adaptive step control needs a global error norm over the state,
- * which a batch of independent parcels does not have: this is the tableau applied per parcel with the caller's dt.
+ * solve(prob, SSPRK33(), dt = ...)), and OrdinaryDiffEq's adaptive step control uses a global error norm over the state,
+ * which a batch of independent parcels does not have: this is the tableau applied per parcel with the caller's dt
+ * (cloudy_tsit5_adaptive below controls the step per parcel, with a per-parcel norm).
  * Served for every plan cloudy_ssprk33_steps serves (round 4): AnalyticalCoalStyle with thresholds Inf (state kept in
  * normalised units between load and store), fixed or MovingThreshold, and NumericalCoalStyle in either quad_mode; fp64 or
  * float planes (CLOUDY_F32_FAST: CLOUDY_EUNSUPPORTED).  The kernel is compiled for the plan on the first call
@@ -286,6 +287,52 @@ int cloudy_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, c
  * NumericalCoalStyle plan answers CLOUDY_EUNSUPPORTED. */
 int cloudy_tsit5_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
                        double dt, int n_steps, void *stream);
+
+/* Per-parcel ADAPTIVE Tsit5: every parcel is advanced from t = 0 to t = t_span with the 5(4) pair of the Tsit5 tableau under a
+ * step-size controller of its own (csrc/adaptive.hpp).  Each parcel of a batch is its own ODE, so each lane carries its own t, dt
+ * and error estimate: a batch whose number concentrations span decades is advanced by one model time step without a common dt, and
+ * the caller learns what happened to every parcel.  (cloudy_tsit5_steps is the same tableau with one fixed dt for the batch.)
+ *   error norm   err_i = h sum_j btilde_j k_j,i; sc_i = abstol + reltol max(|u_i|, |u_new,i|); EEst = sqrt(mean_i (err_i/sc_i)^2) over
+ *                the parcel's prognostic moments.  abstol is in the plan's NORMALISED units (mom ./ norms: the units in which every
+ *                moment of a plan is O(1)); reltol is relative.
+ *   controller   a PI controller with these constants -- beta1 = 7/50, beta2 = 2/25, gamma = 9/10, qmin = 1/5, qmax = 10,
+ *                qold_0 = 1e-4: q11 = EEst^beta1, q = clamp(q11 / qold^beta2 / gamma, 1/qmax, 1/qmin).  With h the step tried (h = dt
+ *                but for the last step): EEst <= 1 accepts -- t += h, dt <- max(h / q, min(dt, dt / q)), qold <- max(EEst, qold_0);
+ *                otherwise the step is rejected -- dt <- h / min(1/qmin, q11 / gamma), an estimate that is not finite divides h by
+ *                5.  For h = dt the accept rule is dt / q.  It is specified here and in csrc/adaptive.hpp, not by reference to
+ *                another solver: no bit identity with a run of OrdinaryDiffEq's Tsit5() is claimed.
+ *   last step    t + dt >= t_span (1 - 4 eps): the step tried is h = t_span - t and t lands on t_span exactly.  The accept rule
+ *                above then lets dt shrink as the shorter step's estimate asks but not grow past what that step supports, so the
+ *                dt that goes out is a proposal for a full step, not the remainder of the last one.
+ *   first step   dt_dev[i] where dt_dev is given and the value positive and finite, else opts->dt_init where positive, else Hairer's
+ *                first guess 0.01 ||u||_sc / ||f(u)||_sc (t_span where f = 0); capped at t_span.
+ * Outputs, each optional (NULL) but the state: u_out_dev (may equal u_in_dev); dt_dev, one fp64 value per parcel, in/out -- the next
+ * proposed dt, so that a host model calling once per model step starts warm; t_dev, one fp64 value per parcel -- the time reached;
+ * info_dev, int32 [3][ld] -- the planes accepted steps, rejected steps, status:
+ *   0  reached t_span (t_dev[i] == t_span exactly);   1  accepted + rejected reached opts->max_steps;
+ *   2  dt fell below 1e-14 t_span or is not finite.
+ * A parcel that stops early keeps the state and time it reached.  max_steps is mandatory and bounds the work of a launch.
+ * Argument checks precede any device work, the plan last (CLOUDY_EINVAL): opts NULL or of another struct_size; reltol <= 0,
+ * abstol < 0, a value of opts that is not finite, dt_init < 0; t_span < 0 or not finite; max_steps outside [1, 1000000];
+ * ld < n_parcels; a NULL state with n_parcels > 0; plan NULL.  n_parcels = 0 returns CLOUDY_OK at once; t_span = 0 copies the input
+ * to the output with status 0 and zero counts.
+ * Served: AnalyticalCoalStyle plans with thresholds Inf (state in normalised units between load and store), fixed or MovingThreshold
+ * (the workgroup re-ranks its parcels in every evaluation; a finished parcel's lane sits through the barriers), CLOUDY_F64 /
+ * CLOUDY_F64_RELAXED / CLOUDY_F32 planes (state and control in fp64 registers either way), up to CLOUDY_MAX_MODES modes.
+ * Deliberate limits (CLOUDY_EUNSUPPORTED; cloudy_tsit5_steps is the alternative): NumericalCoalStyle plans, CLOUDY_F32_FAST planes,
+ * and plans without plan-time compilation (specialize = -1, or hiprtc unavailable) -- the kernel is compiled for the plan on the
+ * first call (cloudy_jit_adaptive_tsit5_*) and has no ahead-of-time instance. */
+typedef struct cloudy_adaptive_opts {
+    uint32_t struct_size; /* sizeof(cloudy_adaptive_opts), set by cloudy_adaptive_opts_init */
+    double reltol;        /* 1e-6 */
+    double abstol;        /* 1e-9, normalised units */
+    double dt_init;       /* 0: automatic */
+    int32_t max_steps;    /* 10000: accepted + rejected, per parcel */
+} cloudy_adaptive_opts;
+void cloudy_adaptive_opts_init(cloudy_adaptive_opts *opts);
+int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
+                          double t_span, const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev,
+                          void *stream);
 
 /* n_steps SSPRK33 steps of du/dt = [coal](u) + [cond](u; s, xi) with fixed dt, fused like cloudy_ssprk33_steps: a lane keeps its
  * parcel's state in registers over all stages and steps, the state is read once and written once per call and the parcel's

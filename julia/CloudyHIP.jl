@@ -365,6 +365,54 @@ function solve_tsit5!(u, plan::Plan, dt, n_steps; stream = nothing, sync::Bool =
 end
 
 """
+    AdaptiveOpts()
+
+`cloudy_adaptive_opts` with the defaults of `cloudy_adaptive_opts_init`: reltol = 1e-6, abstol = 1e-9 (normalised units),
+dt_init = 0 (automatic first step), max_steps = 10000 (accepted + rejected, per parcel).
+"""
+mutable struct AdaptiveOpts
+    struct_size::UInt32
+    reltol::Float64
+    abstol::Float64
+    dt_init::Float64
+    max_steps::Int32
+    function AdaptiveOpts()
+        o = new()
+        ccall((:cloudy_adaptive_opts_init, lib), Cvoid, (Ref{AdaptiveOpts},), o)
+        return o
+    end
+end
+
+"""
+    solve_tsit5_adaptive!(u, plan, t_span; reltol = 1e-6, abstol = 1e-9, dt = 0.0, max_steps = 10000, dt_dev = nothing,
+                          t_dev = nothing, info_dev = nothing, stream = nothing, sync = true)
+
+Every parcel of `u` from t = 0 to `t_span` with adaptive Tsit5 under a step-size controller of its own (`cloudy_tsit5_adaptive`:
+include/cloudy_hip.h states the PI controller, the per-parcel error norm and the statuses; no bit identity with
+`solve(prob, Tsit5())` is claimed -- OrdinaryDiffEq's norm is global over the state).  `abstol` is in normalised units
+(`mom ./ norms`).  Optional device arrays, one entry per parcel: `dt_dev::Vector{Float64}` (in/out: first step where positive,
+the next proposed step on return), `t_dev::Vector{Float64}` (out: the time reached), `info_dev::Matrix{Int32}` of size (ld, 3)
+(out: accepted, rejected, status; 0 = reached `t_span`, 1 = `max_steps` attempts, 2 = dt below 1e-14 t_span or not finite).
+AnalyticalCoalStyle plans; a NumericalCoalStyle plan answers CLOUDY_EUNSUPPORTED (`solve_tsit5!` steps it with a fixed dt).
+"""
+function solve_tsit5_adaptive!(u, plan::Plan, t_span; reltol = 1e-6, abstol = 1e-9, dt = 0.0, max_steps = 10000,
+                               dt_dev = nothing, t_dev = nothing, info_dev = nothing, stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(u, plan.nmom)
+    s = stream === nothing ? current_stream() : stream
+    o = AdaptiveOpts()
+    o.reltol, o.abstol, o.dt_init, o.max_steps = reltol, abstol, dt, max_steps
+    dptr = dt_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(dt_dev))
+    tptr = t_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(t_dev))
+    iptr = info_dev === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(info_dev))
+    check(ccall((:cloudy_tsit5_adaptive, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Ref{AdaptiveOpts}, Ptr{Cdouble}, Ptr{Cdouble},
+                 Ptr{Int32}, Ptr{Cvoid}),
+                plan.handle, n, ld, pointer(u), pointer(u), t_span, o, dptr, tptr, iptr, s))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), s))
+    return u
+end
+
+"""
     solve_box_ssprk33!(u, plan, dt, n_steps, xi, s; coal = true, cond = true, stream = nothing, sync = true)
 
 `solve(ODEProblem(rhs!, u, tspan, p), SSPRK33(), dt = dt)` for `n_steps` fixed steps on the device with `rhs!` the sum of the

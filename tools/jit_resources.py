@@ -3,7 +3,8 @@
 cloudy_jit_selfcheck compiles the plan's translation unit for gfx950, CLOUDY_HIP_JIT_DUMP keeps the code object, and
 the figures are read from its metadata notes.
 usage: python tools/jit_resources.py [--keep DIR] cfg3b cfg4 moving4 cfg4q rainshaft_gamma_mixture rainshaft_single_gamma
-       parcel_monodisperse parcel_gamma parcel_mixture ..."""
+       parcel_monodisperse parcel_gamma parcel_mixture ...
+       python tools/jit_resources.py --match adaptive --no-vel cfg2 cfg3a cfg3b adaptive_n4    (the adaptive Tsit5 unit alone)"""
 import argparse
 import ctypes as C
 import glob
@@ -21,6 +22,8 @@ READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keep", default="", help="directory for the dumped .hip / .co files (default: a temp dir)")
+    ap.add_argument("--match", default="", help="print only the kernels whose name contains this (e.g. adaptive)")
+    ap.add_argument("--no-vel", action="store_true", help="plans without a velocity term: the column units are not compiled")
     ap.add_argument("workloads", nargs="+")
     a = ap.parse_args()
     dump = a.keep or tempfile.mkdtemp(prefix="cloudy_jit_")
@@ -63,17 +66,23 @@ def main():
             # (1e8, 1e-12), thresholds Inf: the parcel unit (cloudy_jit_parcel_*) among the plan's units
             types = {"parcel_monodisperse": [2], "parcel_gamma": [1], "parcel_mixture": [0, 1]}[name]
             d, keep = pkg.Plan.make_desc(types, np.array([[1.0]]), (float("inf"),) * len(types), (1e8, 1e-12), 0)
+        elif name == "adaptive_n4":
+            # four Gamma modes, Golovin b = 5 between every pair, thresholds Inf: the adaptive Tsit5 unit (cloudy_jit_adaptive_tsit5_*)
+            # of a plan with nine live [4][3] arrays
+            d, keep = pkg.Plan.make_desc([1] * 4, np.array([[2.220446049250313e-22, 5.0], [5.0, 0.0]]), (float("inf"),) * 4, bench.NORMS, 0)
         else:
             spec = bench.workload_spec(name)
             # (one sedimentation velocity term, so that the fused column integrator is compiled as well)
             d, keep = pkg.Plan.make_desc([1] * spec["n_modes"], bench.kernel_matrix(spec), spec["thresholds"], bench.NORMS,
-                                         1 if spec.get("moving") else 0, vel=((50.0, 1.0 / 6),))
+                                         1 if spec.get("moving") else 0, vel=() if a.no_vel else ((50.0, 1.0 / 6),))
         if L.cloudy_jit_selfcheck(C.byref(d), b"gfx950") != 0:
             raise SystemExit(f"{name}: " + L.cloudy_last_error().decode())
         for co in sorted(set(glob.glob(os.path.join(dump, "*.co"))) - before):
             notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True).stdout
             for blk in notes.split("- .agpr_count")[1:]:
                 get = lambda key: (re.search(rf"\.{key}:\s*(\S+)", blk) or [None, "?"])[1]
+                if a.match and a.match not in get("name"):
+                    continue
                 print(f"{name}: {get('name')}: {get('vgpr_count')} VGPRs, {get('vgpr_spill_count')} spilled, "
                       f"scratch {get('private_segment_fixed_size')} B, LDS {get('group_segment_fixed_size')} B, "
                       f"{get('sgpr_count')} SGPRs  [{os.path.basename(co)}]")

@@ -22,6 +22,10 @@ every experiment switch of the library is an environment variable, so an A/B run
         cloudy_parcel_ssprk33_steps on a batch of the driver's mixture case (Exponential + Gamma): (a) the fused call, (b) the
         sequence it replaces -- cloudy_cond_evap per stage plus torch thermodynamics and updates, (c) cloudy_box_ssprk33_steps with
         CLOUDY_SRC_COND on the same moments (constant supersaturation: the floor)
+  python tools/timeit.py adaptive [--parcels P] [--t-span T] [--reltol R]
+        cloudy_tsit5_adaptive on the cfg3a plan, n log-uniform over three decades: (a) the adaptive call, (b) cloudy_tsit5_steps at
+        the fixed dt the densest parcels need for the same measured end-state error -- the caller's only alternative without (a);
+        and the active-lane fraction of (a) from the info planes, sum(attempts) / sum over waves of 64 max(attempts)
   python tools/timeit.py host [--parcels P]
         cloudy_coal_rhs_host on cfg3a: the PCIe-inclusive rate (host arrays staged through the device)
 
@@ -206,6 +210,51 @@ def cmd_integrators(a, pkg, L):
         print(f"{name}, {n} parcels: SSPRK33 {ms_s / 12:.4f} ms per evaluation, Tsit5 {ms_t / 25:.4f} ms per evaluation", flush=True)
 
 
+def cmd_adaptive(a, pkg, L):
+    """ms per call: (a) cloudy_tsit5_adaptive to t_span at reltol, (b) cloudy_tsit5_steps with the number of equal steps at which
+    its worst end-state error over a sample of parcels (against 400 fixed steps) is no larger than (a)'s"""
+    n, t_span, sample = a.parcels or 10_000_000, a.t_span, 20000
+    wl = bench.make_workload("cfg3a", 1)
+    plan = wl["coal_data"].plan(wl["dist_types"])
+    mom = bench.synth_moments(2, n, 7, degenerate_frac=0.0)   # the cloud mode's n: 1e6 .. 1e9, log-uniform
+    u0, out = pkg.DeviceArray.from_numpy(mom), pkg.DeviceArray.zeros(*mom.shape)
+    info, t_dev = pkg.DeviceArray.zeros(3, n, np.int32), pkg.DeviceArray.zeros(1, n)
+    opts = pkg._lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol = a.reltol
+    call = lambda: pkg._lib.check(L.cloudy_tsit5_adaptive(plan.handle, n, n, u0.ptr, out.ptr, t_span, C.byref(opts), None, t_dev.ptr,   # noqa: E731
+                                                          info.ptr, None))
+    ms_a = bench._sustained_ms(pkg, call, min_reps=3)
+    counts = info.to_numpy()
+    attempts = (counts[0] + counts[1]).astype(np.int64)
+    waves = np.pad(attempts, (0, -n % 64)).reshape(-1, 64)
+    lane_fraction = attempts.sum() / (64 * waves.max(axis=1)).sum()
+    got = out.columns_to_numpy(sample)
+    us, truth = pkg.DeviceArray.from_numpy(np.ascontiguousarray(mom[:, :sample])), pkg.DeviceArray.zeros(6, sample)
+    pkg._lib.check(L.cloudy_tsit5_steps(plan.handle, sample, sample, us.ptr, truth.ptr, t_span / 400, 400, None))
+    want = truth.to_numpy()
+    # the error is measured on the regular parcels of the sample (as the stepping tests: finite and within a factor 10 of their
+    # initial state after 400 steps) that the adaptive call brought to t_span: the order-2 kernel blows up in finite time on the
+    # densest tail of 1e7 parcels, where no step size has an error to compare
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(want).all(axis=0) & (np.abs(want) <= 10 * np.abs(mom[:, :sample]) + 1e-300).all(axis=0) & (counts[2, :sample] == 0)
+    err = lambda x: float(np.max((np.abs(x - want) / np.maximum(np.abs(mom[:, :sample]) + np.abs(want), 1e-300))[:, ok]))   # noqa: E731
+    e_a = err(got)
+    steps, fs = 1, pkg.DeviceArray.zeros(6, sample)
+    while steps < 400:
+        pkg._lib.check(L.cloudy_tsit5_steps(plan.handle, sample, sample, us.ptr, fs.ptr, t_span / steps, steps, None))
+        e_b = err(fs.to_numpy())
+        if e_b <= e_a:   # (NaN: not yet)
+            break
+        steps += max(1, steps // 4)
+    ms_b = bench._sustained_ms(pkg, lambda: pkg._lib.check(L.cloudy_tsit5_steps(plan.handle, n, n, u0.ptr, out.ptr, t_span / steps, steps, None)),
+                               min_reps=3)
+    print(f"cfg3a, {n} parcels to t = {t_span:g}, reltol {a.reltol:g}: (a) cloudy_tsit5_adaptive {ms_a:.3f} ms, attempts 1 .. {attempts.max()} "
+          f"(mean {attempts.mean():.2f}, rejected {int(counts[1].sum())}, status != 0: {int((counts[2] != 0).sum())}), end-state error "
+          f"{e_a:.1e} on {int(ok.sum())} regular parcels of {sample} | (b) cloudy_tsit5_steps, {steps} steps of {t_span / steps:.3g} for error {e_b:.1e}: {ms_b:.3f} ms | "
+          f"b/a {ms_b / ms_a:.2f} | active-lane fraction of (a) {lane_fraction:.3f}", flush=True)
+
+
 def cmd_box(a, pkg, L):
     """ms per call of S steps: (a) cloudy_ssprk33_steps, (b) / (c) cloudy_box_ssprk33_steps with COAL | COND / COND, (d) the same
     steps stage by stage: two right-hand-side launches and the update on the planes (torch, on the same stream) per stage"""
@@ -371,11 +420,16 @@ def main():
     pc = sub.add_parser("parcel")
     pc.add_argument("--parcels", type=int, default=0)
     pc.add_argument("--steps", type=int, default=2)
+    ad = sub.add_parser("adaptive")
+    ad.add_argument("--parcels", type=int, default=0)
+    ad.add_argument("--t-span", type=float, default=5e-3)
+    ad.add_argument("--reltol", type=float, default=1e-6)
     hh = sub.add_parser("host")
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
-    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
+    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "adaptive": cmd_adaptive,
+     "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
 if __name__ == "__main__":
