@@ -86,6 +86,7 @@ SYMBOLS = {
     "cloudy_tsit5_steps": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, _i, _vp]),
     "cloudy_adaptive_opts_init": (None, [C.POINTER(AdaptiveOptsC)]),
     "cloudy_tsit5_adaptive": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp]),
+    "cloudy_tsit5_adaptive_saveat": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp, _sz, _dp, _vp]),
     "cloudy_box_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, _i, _vp]),
     "cloudy_parcel_params_init": (None, [C.POINTER(ParcelParamsC)]),
     "cloudy_parcel_rhs": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(ParcelParamsC), _i, _vp, _vp]),

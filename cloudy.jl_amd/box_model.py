@@ -164,6 +164,57 @@ def solve_tsit5_adaptive(par, u, t_span, reltol=1e-6, abstol=1e-9, dt=None, max_
     return accepted, rejected, status, t_arr.to_numpy()[0]
 
 
+def solve_tsit5_adaptive_saveat(par, u, t_span, saveat, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000, out=None, dt_dev=None,
+                                info=False, stream=None, coal_type=None):
+    """solve_tsit5_adaptive with dense output (cloudy_tsit5_adaptive_saveat): the same integration -- the step sequence of every
+    parcel is the one solve_tsit5_adaptive takes, bit for bit -- and the state of every parcel at the batch-wide times `saveat`
+    (host floats in [0, t_span], strictly increasing), from the free 4th-order interpolant of Tsit5 inside the accepted step that
+    holds the time.  Returns the snapshots as a DeviceArray of shape (n_save * planes, ld) in the plane type of `u`: snapshot j,
+    plane p is row j * planes + p; a snapshot at 0 equals the input and one at t_span the final state bit for bit; a parcel that
+    stopped early has NaN in the snapshots it did not reach.  With info=True returns (snapshots, accepted, rejected, status,
+    t_reached) and raises as solve_tsit5_adaptive does -- keep the snapshots of a run that may stop early with info=False and
+    read the status planes through the C call.  Everything else as solve_tsit5_adaptive."""
+    import ctypes as C
+
+    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
+        raise ValueError("Invalid coal style!")
+    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
+    uptr, planes, n, ld = as_device(u)
+    o = out if out is not None else u
+    optr, oplanes, on, old = as_device(o)
+    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
+        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    dptr = None
+    if dt_dev is not None:
+        dptr, dplanes, dn, _ = as_device(dt_dev)
+        if dplanes != 1 or dn != n or dtype_code(dt_dev) != 0:
+            raise ValueError("dt_dev must be an (1, n) fp64 device array")
+    times = np.ascontiguousarray(np.atleast_1d(np.asarray(saveat, dtype=np.float64)))
+    if times.ndim != 1:
+        raise ValueError("saveat must be a sequence of times")
+    n_save = int(times.size)
+    saved = DeviceArray(n_save * planes, ld, dtype=np.float32 if dtype_code(u) else np.float64)
+    L = _lib.lib()
+    opts = _lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
+    t_arr = DeviceArray.zeros(1, n) if info else None
+    i_arr = DeviceArray.zeros(3, ld, dtype=np.int32) if info else None
+    _lib.check(L.cloudy_tsit5_adaptive_saveat(plan.handle, n, ld, uptr, optr, float(t_span), C.byref(opts), dptr,
+                                              t_arr.ptr if info else None, i_arr.ptr if info else None, stream, n_save,
+                                              times.ctypes.data_as(C.POINTER(C.c_double)), saved.ptr if n_save else None))
+    if not info:
+        return saved
+    _lib.check(L.cloudy_stream_synchronize(stream))
+    counts = i_arr.to_numpy()[:, :n]
+    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise RuntimeError(f"solve_tsit5_adaptive_saveat: {bad.size} of {n} parcels did not reach t_span; the first is parcel "
+                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
+    return saved, accepted, rejected, status, t_arr.to_numpy()[0]
+
+
 def solve_box_ssprk33(par, u, dt, n_steps, xi, s, coal=True, cond=True, out=None, stream=None, coal_type=None):
     """solve(ODEProblem(rhs!, u, tspan, par), SSPRK33(), dt = dt) for n_steps fixed steps on the device, with rhs! the sum of
     the selected sources: rhs_coal! (`coal`) and rhs_condensation!(dm, m, par, s) (`cond`; condensation_single_gamma.jl:24-28,

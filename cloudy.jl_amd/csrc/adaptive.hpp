@@ -39,6 +39,17 @@
 // Registers: u, k1 .. k6 and the stage state are eight [N][3] arrays as in tsit5_advance; the k1 .. k6 part of the error estimate
 // is accumulated into k2 (dead once u_new exists) and k7 goes into k3, so no further array is live.
 //
+// Dense output (SAVE = true, cloudy_tsit5_adaptive_saveat): the same loop, the same expressions and the same controller -- nothing
+// of what follows feeds back into a step -- plus the state at the batch-wide save times t_save[0 .. n_save) (device doubles,
+// strictly increasing, within [0, t_span]).  Every lane keeps a cursor j.  After an accepted step t -> t_new, while t_save[j] <=
+// t_new: th = (t_save[j] - t) / h and snapshot j is u + h sum_i b_i(th) k_i, i = 1 .. 7 (tsit5::interp_weights: the free 4th-order
+// interpolant of the pair, no further evaluation), or u_new through the expressions of the final store where t_save[j] == t_new
+// (a snapshot at t_span has the bits of u_out).  A save time 0 gets the values as loaded (the bits of u_in); what a stopped
+// parcel (status 1, 2) did not reach gets a quiet NaN.  Snapshots are stored in physical units in the plan's plane type at
+// u_save[((size_t)j * planes + p) * ld + i]: the lanes of a wave write neighbouring elements of a plane.  So that k1 .. k7, u and
+// u_new are all live when a step is accepted, the error combination and k7 have arrays of their own (two more than above).
+// The snapshot code sits outside the right-hand side: the barriers of a thresholded plan are the ones of SAVE = false.
+//
 // This header includes kernels.hpp alone and kernels.hpp does not know it: the text of every other plan-time unit stays as it is.
 #pragma once
 #include "kernels.hpp"
@@ -49,6 +60,26 @@ namespace tsit5 {
 // btilde = b - b^ ; sum_j bt_j c_j^p = 0 for p = 0 .. 3 with c = (0, 0.161, 0.327, 0.9, 0.9800255409045097, 1, 1)
 constexpr double bt1 = -0.00178001105222577714, bt2 = -0.0008164344596567469, bt3 = 0.007880878010261995,
                  bt4 = -0.1447110071732629, bt5 = 0.5823571654525552, bt6 = -0.45808210592918697, bt7 = 0.015151515151515152;
+// the interpolant over k1 .. k7, th in [0, 1]: b1 = s th (th - r1)(th^2 - p th + q); b2, b3 = s th^2 (th^2 - p th + q);
+// b4 .. b7 = s th^2 (th - r1)(th - r2).  b_i(1) = a7i, b7(1) = 0; sum_i b_i(th) c_i^p = th^(p+1) / (p+1) for p = 0 .. 3
+constexpr double bi1_s = -1.0530884977290216, bi1_r1 = 1.3299890189751412, bi1_p = 1.4364028541716351, bi1_q = 0.7139816917074209;
+constexpr double bi2_s = 0.1017, bi2_p = 2.1966568338249754, bi2_q = 1.2949852507374631;
+constexpr double bi3_s = 2.490627285651252793, bi3_p = 2.38535645472061657, bi3_q = 1.57803468208092486;
+constexpr double bi4_s = -16.54810288924490272, bi4_r1 = 1.21712927295533244, bi4_r2 = 0.61620406037800089;
+constexpr double bi5_s = 47.37952196281928122, bi5_r1 = 1.203071208372362603, bi5_r2 = 0.658047292653547382;
+constexpr double bi6_s = -34.87065786149660974, bi6_r1 = 1.2, bi6_r2 = 0.666666666666666667;
+constexpr double bi7_s = 2.5, bi7_r1 = 1.0, bi7_r2 = 0.6;
+// (the quadratic factors by Horner: th (th - p) + q)
+__device__ __forceinline__ void interp_weights(double th, double (&b)[7]) {
+    const double th2 = th * th;
+    b[0] = bi1_s * th * (th - bi1_r1) * fma(th, th - bi1_p, bi1_q);
+    b[1] = bi2_s * th2 * fma(th, th - bi2_p, bi2_q);
+    b[2] = bi3_s * th2 * fma(th, th - bi3_p, bi3_q);
+    b[3] = bi4_s * th2 * ((th - bi4_r1) * (th - bi4_r2));
+    b[4] = bi5_s * th2 * ((th - bi5_r1) * (th - bi5_r2));
+    b[5] = bi6_s * th2 * ((th - bi6_r1) * (th - bi6_r2));
+    b[6] = bi7_s * th2 * ((th - bi7_r1) * (th - bi7_r2));
+}
 }  // namespace tsit5
 
 // cloudy_adaptive_opts without its struct_size: a kernel argument
@@ -64,17 +95,35 @@ __device__ __forceinline__ bool is_finite(double x) { return fabs(x) < INFINITY;
 }  // namespace adaptive
 
 // u_in / u_out: the plan's planes (they may alias); dt_dev (in/out, one double per parcel: the next proposed dt), t_dev (out: the
-// time reached) and info_dev (out, int32 [3][ld]: accepted, rejected, status) may each be null.
-template <int N, int P, int MODE, typename TIO, bool SPEC = false, int BS = kBlock>
+// time reached) and info_dev (out, int32 [3][ld]: accepted, rejected, status) may each be null.  SAVE: n_save, t_save and u_save
+// (n_save x planes planes of leading dimension ld, aliasing neither u_in nor u_out) as above; without it they are not read.
+template <int N, int P, int MODE, typename TIO, bool SPEC = false, int BS = kBlock, bool SAVE = false>
 __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restrict__ Ag, const double *__restrict__ nodes, size_t n,
                                                     size_t ld, const TIO *u_in, TIO *u_out, double t_span, AdaptiveOpts o,
-                                                    double *dt_dev, double *t_dev, int *info_dev) {
+                                                    double *dt_dev, double *t_dev, int *info_dev, size_t n_save = 0,
+                                                    const double *__restrict__ t_save = nullptr, TIO *__restrict__ u_save = nullptr) {
     using namespace tsit5;
     const KArgs<N, P> &A = *Ag;
     const size_t i = (size_t)blockIdx.x * BS + threadIdx.x;
     const bool valid = i < n;
     constexpr bool kRanked = MODE != MODE_ALLINF;
     constexpr bool kNormalisedState = !kRanked;  // see rhs_normalised
+    // SAVE: snapshot js of this lane's parcel from v (the units of the state) as the final store writes u -- physical units, the
+    // planes a mode has
+    size_t planes = 0;
+#pragma unroll
+    for (int m = 0; m < N; ++m) planes += A.np[m] == 3 ? 3 : 2;
+    auto snapshot = [&](size_t js, const double (&v)[N][3]) {
+#pragma unroll
+        for (int m = 0; m < N; ++m)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (q < 2 || A.np[m] == 3) {
+                    double x = v[m][q];
+                    if (kNormalisedState) x *= A.norm[3 * m + q];
+                    u_save[(js * planes + (size_t)(A.off[m] + q)) * ld + i] = (TIO)x;
+                }
+    };
     if (!(t_span > 0.0)) {   // (wave- and workgroup-uniform: a kernel argument) nothing to integrate, the planes as they are
         if (!valid) return;
 #pragma unroll
@@ -84,6 +133,8 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
                 if (q < 2 || A.np[m] == 3) {
                     const TIO v = u_in[(size_t)(A.off[m] + q) * ld + i];
                     u_out[(size_t)(A.off[m] + q) * ld + i] = v;
+                    if (SAVE)   // (every save time is 0)
+                        for (size_t js = 0; js < n_save; ++js) u_save[(js * planes + (size_t)(A.off[m] + q)) * ld + i] = v;
                 }
         if (t_dev) t_dev[i] = 0.0;
         if (info_dev) info_dev[i] = 0, info_dev[ld + i] = 0, info_dev[2 * ld + i] = ADAPT_DONE;
@@ -92,6 +143,8 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
     if (!kRanked && !valid) return;
     double u[N][3], atol[N][3];
     int count = 0;
+    const bool save0 = SAVE && valid && n_save > 0 && t_save[0] == 0.0;
+    size_t j = save0 ? 1 : 0;   // SAVE: the lane's cursor into t_save
 #pragma unroll
     for (int m = 0; m < N; ++m) {
         const int off = A.off[m];
@@ -99,6 +152,12 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
         u[m][1] = valid ? (double)u_in[(size_t)(off + 1) * ld + i] : 0.0;
         u[m][2] = (valid && A.np[m] == 3) ? (double)u_in[(size_t)(off + 2) * ld + i] : 0.0;
         count += A.np[m] == 3 ? 3 : 2;   // (the planes a mode has: the third slot of a two-moment mode is padding)
+        if constexpr (SAVE)   // a save time 0: the values as loaded, before any normalisation
+            if (save0) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    if (q < 2 || A.np[m] == 3) u_save[(size_t)(off + q) * ld + i] = (TIO)u[m][q];
+            }
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             if (kNormalisedState) u[m][q] = div_by_const(u[m][q], A.norm[3 * m + q], A.inv_norm[3 * m + q]);
@@ -118,6 +177,11 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
             rhs_physical<N, P, MODE, SPEC, BS>(*(Ag + oz), nodes, valid && active, state, deriv);
     };
     double k1[N][3], k2[N][3], k3[N][3], k4[N][3], k5[N][3], k6[N][3], w[N][3];
+    // where the error combination and k7 go: k2 and k3, which are dead by then -- SAVE keeps k1 .. k7 for the interpolant and
+    // gives both an array of its own (not touched, and so not there, without it)
+    double ke_own[N][3], k7_own[N][3];
+    double(&ke)[N][3] = *[&]() -> double(*)[N][3] { if constexpr (SAVE) return &ke_own; else return &k2; }();
+    double(&k7)[N][3] = *[&]() -> double(*)[N][3] { if constexpr (SAVE) return &k7_own; else return &k3; }();
     rhs(u, k1);
     // ---- the first step
     double dt = dt_dev && valid ? dt_dev[i] : o.dt_init;
@@ -181,7 +245,7 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
                 w[m][q] = fma(h, fma(a61, k1[m][q], fma(a62, k2[m][q], fma(a63, k3[m][q], fma(a64, k4[m][q], a65 * k5[m][q])))),
                               u[m][q]);
         rhs(w, k6);
-        // u_new into w; the k1 .. k6 part of the error estimate into k2, which is dead from here; then k7 into k3
+        // u_new into w; the k1 .. k6 part of the error estimate into k2, which is dead from here; then k7 into k3 (ke, k7 above)
 #pragma unroll
         for (int m = 0; m < N; ++m)
 #pragma unroll
@@ -189,17 +253,17 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
                 w[m][q] = fma(h, fma(a71, k1[m][q], fma(a72, k2[m][q], fma(a73, k3[m][q], fma(a74, k4[m][q],
                                                                                             fma(a75, k5[m][q], a76 * k6[m][q]))))),
                               u[m][q]);
-                k2[m][q] = fma(bt1, k1[m][q], fma(bt2, k2[m][q], fma(bt3, k3[m][q], fma(bt4, k4[m][q],
+                ke[m][q] = fma(bt1, k1[m][q], fma(bt2, k2[m][q], fma(bt3, k3[m][q], fma(bt4, k4[m][q],
                                                                                         fma(bt5, k5[m][q], bt6 * k6[m][q])))));
             }
-        rhs(w, k3);
+        rhs(w, k7);
         double s = 0.0;
 #pragma unroll
         for (int m = 0; m < N; ++m)
 #pragma unroll
             for (int q = 0; q < 3; ++q)
                 if (q < 2 || A.np[m] == 3) {
-                    const double err = h * fma(bt7, k3[m][q], k2[m][q]);
+                    const double err = h * fma(bt7, k7[m][q], ke[m][q]);
                     const double sc = fma(o.reltol, fmax(fabs(u[m][q]), fabs(w[m][q])), atol[m][q]);
                     const double r = err / sc;
                     s = fma(r, r, s);
@@ -216,13 +280,34 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
             double q = q11 / exp_fin(adaptive::kBeta2 * log_pos(qold)) / adaptive::kSafety;
             q = fmin(fmax(q, 1.0 / adaptive::kQmax), 1.0 / adaptive::kQmin);
             ++n_acc;
+            if constexpr (SAVE) {
+                const double t_new = last ? t_span : t + h;
+                while (j < n_save) {
+                    const double ts = t_save[j];
+                    if (!(ts <= t_new)) break;
+                    if (ts == t_new) {   // (the end of the step: u_new itself, what the final store writes at t_span)
+                        snapshot(j, w);
+                    } else {
+                        double b[7], v[N][3];
+                        interp_weights((ts - t) / h, b);
+#pragma unroll
+                        for (int m = 0; m < N; ++m)
+#pragma unroll
+                            for (int qq = 0; qq < 3; ++qq)
+                                v[m][qq] = fma(h, fma(b[0], k1[m][qq], fma(b[1], k2[m][qq], fma(b[2], k3[m][qq], fma(b[3], k4[m][qq],
+                                                      fma(b[4], k5[m][qq], fma(b[5], k6[m][qq], b[6] * k7[m][qq])))))), u[m][qq]);
+                        snapshot(j, v);
+                    }
+                    ++j;
+                }
+            }
             t = last ? t_span : t + h;
             dt = fmax(h / q, fmin(dt, dt / q));
             qold = fmax(eest, adaptive::kQold0);
 #pragma unroll
             for (int m = 0; m < N; ++m)
 #pragma unroll
-                for (int qq = 0; qq < 3; ++qq) u[m][qq] = w[m][qq], k1[m][qq] = k3[m][qq];
+                for (int qq = 0; qq < 3; ++qq) u[m][qq] = w[m][qq], k1[m][qq] = k7[m][qq];
             if (last) active = false;   // status 0
         } else {
             ++n_rej;
@@ -230,6 +315,15 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
         }
     }
     if (!valid) return;
+    if constexpr (SAVE) {   // what a parcel stopped by the budget or by dt did not reach (status 0: the cursor is at n_save)
+        const TIO nan = (TIO)__builtin_nan("");
+        for (; j < n_save; ++j)
+#pragma unroll
+            for (int m = 0; m < N; ++m)
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    if (q < 2 || A.np[m] == 3) u_save[(j * planes + (size_t)(A.off[m] + q)) * ld + i] = nan;
+    }
 #pragma unroll
     for (int m = 0; m < N; ++m) {
         const int off = A.off[m];

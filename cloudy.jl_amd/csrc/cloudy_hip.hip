@@ -30,6 +30,35 @@
 
 using namespace cloudy;
 
+namespace {
+// One plain hipMalloc allocation, freed with its owner: a function (hipFree waits for the device: the kernels launched on the
+// allocation are done when the function that owns it returns) or a plan.
+struct DeviceScratch {
+    char *p = nullptr;
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    ~DeviceScratch() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc((void **)&p, bytes); }
+};
+
+// A HIP event, destroyed on return if it was created (or adopted) and not released
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    explicit Event(hipEvent_t adopted) : ev(adopted) {}
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    hipError_t create() { return hipEventCreate(&ev); }
+    hipEvent_t release() { return std::exchange(ev, nullptr); }
+};
+}  // namespace
+
 struct cloudy_plan {
     HostPlan h;
     bool jit_on = false;   // the main unit compiled for the plan (jit.hpp) loaded: plan-time specialised kernels serve the plan
@@ -46,6 +75,12 @@ struct cloudy_plan {
     mutable size_t hint_cap = 0;
     mutable std::vector<unsigned char *> hint_old;
     mutable std::mutex hint_mu;
+    // cloudy_tsit5_adaptive_saveat: the save times of a call on the device -- CLOUDY_MAX_SAVE_TIMES doubles, allocated on the first
+    // such call, freed with the plan.  Calls take turns under save_mu: the upload of a call waits on its stream for `save_done`,
+    // recorded behind the kernel of the call before, so a call on another stream does not overwrite times a kernel still reads.
+    mutable DeviceScratch save_times;
+    mutable Event save_done;
+    mutable std::mutex save_mu;
 };
 
 namespace {
@@ -129,33 +164,6 @@ struct PlanDestroy {
     void operator()(cloudy_plan *p) const { cloudy_plan_destroy(p); }
 };
 using PlanHandle = std::unique_ptr<cloudy_plan, PlanDestroy>;
-
-// One plain hipMalloc allocation, freed on return.  hipFree waits for the device: the kernels launched on the allocation are done
-// when the function that owns it returns.
-struct DeviceScratch {
-    char *p = nullptr;
-    DeviceScratch() = default;
-    DeviceScratch(const DeviceScratch &) = delete;
-    DeviceScratch &operator=(const DeviceScratch &) = delete;
-    ~DeviceScratch() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc((void **)&p, bytes); }
-};
-
-// A HIP event, destroyed on return if it was created (or adopted) and not released
-struct Event {
-    hipEvent_t ev = nullptr;
-    Event() = default;
-    explicit Event(hipEvent_t adopted) : ev(adopted) {}
-    Event(const Event &) = delete;
-    Event &operator=(const Event &) = delete;
-    ~Event() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
-    hipError_t create() { return hipEventCreate(&ev); }
-    hipEvent_t release() { return std::exchange(ev, nullptr); }
-};
 
 // Bytes per element of the plan's planes
 size_t plane_bytes(const HostPlan &h) { return h.dtype != CLOUDY_F64 ? sizeof(float) : sizeof(double); }
@@ -298,7 +306,8 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_BOX_SSPRK33: return JIT_BOX;
     case OP_PARCEL_SSPRK33:
     case OP_PARCEL_RHS: return JIT_PARCEL;
-    case OP_TSIT5_ADAPTIVE: return JIT_ADAPTIVE;
+    case OP_TSIT5_ADAPTIVE:
+    case OP_TSIT5_SAVEAT: return JIT_ADAPTIVE;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
@@ -323,12 +332,24 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
         return ppl == 4 ? MAIN_ALLINF4 : ppl == 2 ? MAIN_ALLINF2 : MAIN_PPL1;
     }
     case JIT_BOX: return coal ? BOX_COALCOND : BOX_COND;
+    case JIT_ADAPTIVE: return r.op == OP_TSIT5_SAVEAT ? ADAPTIVE_SAVEAT : ADAPTIVE_PLAIN;
     case JIT_PARCEL: return r.op == OP_PARCEL_RHS ? (coal ? PARCEL_RHS_COAL : PARCEL_RHS) : (coal ? PARCEL_COALCOND : PARCEL_COND);
     case JIT_DIAG:
         return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
                : r.op == OP_COND      ? DIAG_COND_EVAP   : r.op == OP_NQ        ? DIAG_STANDARD_NQ : DIAG_COAL_INTS;
     default: return jit_is_column(u) && (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) ? COL_RHS : 0;
     }
+}
+
+// The save times of a cloudy_tsit5_adaptive_saveat call, stream-ordered into the plan's scratch (cloudy_plan::save_times says how
+// calls on several streams share it; the caller holds save_mu).  r.t_save is pageable host memory: the copy has left it when
+// hipMemcpyAsync returns.
+hipError_t upload_save_times(const cloudy_plan *plan, const LaunchReq &r) {
+    hipError_t e = hipSuccess;
+    if (!plan->save_times.p) e = plan->save_times.alloc(CLOUDY_MAX_SAVE_TIMES * sizeof(double));
+    if (e == hipSuccess) e = plan->save_done.ev ? hipStreamWaitEvent(r.stream, plan->save_done.ev, 0) : plan->save_done.create();
+    if (e == hipSuccess) e = hipMemcpyAsync(plan->save_times.p, r.t_save, r.n_save * sizeof(double), hipMemcpyHostToDevice, r.stream);
+    return e;
 }
 
 // One launch of a kernel compiled for the plan: the arguments by the tags of its signature, the grid by its workgroup size and the
@@ -349,6 +370,9 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
     const double *s_dev = r.s_dev;
     double *dt_dev = r.dt_dev, *t_dev = r.t_dev;
     int32_t *info_dev = r.info_dev;
+    size_t n_save = r.n_save;
+    const double *t_save = nullptr;
+    std::unique_lock<std::mutex> save_lock;   // (held from the upload of the save times to the event behind the kernel)
     double nq_cutoff = r.s_scalar / h.norms[1], nq_n0 = h.norms[0], nq_m0 = h.norms[1];
     void *args[kJitMaxArgs];
     for (int i = 0; i < k.n_args; ++i) switch (k.args[i]) {
@@ -377,12 +401,22 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
         case A_DT_DEV: args[i] = &dt_dev; break;
         case A_T_DEV: args[i] = &t_dev; break;
         case A_INFO_DEV: args[i] = &info_dev; break;
+        case A_NSAVE: args[i] = &n_save; break;
+        case A_TSAVE:
+            save_lock = std::unique_lock<std::mutex>(plan->save_mu);
+            if (hipError_t e = upload_save_times(plan, r)) return e;
+            t_save = reinterpret_cast<const double *>(plan->save_times.p);
+            args[i] = &t_save;
+            break;
+        case A_USAVE: args[i] = &out2; break;
         case A_NQ_CUTOFF: args[i] = &nq_cutoff; break;
         case A_NQ_N0: args[i] = &nq_n0; break;
         case A_NQ_M0: args[i] = &nq_m0; break;
         }
     const size_t per_wg = k.per_lane ? (size_t)k.block * k.per_lane : (size_t)k.block / r.nz * r.nz;
-    return hipModuleLaunchKernel(k.fn, (unsigned)((n + per_wg - 1) / per_wg), 1, 1, (unsigned)k.block, 1, 1, 0, r.stream, args, nullptr);
+    hipError_t e = hipModuleLaunchKernel(k.fn, (unsigned)((n + per_wg - 1) / per_wg), 1, 1, (unsigned)k.block, 1, 1, 0, r.stream, args, nullptr);
+    if (e == hipSuccess && save_lock.owns_lock()) e = hipEventRecord(plan->save_done.ev, r.stream);
+    return e;
 }
 
 int launch(const cloudy_plan *plan, const LaunchReq &r);
@@ -522,7 +556,7 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
                                                   "the plan (hiprtc)");
     if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS)
         return refuse_without_unit(plan, JIT_PARCEL, "the parcel kernels are compiled for the plan (hiprtc)");
-    if (r.op == OP_TSIT5_ADAPTIVE)
+    if (r.op == OP_TSIT5_ADAPTIVE || r.op == OP_TSIT5_SAVEAT)
         return refuse_without_unit(plan, JIT_ADAPTIVE, "cloudy_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and has no "
                                                        "ahead-of-time instance: cloudy_tsit5_steps steps such a plan with a fixed dt");
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
@@ -602,7 +636,7 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
             return fail(CLOUDY_EUNSUPPORTED, "the parcel kernel with coalescence is built for plans whose thresholds are all Inf (the "
                                              "ranked variant is not): pass CLOUDY_SRC_COND alone, or %s", kStaged);
     }
-    if (r.op == OP_TSIT5_ADAPTIVE) {
+    if (r.op == OP_TSIT5_ADAPTIVE || r.op == OP_TSIT5_SAVEAT) {   // (one kernel body: the same limits, the same words)
         if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
             return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_adaptive is not built for quadrature (NumericalCoalStyle) plans: "
                                              "cloudy_tsit5_steps steps them with a fixed dt");
@@ -1148,6 +1182,39 @@ int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const vo
     r.dt_dev = dt_dev;
     r.t_dev = t_dev;
     r.info_dev = info_dev;
+    return run(plan, r);
+}
+
+int cloudy_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, double t_span,
+                                 const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
+                                 size_t n_save, const double *t_save, void *u_save_dev) {
+    // the checks of the save times need no device either: before the plan is looked at (t_span is checked below; a save time
+    // compared with a t_span that is not finite or negative fails here or there, with an EINVAL either way)
+    if (n_save > CLOUDY_MAX_SAVE_TIMES)
+        return fail(CLOUDY_EINVAL, "n_save (%zu) must be <= CLOUDY_MAX_SAVE_TIMES (%d)", n_save, CLOUDY_MAX_SAVE_TIMES);
+    if (n_save > 0 && !t_save) return fail(CLOUDY_EINVAL, "t_save is NULL with n_save = %zu", n_save);
+    if (n_save > 0 && !u_save_dev) return fail(CLOUDY_EINVAL, "u_save_dev is NULL with n_save = %zu", n_save);
+    for (size_t j = 0; j < n_save; ++j) {
+        if (!std::isfinite(t_save[j]) || t_save[j] < 0.0 || t_save[j] > t_span)
+            return fail(CLOUDY_EINVAL, "t_save[%zu] (%g) must be finite and within [0, t_span] (t_span = %g)", j, t_save[j], t_span);
+        if (j > 0 && !(t_save[j] > t_save[j - 1]))
+            return fail(CLOUDY_EINVAL, "t_save must be strictly increasing: t_save[%zu] (%g) <= t_save[%zu] (%g)", j, t_save[j], j - 1,
+                        t_save[j - 1]);
+    }
+    if (n_save == 0)   // nothing to save: cloudy_tsit5_adaptive, its kernel
+        return cloudy_tsit5_adaptive(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, dt_dev, t_dev, info_dev, stream);
+    AdaptiveOpts c;
+    int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c);
+    if (rc) return rc;
+    LaunchReq r(OP_TSIT5_SAVEAT, n, ld, u_in_dev, u_out_dev, stream);
+    r.dt = t_span;
+    r.adaptive = &c;
+    r.dt_dev = dt_dev;
+    r.t_dev = t_dev;
+    r.info_dev = info_dev;
+    r.n_save = n_save;
+    r.t_save = t_save;
+    r.out2 = u_save_dev;
     return run(plan, r);
 }
 

@@ -101,6 +101,7 @@ extern "C" {
 #define CLOUDY_AOT_MAX_P 5
 #define CLOUDY_MAX_VEL 4    /* terms of the terminal-velocity power series */
 #define CLOUDY_MAX_MOMENTS (3 * CLOUDY_MAX_MODES)
+#define CLOUDY_MAX_SAVE_TIMES 4096 /* save times of one cloudy_tsit5_adaptive_saveat call */
 /* the sources cloudy_box_ssprk33_steps integrates (bits of its `sources` argument) */
 #define CLOUDY_SRC_COAL 1 /* collision-coalescence, rhs_coal! */
 #define CLOUDY_SRC_COND 2 /* condensation / evaporation, rhs_condensation! */
@@ -333,6 +334,42 @@ void cloudy_adaptive_opts_init(cloudy_adaptive_opts *opts);
 int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
                           double t_span, const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev,
                           void *stream);
+
+/* cloudy_tsit5_adaptive with DENSE OUTPUT: the same integration -- the same kernel body, controller and step sequence per parcel;
+ * u_out_dev, dt_dev, t_dev and info_dev have the bits cloudy_tsit5_adaptive gives -- and the state of every parcel at the n_save
+ * batch-wide times t_save.  A caller that needs the state at common times (output intervals, coupling sub-steps) gets them from one
+ * launch, and no step is clamped at a save time: where one looks does not change the steps taken.
+ *   interpolant  the free 4th-order interpolant of the Tsit5 pair over the seven stage derivatives of the accepted step t -> t + h that
+ *                holds the save time: u(t + th h) = u + h sum_i b_i(th) k_i, i = 1 .. 7, th = (t_save[j] - t) / h in (0, 1], with
+ *                  b1 = -1.0530884977290216 th (th - 1.3299890189751412)(th^2 - 1.4364028541716351 th + 0.7139816917074209)
+ *                  b2 =  0.1017 th^2 (th^2 - 2.1966568338249754 th + 1.2949852507374631)
+ *                  b3 =  2.490627285651252793 th^2 (th^2 - 2.38535645472061657 th + 1.57803468208092486)
+ *                  b4 = -16.54810288924490272 th^2 (th - 1.21712927295533244)(th - 0.61620406037800089)
+ *                  b5 =  47.37952196281928122 th^2 (th - 1.203071208372362603)(th - 0.658047292653547382)
+ *                  b6 = -34.87065786149660974 th^2 (th - 1.2)(th - 0.666666666666666667)
+ *                  b7 =  2.5 th^2 (th - 1)(th - 0.6)
+ *                It costs no evaluation of the right-hand side and is not seen by the controller: reltol and abstol bound the error
+ *                at the ends of the steps, and inside a step the error of the interpolant (O(h^5), as the local error of the
+ *                step) adds to it.
+ *   save times   t_save: a HOST pointer to n_save doubles, finite, within [0, t_span], strictly increasing, n_save <=
+ *                CLOUDY_MAX_SAVE_TIMES.  The library checks them and uploads them on `stream` into scratch the plan owns (allocated
+ *                by the first such call -- not inside a stream capture); calls on several streams are ordered among themselves by an
+ *                event.  n_save = 0 (t_save, u_save_dev may be NULL) is cloudy_tsit5_adaptive.
+ *   layout       u_save_dev: n_save * planes planes of leading dimension ld in the plan's plane type, planes = cloudy_plan_nmom:
+ *                snapshot j, plane p, parcel i at u_save_dev[(j * planes + p) * ld + i], physical units.  It must not overlap
+ *                u_in_dev or u_out_dev.  Columns n_parcels .. ld are not written.
+ *   NaN rule     a parcel that stops with status 1 or 2 has a quiet NaN in every plane of every snapshot with t_save[j] beyond the
+ *                time it reached; its other snapshots hold what it passed.
+ *   bit-equal    a snapshot at t_save[j] == 0 holds the bits of u_in_dev; a snapshot at t_save[j] == t_span those of u_out_dev
+ *                (of a parcel with status 0).  More generally a save time that is the end of an accepted step gets that step's
+ *                u_new, not the interpolant at th = 1.  t_span = 0: every snapshot is the input.
+ * Argument checks precede any device work, the plan last (CLOUDY_EINVAL, the message names the argument): n_save above the cap;
+ * t_save or u_save_dev NULL with n_save > 0; an entry of t_save that is not finite, below 0 or above t_span; entries that do not
+ * strictly increase; then those of cloudy_tsit5_adaptive.  Served and refused (CLOUDY_EUNSUPPORTED, nothing is written) exactly
+ * as cloudy_tsit5_adaptive: the second kernel of the same plan-time unit (cloudy_jit_dense_tsit5_*). */
+int cloudy_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
+                                 double t_span, const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev,
+                                 void *stream, size_t n_save, const double *t_save, void *u_save_dev);
 
 /* n_steps SSPRK33 steps of du/dt = [coal](u) + [cond](u; s, xi) with fixed dt, fused like cloudy_ssprk33_steps: a lane keeps its
  * parcel's state in registers over all stages and steps, the state is read once and written once per call and the parcel's

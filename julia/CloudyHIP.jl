@@ -413,6 +413,39 @@ function solve_tsit5_adaptive!(u, plan::Plan, t_span; reltol = 1e-6, abstol = 1e
 end
 
 """
+    solve_tsit5_adaptive_saveat!(u_save, u, plan, t_span, saveat; reltol = 1e-6, abstol = 1e-9, dt = 0.0, max_steps = 10000,
+                                 dt_dev = nothing, t_dev = nothing, info_dev = nothing, stream = nothing, sync = true)
+
+`solve_tsit5_adaptive!` with dense output (`cloudy_tsit5_adaptive_saveat`): the same steps, bit for bit, and the state of every
+parcel at the batch-wide times `saveat` (a HOST vector within [0, `t_span`], strictly increasing), from the free 4th-order
+interpolant of Tsit5 -- the `saveat` of `solve(prob, Tsit5(); saveat = ...)`.  `u_save`: a device array of the element type of
+`u` with room for `length(saveat) * nmom` planes of leading dimension ld; snapshot j (1-based), plane p of parcel i is
+`u_save[i + ld * ((j - 1) * nmom + p - 1)]`, e.g. an (ld, nmom, n_save) array.  A snapshot at 0 has the bits of the input, one
+at `t_span` those of `u`; a parcel that stopped early has NaN in the snapshots it did not reach (see `info_dev`).
+"""
+function solve_tsit5_adaptive_saveat!(u_save, u, plan::Plan, t_span, saveat; reltol = 1e-6, abstol = 1e-9, dt = 0.0,
+                                      max_steps = 10000, dt_dev = nothing, t_dev = nothing, info_dev = nothing, stream = nothing,
+                                      sync::Bool = true)
+    n, ld = batch_shape(u, plan.nmom)
+    s = stream === nothing ? current_stream() : stream
+    o = AdaptiveOpts()
+    o.reltol, o.abstol, o.dt_init, o.max_steps = reltol, abstol, dt, max_steps
+    ts = convert(Vector{Float64}, collect(saveat))
+    length(u_save) >= length(ts) * plan.nmom * ld || error("u_save holds fewer than length(saveat) * nmom planes of ld elements")
+    eltype(u_save) == eltype(u) || error("u_save must have the element type of u")
+    dptr = dt_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(dt_dev))
+    tptr = t_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(t_dev))
+    iptr = info_dev === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(info_dev))
+    GC.@preserve ts check(ccall((:cloudy_tsit5_adaptive_saveat, lib), Cint,
+                                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Ref{AdaptiveOpts}, Ptr{Cdouble},
+                                 Ptr{Cdouble}, Ptr{Int32}, Ptr{Cvoid}, Csize_t, Ptr{Cdouble}, Ptr{Cvoid}),
+                                plan.handle, n, ld, pointer(u), pointer(u), t_span, o, dptr, tptr, iptr, s, length(ts), pointer(ts),
+                                pointer(u_save)))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), s))
+    return u_save
+end
+
+"""
     solve_box_ssprk33!(u, plan, dt, n_steps, xi, s; coal = true, cond = true, stream = nothing, sync = true)
 
 `solve(ODEProblem(rhs!, u, tspan, p), SSPRK33(), dt = dt)` for `n_steps` fixed steps on the device with `rhs!` the sum of the

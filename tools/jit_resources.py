@@ -4,7 +4,9 @@ cloudy_jit_selfcheck compiles the plan's translation unit for gfx950, CLOUDY_HIP
 the figures are read from its metadata notes.
 usage: python tools/jit_resources.py [--keep DIR] cfg3b cfg4 moving4 cfg4q rainshaft_gamma_mixture rainshaft_single_gamma
        parcel_monodisperse parcel_gamma parcel_mixture ...
-       python tools/jit_resources.py --match adaptive --no-vel cfg2 cfg3a cfg3b adaptive_n4    (the adaptive Tsit5 unit alone)"""
+       python tools/jit_resources.py --match adaptive --no-vel cfg2 cfg3a cfg3b adaptive_n4    (the adaptive Tsit5 unit alone)
+       python tools/jit_resources.py --match adaptive,dense --no-vel adaptive_golovin cfg3a cfg3b adaptive_moving
+                                                           (both of its kernels: to t_span, and with snapshots at the save times)"""
 import argparse
 import ctypes as C
 import glob
@@ -22,7 +24,7 @@ READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keep", default="", help="directory for the dumped .hip / .co files (default: a temp dir)")
-    ap.add_argument("--match", default="", help="print only the kernels whose name contains this (e.g. adaptive)")
+    ap.add_argument("--match", default="", help="print only the kernels whose name contains one of these, comma-separated (e.g. adaptive,dense)")
     ap.add_argument("--no-vel", action="store_true", help="plans without a velocity term: the column units are not compiled")
     ap.add_argument("workloads", nargs="+")
     a = ap.parse_args()
@@ -70,6 +72,12 @@ def main():
             # four Gamma modes, Golovin b = 5 between every pair, thresholds Inf: the adaptive Tsit5 unit (cloudy_jit_adaptive_tsit5_*)
             # of a plan with nine live [4][3] arrays
             d, keep = pkg.Plan.make_desc([1] * 4, np.array([[2.220446049250313e-22, 5.0], [5.0, 0.0]]), (float("inf"),) * 4, bench.NORMS, 0)
+        elif name == "adaptive_golovin":
+            # one Gamma mode, Golovin b = 5, threshold Inf: the closed-form case of the adaptive Tsit5 tests
+            d, keep = pkg.Plan.make_desc([1], np.array([[0.0, 5.0], [5.0, 0.0]]), (float("inf"),), bench.NORMS, 0)
+        elif name == "adaptive_moving":
+            # cfg3a's matrix under MovingThreshold percentiles (0.9, 1.0): the moving plan of the adaptive Tsit5 tests
+            d, keep = pkg.Plan.make_desc([1, 1], bench.kernel_matrix(bench.workload_spec("cfg3a")), (0.9, 1.0), bench.NORMS, 1)
         else:
             spec = bench.workload_spec(name)
             # (one sedimentation velocity term, so that the fused column integrator is compiled as well)
@@ -81,7 +89,7 @@ def main():
             notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True).stdout
             for blk in notes.split("- .agpr_count")[1:]:
                 get = lambda key: (re.search(rf"\.{key}:\s*(\S+)", blk) or [None, "?"])[1]
-                if a.match and a.match not in get("name"):
+                if a.match and not any(m in get("name") for m in a.match.split(",")):
                     continue
                 print(f"{name}: {get('name')}: {get('vgpr_count')} VGPRs, {get('vgpr_spill_count')} spilled, "
                       f"scratch {get('private_segment_fixed_size')} B, LDS {get('group_segment_fixed_size')} B, "

@@ -26,6 +26,9 @@ every experiment switch of the library is an environment variable, so an A/B run
         cloudy_tsit5_adaptive on the cfg3a plan, n log-uniform over three decades: (a) the adaptive call, (b) cloudy_tsit5_steps at
         the fixed dt the densest parcels need for the same measured end-state error -- the caller's only alternative without (a);
         and the active-lane fraction of (a) from the info planes, sum(attempts) / sum over waves of 64 max(attempts)
+  python tools/timeit.py saveat [--parcels P] [--t-span T] [--reltol R]
+        cloudy_tsit5_adaptive_saveat on the batch of `adaptive`: cloudy_tsit5_adaptive itself, then the new entry point with n_save =
+        0, 1 and 16 equidistant save times (the last at t_span), and the algorithmic snapshot traffic per parcel
   python tools/timeit.py host [--parcels P]
         cloudy_coal_rhs_host on cfg3a: the PCIe-inclusive rate (host arrays staged through the device)
 
@@ -255,6 +258,33 @@ def cmd_adaptive(a, pkg, L):
           f"b/a {ms_b / ms_a:.2f} | active-lane fraction of (a) {lane_fraction:.3f}", flush=True)
 
 
+def cmd_saveat(a, pkg, L):
+    """ms per call on the batch of cmd_adaptive: cloudy_tsit5_adaptive, and cloudy_tsit5_adaptive_saveat with 0, 1 and 16 save times"""
+    n, t_span = a.parcels or 10_000_000, a.t_span
+    wl = bench.make_workload("cfg3a", 1)
+    plan = wl["coal_data"].plan(wl["dist_types"])
+    mom = bench.synth_moments(2, n, 7, degenerate_frac=0.0)
+    u0, out = pkg.DeviceArray.from_numpy(mom), pkg.DeviceArray.zeros(*mom.shape)
+    info, t_dev = pkg.DeviceArray.zeros(3, n, np.int32), pkg.DeviceArray.zeros(1, n)
+    opts = pkg._lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol = a.reltol
+    plain = lambda: pkg._lib.check(L.cloudy_tsit5_adaptive(plan.handle, n, n, u0.ptr, out.ptr, t_span, C.byref(opts), None, t_dev.ptr,   # noqa: E731
+                                                           info.ptr, None))
+    ms = {"cloudy_tsit5_adaptive": bench._sustained_ms(pkg, plain, min_reps=3)}
+    for n_save in (0, 1, 16):
+        times = (C.c_double * max(n_save, 1))(*[t_span * (j + 1) / n_save for j in range(n_save)])
+        saved = pkg.DeviceArray(max(n_save, 1) * plan.nmom, n)
+        call = lambda: pkg._lib.check(L.cloudy_tsit5_adaptive_saveat(plan.handle, n, n, u0.ptr, out.ptr, t_span, C.byref(opts), None,   # noqa: E731
+                                                                     t_dev.ptr, info.ptr, None, n_save, times, saved.ptr))
+        ms[f"saveat n_save = {n_save}"] = bench._sustained_ms(pkg, call, min_reps=3)
+        saved.free()
+    base = ms["cloudy_tsit5_adaptive"]
+    print(f"cfg3a, {n} parcels to t = {t_span:g}, reltol {a.reltol:g}: " + " | ".join(f"{k} {v:.3f} ms ({v / base:.3f} x)" for k, v in ms.items()) +
+          f" | snapshot traffic n_save x {plan.nmom} planes x 8 B = {plan.nmom * 8} B per parcel and save time (state in + out: "
+          f"{2 * plan.nmom * 8} B)", flush=True)
+
+
 def cmd_box(a, pkg, L):
     """ms per call of S steps: (a) cloudy_ssprk33_steps, (b) / (c) cloudy_box_ssprk33_steps with COAL | COND / COND, (d) the same
     steps stage by stage: two right-hand-side launches and the update on the planes (torch, on the same stream) per stage"""
@@ -424,11 +454,16 @@ def main():
     ad.add_argument("--parcels", type=int, default=0)
     ad.add_argument("--t-span", type=float, default=5e-3)
     ad.add_argument("--reltol", type=float, default=1e-6)
+    sv = sub.add_parser("saveat")
+    sv.add_argument("--parcels", type=int, default=0)
+    sv.add_argument("--t-span", type=float, default=5e-3)
+    sv.add_argument("--reltol", type=float, default=1e-6)
     hh = sub.add_parser("host")
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
     {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "adaptive": cmd_adaptive,
+     "saveat": cmd_saveat,
      "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
