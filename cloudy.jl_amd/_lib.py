@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("CLOUDY_HIP_LIB") or os.path.join(_HERE, "libcloudy_hi
 MAX_MODES, MAX_P, MAX_VEL = 8, 8, 4
 OK, EINVAL, ENOTSYMMETRIC, EHIP, ENOMEM, EUNSUPPORTED, ENODEVICE, ECOMM = 0, -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
-SRC_COAL, SRC_COND = 1, 2  # CLOUDY_SRC_*: the sources of cloudy_box_ssprk33_steps
+SRC_COAL, SRC_COND = 1, 2  # CLOUDY_SRC_*: the sources of cloudy_box_ssprk33_steps and cloudy_box_tsit5_adaptive
 
 
 class CloudyError(RuntimeError):
@@ -88,6 +88,8 @@ SYMBOLS = {
     "cloudy_tsit5_adaptive": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp]),
     "cloudy_tsit5_adaptive_saveat": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp, _sz, _dp, _vp]),
     "cloudy_box_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, _i, _vp]),
+    "cloudy_box_tsit5_adaptive": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, C.POINTER(AdaptiveOptsC),
+                                       _vp, _vp, _vp, _vp, _sz, _dp, _vp]),
     "cloudy_parcel_params_init": (None, [C.POINTER(ParcelParamsC)]),
     "cloudy_parcel_rhs": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(ParcelParamsC), _i, _vp, _vp]),
     "cloudy_parcel_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.POINTER(ParcelParamsC), C.c_double, _i, _vp]),

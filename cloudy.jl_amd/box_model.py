@@ -241,3 +241,68 @@ def solve_box_ssprk33(par, u, dt, n_steps, xi, s, coal=True, cond=True, out=None
     _lib.check(_lib.lib().cloudy_box_ssprk33_steps(plan.handle, n, ld, uptr, optr, sources, sptr, sval, float(xi), float(dt),
                                                   int(n_steps), stream))
     return o
+
+
+def solve_box_tsit5_adaptive(par, u, t_span, xi, s, coal=True, cond=True, saveat=None, reltol=1e-6, abstol=1e-9, dt=None,
+                             max_steps=10000, out=None, dt_dev=None, info=False, stream=None, coal_type=None):
+    """Every parcel of `u` from t = 0 to t = t_span with adaptive Tsit5 under a step-size controller of its own, the right-hand
+    side the sum of the selected sources (cloudy_box_tsit5_adaptive): rhs_coal! (`coal`) and rhs_condensation!(dm, m, par, s)
+    (`cond`) -- the error-controlled counterpart of solve_box_ssprk33.  `xi` and `s` as solve_box_ssprk33 takes them (`s`: a float
+    or an (1, n) fp64 device array, one supersaturation per parcel); the controller, `reltol`, `abstol`, `dt`, `max_steps`,
+    `dt_dev`, `out` and `info` as solve_tsit5_adaptive.  `saveat` (None: no snapshots): host times as solve_tsit5_adaptive_saveat
+    takes them; the snapshots come back as it returns them.  Returns what solve_tsit5_adaptive returns -- the state, or with
+    info=True (accepted, rejected, status, t_reached) -- and with `saveat` what solve_tsit5_adaptive_saveat returns: the snapshots,
+    or (snapshots, accepted, rejected, status, t_reached).  With info=True a parcel that did not reach t_span raises the
+    RuntimeError of solve_tsit5_adaptive, after the call.  `coal_type`: as solve_ssprk33; a NumericalCoalStyle plan serves cond
+    alone."""
+    import ctypes as C
+
+    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
+        raise ValueError("Invalid coal style!")
+    sources = (_lib.SRC_COAL if coal else 0) | (_lib.SRC_COND if cond else 0)
+    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
+    uptr, planes, n, ld = as_device(u)
+    o = out if out is not None else u
+    optr, oplanes, on, old = as_device(o)
+    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
+        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    if hasattr(s, "data_ptr") or isinstance(s, DeviceArray):
+        sptr, splanes, sn, _ = as_device(s)
+        if splanes != 1 or sn != n or dtype_code(s) != 0:   # (the kernel reads n doubles, whatever the plan's plane type)
+            raise ValueError("s must be a float or an (1, n) fp64 device array")
+        sval = 0.0
+    else:
+        sptr, sval = None, float(s)
+    dptr = None
+    if dt_dev is not None:
+        dptr, dplanes, dn, _ = as_device(dt_dev)
+        if dplanes != 1 or dn != n or dtype_code(dt_dev) != 0:
+            raise ValueError("dt_dev must be an (1, n) fp64 device array")
+    n_save, times, saved = 0, None, None
+    if saveat is not None:
+        times = np.ascontiguousarray(np.atleast_1d(np.asarray(saveat, dtype=np.float64)))
+        if times.ndim != 1:
+            raise ValueError("saveat must be a sequence of times")
+        n_save = int(times.size)
+        saved = DeviceArray(n_save * planes, ld, dtype=np.float32 if dtype_code(u) else np.float64)
+    L = _lib.lib()
+    opts = _lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
+    t_arr = DeviceArray.zeros(1, n) if info else None
+    i_arr = DeviceArray.zeros(3, ld, dtype=np.int32) if info else None
+    _lib.check(L.cloudy_box_tsit5_adaptive(plan.handle, n, ld, uptr, optr, sources, sptr, sval, float(xi), float(t_span), C.byref(opts),
+                                           dptr, t_arr.ptr if info else None, i_arr.ptr if info else None, stream, n_save,
+                                           times.ctypes.data_as(C.POINTER(C.c_double)) if n_save else None,
+                                           saved.ptr if n_save else None))
+    if not info:
+        return o if saveat is None else saved
+    _lib.check(L.cloudy_stream_synchronize(stream))
+    counts = i_arr.to_numpy()[:, :n]
+    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise RuntimeError(f"solve_box_tsit5_adaptive: {bad.size} of {n} parcels did not reach t_span; the first is parcel "
+                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
+    res = (accepted, rejected, status, t_arr.to_numpy()[0])
+    return res if saveat is None else (saved,) + res

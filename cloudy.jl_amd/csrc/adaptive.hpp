@@ -94,25 +94,35 @@ constexpr double kBeta1 = 7.0 / 50.0, kBeta2 = 2.0 / 25.0, kSafety = 9.0 / 10.0 
 __device__ __forceinline__ bool is_finite(double x) { return fabs(x) < INFINITY; }   // (false for NaN)
 }  // namespace adaptive
 
-// u_in / u_out: the plan's planes (they may alias); dt_dev (in/out, one double per parcel: the next proposed dt), t_dev (out: the
-// time reached) and info_dev (out, int32 [3][ld]: accepted, rejected, status) may each be null.  SAVE: n_save, t_save and u_save
-// (n_save x planes planes of leading dimension ld, aliasing neither u_in nor u_out) as above; without it they are not read.
-template <int N, int P, int MODE, typename TIO, bool SPEC = false, int BS = kBlock, bool SAVE = false>
-__device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restrict__ Ag, const double *__restrict__ nodes, size_t n,
-                                                    size_t ld, const TIO *u_in, TIO *u_out, double t_span, AdaptiveOpts o,
-                                                    double *dt_dev, double *t_dev, int *info_dev, size_t n_save = 0,
-                                                    const double *__restrict__ t_save = nullptr, TIO *__restrict__ u_save = nullptr) {
+// The loop itself -- the seven-stage step, the error estimate, the controller, the FSAL hand-over, the snapshots and the final
+// store -- for any right-hand side: rhs(live, state, deriv) writes d(state)/dt into deriv, in the units of the state.
+//   RANKED = false: a plain per-lane loop; the state is kept in normalised units (mom ./ norms) between load and store and rhs
+//     sees it so; a lane without a parcel returns at once and `live` is always true.
+//   RANKED = true: rhs holds workgroup barriers, so every lane of the workgroup makes the same sequence of calls and the loop
+//     runs while ANY lane is active; `live` = the lane's result is wanted (false: a lane without a parcel or one that has
+//     finished, which only sits through the barriers); the state is physical.
+// A: the plan constants the loop itself reads (off, np, norm, inv_norm).  u_in / u_out: the plan's planes (they may alias);
+// dt_dev (in/out, one double per parcel: the next proposed dt), t_dev (out: the time reached) and info_dev (out, int32 [3][ld]:
+// accepted, rejected, status) may each be null.  SAVE: n_save, t_save and u_save (n_save x planes planes of leading dimension
+// ld, aliasing neither u_in nor u_out) as above; without it they are not read.
+// KEEP0: the right-hand side leaves the number plane of every mode alone (condensation without coalescence: dM0/dt is zero
+// identically), so u_out and every snapshot get that plane's value as loaded, not its round trip through the normalised units.
+template <int N, int P, typename TIO, bool RANKED, int BS, bool SAVE, bool KEEP0 = false, typename RHS>
+__device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t n, size_t ld, const TIO *u_in, TIO *u_out,
+                                                    double t_span, AdaptiveOpts o, double *dt_dev, double *t_dev, int *info_dev,
+                                                    size_t n_save, const double *__restrict__ t_save, TIO *__restrict__ u_save,
+                                                    RHS rhs_of) {
     using namespace tsit5;
-    const KArgs<N, P> &A = *Ag;
     const size_t i = (size_t)blockIdx.x * BS + threadIdx.x;
     const bool valid = i < n;
-    constexpr bool kRanked = MODE != MODE_ALLINF;
+    constexpr bool kRanked = RANKED;
     constexpr bool kNormalisedState = !kRanked;  // see rhs_normalised
     // SAVE: snapshot js of this lane's parcel from v (the units of the state) as the final store writes u -- physical units, the
     // planes a mode has
     size_t planes = 0;
 #pragma unroll
     for (int m = 0; m < N; ++m) planes += A.np[m] == 3 ? 3 : 2;
+    double number_in[N];   // KEEP0: the number planes as loaded
     auto snapshot = [&](size_t js, const double (&v)[N][3]) {
 #pragma unroll
         for (int m = 0; m < N; ++m)
@@ -121,6 +131,8 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
                 if (q < 2 || A.np[m] == 3) {
                     double x = v[m][q];
                     if (kNormalisedState) x *= A.norm[3 * m + q];
+                    if constexpr (KEEP0)
+                        if (q == 0) x = number_in[m];
                     u_save[(js * planes + (size_t)(A.off[m] + q)) * ld + i] = (TIO)x;
                 }
     };
@@ -152,6 +164,7 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
         u[m][1] = valid ? (double)u_in[(size_t)(off + 1) * ld + i] : 0.0;
         u[m][2] = (valid && A.np[m] == 3) ? (double)u_in[(size_t)(off + 2) * ld + i] : 0.0;
         count += A.np[m] == 3 ? 3 : 2;   // (the planes a mode has: the third slot of a two-moment mode is padding)
+        if constexpr (KEEP0) number_in[m] = u[m][0];
         if constexpr (SAVE)   // a save time 0: the values as loaded, before any normalisation
             if (save0) {
 #pragma unroll
@@ -165,17 +178,9 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
         }
     }
     const double n_moms = (double)count;
-    // the plan constants through an opaque zero offset per RHS evaluation (see ssprk33_body); none when compiled for the plan.
-    // live: the lane's result is wanted (thresholded plans: every lane calls, idle ones sit through the ranking's barriers)
+    // live: the lane's result is wanted (ranked: every lane calls, idle ones sit through the ranking's barriers)
     bool active = valid;
-    auto rhs = [&](const double (&state)[N][3], double (&deriv)[N][3]) {
-        size_t oz = 0;
-        if (!SPEC) asm volatile("" : "+s"(oz));
-        if (kNormalisedState)
-            rhs_normalised<N, P, SPEC>(*(Ag + oz), state, deriv);
-        else
-            rhs_physical<N, P, MODE, SPEC, BS>(*(Ag + oz), nodes, valid && active, state, deriv);
-    };
+    auto rhs = [&](const double (&state)[N][3], double (&deriv)[N][3]) { rhs_of(valid && active, state, deriv); };
     double k1[N][3], k2[N][3], k3[N][3], k4[N][3], k5[N][3], k6[N][3], w[N][3];
     // where the error combination and k7 go: k2 and k3, which are dead by then -- SAVE keeps k1 .. k7 for the interpolant and
     // gives both an array of its own (not touched, and so not there, without it)
@@ -331,6 +336,7 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
 #pragma unroll
             for (int q = 0; q < 3; ++q) u[m][q] *= A.norm[3 * m + q];
         }
+        if constexpr (KEEP0) u[m][0] = number_in[m];
         u_out[(size_t)(off + 0) * ld + i] = (TIO)u[m][0];
         u_out[(size_t)(off + 1) * ld + i] = (TIO)u[m][1];
         if (A.np[m] == 3) u_out[(size_t)(off + 2) * ld + i] = (TIO)u[m][2];
@@ -338,6 +344,27 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
     if (dt_dev) dt_dev[i] = dt;
     if (t_dev) t_dev[i] = t;
     if (info_dev) info_dev[i] = n_acc, info_dev[ld + i] = n_rej, info_dev[2 * ld + i] = status;
+}
+
+// cloudy_tsit5_adaptive / cloudy_tsit5_adaptive_saveat: the loop on the coalescence right-hand side of the plan -- rhs_normalised
+// where the thresholds are all Inf, rhs_physical (ranked) otherwise.
+template <int N, int P, int MODE, typename TIO, bool SPEC = false, int BS = kBlock, bool SAVE = false>
+__device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restrict__ Ag, const double *__restrict__ nodes, size_t n,
+                                                    size_t ld, const TIO *u_in, TIO *u_out, double t_span, AdaptiveOpts o,
+                                                    double *dt_dev, double *t_dev, int *info_dev, size_t n_save = 0,
+                                                    const double *__restrict__ t_save = nullptr, TIO *__restrict__ u_save = nullptr) {
+    constexpr bool kRanked = MODE != MODE_ALLINF;
+    // the plan constants through an opaque zero offset per RHS evaluation (see ssprk33_body); none when compiled for the plan
+    tsit5_adaptive_loop<N, P, TIO, kRanked, BS, SAVE>(
+        *Ag, n, ld, u_in, u_out, t_span, o, dt_dev, t_dev, info_dev, n_save, t_save, u_save,
+        [&](bool live, const double (&state)[N][3], double (&deriv)[N][3]) {
+            size_t oz = 0;
+            if (!SPEC) asm volatile("" : "+s"(oz));
+            if (!kRanked)
+                rhs_normalised<N, P, SPEC>(*(Ag + oz), state, deriv);
+            else
+                rhs_physical<N, P, MODE, SPEC, BS>(*(Ag + oz), nodes, live, state, deriv);
+        });
 }
 
 }  // namespace cloudy

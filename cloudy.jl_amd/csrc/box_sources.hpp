@@ -19,6 +19,57 @@ namespace cloudy {
 enum { SRC_COAL = 1, SRC_COND = 2 };  // CLOUDY_SRC_* of include/cloudy_hip.h
 #endif
 
+// One evaluation of the box's right-hand side for the lane's parcel, f = [coal](u) + [cond](u; sv) by SRC as above: what a stage
+// of box_ssprk33_body and a stage of the adaptive loop (adaptive_box.hpp) both call.  u and f are in the units the instance keeps
+// its state in: physical where the parcels are ranked (SRC_COAL with a threshold), normalised otherwise.  Ranked: every lane of the
+// workgroup calls it (coal_ints_ranked_impl's barriers), `valid` = the lane's result is wanted; the condensation term sits
+// after the barriers.  Otherwise nodes and valid are not read.
+template <int N, int P, int MODE, bool SPEC, int BS, int SRC>
+__device__ __forceinline__ void box_rhs(const KArgs<N, P> &As, const double *__restrict__ nodes, bool valid, double coef, double sv,
+                                        const double (&u)[N][3], double (&f)[N][3]) {
+    static_assert((SRC & SRC_COND) != 0 && (SRC & ~(SRC_COAL | SRC_COND)) == 0, "SRC_COND or SRC_COAL | SRC_COND");
+    constexpr bool kCoal = (SRC & SRC_COAL) != 0;
+    constexpr bool kRanked = kCoal && MODE != MODE_ALLINF;
+    double nn[N], th[N], kk[N];
+#pragma unroll
+    for (int m = 0; m < N; ++m) {
+        if (!kRanked) {
+            invert_closure(As.dist_type[m], u[m][0], u[m][1], u[m][2], As.kmin, As.kmax, nn[m], th[m], kk[m]);
+        } else {
+            const double m0 = div_by_const(u[m][0], As.norm[3 * m + 0], As.inv_norm[3 * m + 0]);
+            const double m1 = div_by_const(u[m][1], As.norm[3 * m + 1], As.inv_norm[3 * m + 1]);
+            const double m2 = div_by_const(u[m][2], As.norm[3 * m + 2], As.inv_norm[3 * m + 2]);
+            invert_closure(As.dist_type[m], m0, m1, m2, As.kmin, As.kmax, nn[m], th[m], kk[m]);
+        }
+    }
+    if constexpr (!kCoal) {
+        cond_evap_parcel<N, P, false>(As, coef, sv, nn, th, kk, f);
+    } else if constexpr (!kRanked) {
+        // (the condensation term first: its 2N values are fewer to keep across the tensor contractions than the
+        // 3N closure parameters)
+        double fc[N][3], acc[N][3];
+        cond_evap_parcel<N, P, false>(As, coef, sv, nn, th, kk, fc);
+        coal_ints_parcel<N, P, MODE_ALLINF, false, SPEC>(As, nullptr, nn, th, kk, acc);
+#pragma unroll
+        for (int m = 0; m < N; ++m) {
+            f[m][0] = acc[m][0];  // (condensation leaves the number alone)
+            f[m][1] = acc[m][1] + fc[m][1];
+            f[m][2] = (As.np[m] == 3) ? acc[m][2] + fc[m][2] : 0.0;
+        }
+    } else {
+        double fc[N][3], acc[N][3];
+        double (*rows)[BS];
+        coal_ints_ranked_impl<N, P, MODE, SPEC, BS, true>(As, nodes, valid, nn, th, kk, acc, rows);
+        cond_evap_parcel<N, P, true>(As, coef, sv, nn, th, kk, fc);  // (n, theta, k) as the ranking's LDS rows hold them
+#pragma unroll
+        for (int m = 0; m < N; ++m) {
+            f[m][0] = acc[m][0] * As.out_scale[3 * m + 0];
+            f[m][1] = acc[m][1] * As.out_scale[3 * m + 1] + fc[m][1];
+            f[m][2] = (As.np[m] == 3) ? acc[m][2] * As.out_scale[3 * m + 2] + fc[m][2] : 0.0;
+        }
+    }
+}
+
 // n_steps SSPRK33 steps of du/dt = [coal](u) + [cond](u; s) for one parcel per lane; SRC: SRC_COND or SRC_COAL | SRC_COND
 // (coalescence alone is ssprk33_body).  State and u_prev stay in registers over all stages and steps, the state is read once
 // and written once, the parcel's supersaturation is loaded once; the update formulas are OrdinaryDiffEq's, as in ssprk33_body.
@@ -68,46 +119,7 @@ __device__ __forceinline__ void box_ssprk33_body(const KArgs<N, P> *__restrict__
             size_t opaque_zero = 0;
             if (!SPEC) asm volatile("" : "+s"(opaque_zero));
             const KArgs<N, P> &As = *(Ag + opaque_zero);
-            {
-                double nn[N], th[N], kk[N];
-#pragma unroll
-                for (int m = 0; m < N; ++m) {
-                    if (kNormalisedState) {
-                        invert_closure(As.dist_type[m], u[m][0], u[m][1], u[m][2], As.kmin, As.kmax, nn[m], th[m], kk[m]);
-                    } else {
-                        const double m0 = div_by_const(u[m][0], As.norm[3 * m + 0], As.inv_norm[3 * m + 0]);
-                        const double m1 = div_by_const(u[m][1], As.norm[3 * m + 1], As.inv_norm[3 * m + 1]);
-                        const double m2 = div_by_const(u[m][2], As.norm[3 * m + 2], As.inv_norm[3 * m + 2]);
-                        invert_closure(As.dist_type[m], m0, m1, m2, As.kmin, As.kmax, nn[m], th[m], kk[m]);
-                    }
-                }
-                if constexpr (!kCoal) {
-                    cond_evap_parcel<N, P, false>(As, coef, sv, nn, th, kk, f);
-                } else if constexpr (!kRanked) {
-                    // (the condensation term first: its 2N values are fewer to keep across the tensor contractions than the
-                    // 3N closure parameters)
-                    double fc[N][3], acc[N][3];
-                    cond_evap_parcel<N, P, false>(As, coef, sv, nn, th, kk, fc);
-                    coal_ints_parcel<N, P, MODE_ALLINF, false, SPEC>(As, nullptr, nn, th, kk, acc);
-#pragma unroll
-                    for (int m = 0; m < N; ++m) {
-                        f[m][0] = acc[m][0];  // (condensation leaves the number alone)
-                        f[m][1] = acc[m][1] + fc[m][1];
-                        f[m][2] = (As.np[m] == 3) ? acc[m][2] + fc[m][2] : 0.0;
-                    }
-                } else {
-                    double fc[N][3], acc[N][3];
-                    double (*rows)[BS];
-                    coal_ints_ranked_impl<N, P, MODE, SPEC, BS, true>(As, nodes, valid, nn, th, kk, acc, rows);
-                    cond_evap_parcel<N, P, true>(As, coef, sv, nn, th, kk, fc);  // (n, theta, k) as the ranking's LDS rows hold them
-#pragma unroll
-                    for (int m = 0; m < N; ++m) {
-                        f[m][0] = acc[m][0] * As.out_scale[3 * m + 0];
-                        f[m][1] = acc[m][1] * As.out_scale[3 * m + 1] + fc[m][1];
-                        f[m][2] = (As.np[m] == 3) ? acc[m][2] * As.out_scale[3 * m + 2] + fc[m][2] : 0.0;
-                    }
-                }
-            }
+            box_rhs<N, P, MODE, SPEC, BS, SRC>(As, nodes, valid, coef, sv, u, f);
             // OrdinaryDiffEq SSPRK33: u = uprev + dt k;  u = (3 uprev + u + dt k)/4;  u = (uprev + 2u + 2dt k)/3
             if (stage == 0) {
 #pragma unroll

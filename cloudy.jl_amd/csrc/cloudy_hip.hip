@@ -222,6 +222,17 @@ int check_steps(int n_steps, double dt) {
     if (n_steps < 0 || !(dt == dt)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0 and dt not NaN");
     return CLOUDY_OK;
 }
+// ... the sources of a box call ...
+int check_sources(int sources) {
+    if (sources < 1 || sources > (SRC_COAL | SRC_COND))
+        return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COAL, CLOUDY_SRC_COND or both", sources);
+    return CLOUDY_OK;
+}
+int check_box_sources(int sources, double xi) {   // (the supersaturation, of either sign, is the caller's)
+    if (int rc = check_sources(sources)) return rc;
+    if (!(xi == xi)) return fail(CLOUDY_EINVAL, "xi must not be NaN");
+    return CLOUDY_OK;
+}
 // ... the batch of a column call (n = nz * n_columns cells) and its grid ...
 int check_columns(const cloudy_plan *plan, size_t nz, size_t n, size_t ld, const void *a, const void *b, double dz) {
     if (int rc = check_batch(plan, n, ld, a, b)) return rc;
@@ -308,6 +319,8 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_PARCEL_RHS: return JIT_PARCEL;
     case OP_TSIT5_ADAPTIVE:
     case OP_TSIT5_SAVEAT: return JIT_ADAPTIVE;
+    case OP_BOX_TSIT5_ADAPTIVE:
+    case OP_BOX_TSIT5_SAVEAT: return JIT_BOX_ADAPTIVE;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
@@ -333,6 +346,7 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
     }
     case JIT_BOX: return coal ? BOX_COALCOND : BOX_COND;
     case JIT_ADAPTIVE: return r.op == OP_TSIT5_SAVEAT ? ADAPTIVE_SAVEAT : ADAPTIVE_PLAIN;
+    case JIT_BOX_ADAPTIVE: return (coal ? BOXAD_COALCOND : BOXAD_COND) + (r.op == OP_BOX_TSIT5_SAVEAT ? 1 : 0);
     case JIT_PARCEL: return r.op == OP_PARCEL_RHS ? (coal ? PARCEL_RHS_COAL : PARCEL_RHS) : (coal ? PARCEL_COALCOND : PARCEL_COND);
     case JIT_DIAG:
         return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
@@ -559,6 +573,10 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
     if (r.op == OP_TSIT5_ADAPTIVE || r.op == OP_TSIT5_SAVEAT)
         return refuse_without_unit(plan, JIT_ADAPTIVE, "cloudy_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and has no "
                                                        "ahead-of-time instance: cloudy_tsit5_steps steps such a plan with a fixed dt");
+    if (r.op == OP_BOX_TSIT5_ADAPTIVE || r.op == OP_BOX_TSIT5_SAVEAT)
+        return refuse_without_unit(plan, JIT_BOX_ADAPTIVE, "cloudy_box_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and "
+                                                           "has no ahead-of-time instance: step such a plan stage by stage with "
+                                                           "cloudy_coal_rhs and cloudy_cond_evap");
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
@@ -606,8 +624,7 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
         return fail(CLOUDY_EUNSUPPORTED, "cloudy_rainshaft_cond_* serve CLOUDY_F64, CLOUDY_F64_RELAXED and CLOUDY_F32 plans (the fused "
                                          "integrators keep the state in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode)");
     if (r.op == OP_BOX_SSPRK33) {
-        if (r.sources < 1 || r.sources > (SRC_COAL | SRC_COND))
-            return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COAL, CLOUDY_SRC_COND or both", r.sources);
+        if (int rc = check_sources(r.sources)) return rc;
         if (r.n_steps < 0 || !(r.dt == r.dt) || !(r.coef == r.coef)) return fail(CLOUDY_EINVAL, "n_steps must be >= 0, dt and xi not NaN");
         if (plan->h.dtype == CLOUDY_F32_FAST)
             return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_ssprk33_steps serves CLOUDY_F64 and CLOUDY_F32 plans (the fused integrators keep "
@@ -622,6 +639,16 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
             coal.n_steps = r.n_steps;
             return run(plan, coal);
         }
+    }
+    if (r.op == OP_BOX_TSIT5_ADAPTIVE || r.op == OP_BOX_TSIT5_SAVEAT) {   // (sources: COND or COAL | COND; the entry point forwards COAL)
+        static const char kStaged[] = "step such a plan stage by stage with cloudy_coal_rhs and cloudy_cond_evap";
+        if (plan->h.dtype == CLOUDY_F32_FAST)
+            return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_tsit5_adaptive serves CLOUDY_F64, CLOUDY_F64_RELAXED and CLOUDY_F32 plans (state and "
+                                             "step control in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode): create "
+                                             "a CLOUDY_F32 plan, or %s", kStaged);
+        if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL && (r.sources & SRC_COAL))
+            return fail(CLOUDY_EUNSUPPORTED, "the combined coalescence + condensation kernel is not built for quadrature "
+                                             "(NumericalCoalStyle) plans: %s, or pass CLOUDY_SRC_COND alone", kStaged);
     }
     if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS) {
         static const char kStaged[] = "step such a parcel stage by stage: cloudy_cond_evap (and cloudy_coal_rhs) per stage with the "
@@ -1149,9 +1176,11 @@ void cloudy_adaptive_opts_init(cloudy_adaptive_opts *o) {
     o->max_steps = 10000;
 }
 
-// the checks of cloudy_tsit5_adaptive that need no device.  The plan comes last (parcel_request says why).
+// the checks of cloudy_tsit5_adaptive that need no device.  The plan comes last (parcel_request says why): `more` -- the checks an
+// entry point has beyond these, nullptr: none -- runs between the last of these and the plan's.
 static int adaptive_request(const cloudy_plan *plan, size_t n, size_t ld, const void *in, void *out, double t_span,
-                            const cloudy_adaptive_opts *o, AdaptiveOpts &c) {
+                            const cloudy_adaptive_opts *o, AdaptiveOpts &c, int (*more)(int, double) = nullptr, int more_i = 0,
+                            double more_d = 0.0) {
     if (!o) return fail(CLOUDY_EINVAL, "opts is NULL");
     if (o->struct_size != sizeof(cloudy_adaptive_opts))
         return fail(CLOUDY_EINVAL, "opts.struct_size (%u) is not sizeof(cloudy_adaptive_opts) (%zu): call cloudy_adaptive_opts_init",
@@ -1168,6 +1197,8 @@ static int adaptive_request(const cloudy_plan *plan, size_t n, size_t ld, const 
     if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
     if (n > 0 && (!in || !out)) return fail(CLOUDY_EINVAL, "device buffer is NULL");
     c = {o->reltol, o->abstol, o->dt_init, (int)o->max_steps};
+    if (more)
+        if (int rc = more(more_i, more_d)) return rc;
     return check_batch(plan, n, ld, in, out);
 }
 
@@ -1185,11 +1216,10 @@ int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const vo
     return run(plan, r);
 }
 
-int cloudy_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, double t_span,
-                                 const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
-                                 size_t n_save, const double *t_save, void *u_save_dev) {
-    // the checks of the save times need no device either: before the plan is looked at (t_span is checked below; a save time
-    // compared with a t_span that is not finite or negative fails here or there, with an EINVAL either way)
+// the checks of the save times of a call with dense output: they need no device either and precede the plan's (t_span is
+// checked after them; a save time compared with a t_span that is not finite or negative fails here or there, with an EINVAL
+// either way)
+static int check_save_times(size_t n_save, const double *t_save, const void *u_save_dev, double t_span) {
     if (n_save > CLOUDY_MAX_SAVE_TIMES)
         return fail(CLOUDY_EINVAL, "n_save (%zu) must be <= CLOUDY_MAX_SAVE_TIMES (%d)", n_save, CLOUDY_MAX_SAVE_TIMES);
     if (n_save > 0 && !t_save) return fail(CLOUDY_EINVAL, "t_save is NULL with n_save = %zu", n_save);
@@ -1201,6 +1231,13 @@ int cloudy_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t n, size_t ld, c
             return fail(CLOUDY_EINVAL, "t_save must be strictly increasing: t_save[%zu] (%g) <= t_save[%zu] (%g)", j, t_save[j], j - 1,
                         t_save[j - 1]);
     }
+    return CLOUDY_OK;
+}
+
+int cloudy_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, double t_span,
+                                 const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
+                                 size_t n_save, const double *t_save, void *u_save_dev) {
+    if (int rc = check_save_times(n_save, t_save, u_save_dev, t_span)) return rc;
     if (n_save == 0)   // nothing to save: cloudy_tsit5_adaptive, its kernel
         return cloudy_tsit5_adaptive(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, dt_dev, t_dev, info_dev, stream);
     AdaptiveOpts c;
@@ -1229,6 +1266,33 @@ int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const
     r.s_dev = s_dev;
     r.dt = dt;
     r.n_steps = n_steps;
+    return run(plan, r);
+}
+
+int cloudy_box_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, int sources,
+                              const double *s_dev, double s, double xi, double t_span, const cloudy_adaptive_opts *opts,
+                              double *dt_dev, double *t_dev, int32_t *info_dev, void *stream, size_t n_save, const double *t_save,
+                              void *u_save_dev) {
+    // the checks of cloudy_tsit5_adaptive_saveat in its order, then the box's, then the plan
+    if (int rc = check_save_times(n_save, t_save, u_save_dev, t_span)) return rc;
+    AdaptiveOpts c;
+    if (int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c, check_box_sources, sources, xi)) return rc;
+    if (sources == SRC_COAL)   // coalescence alone is cloudy_tsit5_adaptive[_saveat]: the same request, the same kernel
+        return cloudy_tsit5_adaptive_saveat(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, dt_dev, t_dev, info_dev, stream, n_save,
+                                            t_save, u_save_dev);
+    LaunchReq r(n_save > 0 ? OP_BOX_TSIT5_SAVEAT : OP_BOX_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
+    r.sources = sources;
+    r.coef = cond_coef(plan, xi);
+    r.s_scalar = s;
+    r.s_dev = s_dev;
+    r.dt = t_span;
+    r.adaptive = &c;
+    r.dt_dev = dt_dev;
+    r.t_dev = t_dev;
+    r.info_dev = info_dev;
+    r.n_save = n_save;
+    r.t_save = t_save;
+    r.out2 = u_save_dev;
     return run(plan, r);
 }
 

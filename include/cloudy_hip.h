@@ -392,6 +392,38 @@ int cloudy_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t n_parcels, size
 int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
                              int sources, const double *s_dev, double s, double xi, double dt, int n_steps, void *stream);
 
+/* Per-parcel ADAPTIVE Tsit5 of the box with condensation: du/dt = [coal](u) + [cond](u; s, xi) from t = 0 to t = t_span, every
+ * parcel under a step-size controller of its own (csrc/adaptive_box.hpp).  The box a host model advances per model step is this
+ * sum -- what cloudy_box_ssprk33_steps integrates with one fixed dt -- and condensation is the source whose time scale differs
+ * most from parcel to parcel: the supersaturation is a per-parcel input of either sign, and x^(2/3) of an evaporating mode falls
+ * linearly in t.  The only change to the mathematics of cloudy_tsit5_adaptive is the right-hand side.
+ *   sources, s_dev, s, xi   what they mean in cloudy_box_ssprk33_steps: [cond] is rhs_condensation!(dmom, mom, p, s)
+ *                (test/examples/utils/box_model_helpers.jl:55-67 -> get_cond_evap, src/Sources/Condensation.jl:22-37); s_dev holds
+ *                one fp64 value per parcel (loaded once per parcel) or is NULL to use the scalar `s`; xi = p.xi in physical units.
+ *   t_span .. stream   what they mean in cloudy_tsit5_adaptive: its controller, error norm, first-step rule, last-step rule,
+ *                statuses and abstol units, stated there and not again here.
+ *   n_save, t_save, u_save_dev   every rule of cloudy_tsit5_adaptive_saveat: a host pointer, its checks, its layout, its NaN rule
+ *                and its bit-equal rule; n_save = 0 with NULL pointers means "no snapshots".
+ *   sources = CLOUDY_SRC_COAL: forwards to cloudy_tsit5_adaptive / cloudy_tsit5_adaptive_saveat (the same kernel, the same bits,
+ *     the same refusals);
+ *   sources = CLOUDY_SRC_COND: every plan cloudy_cond_evap serves, NumericalCoalStyle plans included; nothing of the coalescence
+ *     data is read, the state is kept in normalised units, a plain per-lane loop without a barrier;
+ *   sources = CLOUDY_SRC_COAL | CLOUDY_SRC_COND: AnalyticalCoalStyle plans, both sources from ONE closure inversion per
+ *     evaluation.  Thresholds all Inf: a per-lane loop, normalised state.  Fixed or MovingThreshold: physical state, the
+ *     workgroup re-ranks its parcels in every evaluation and the loop runs while any of its lanes is active.  A
+ *     NumericalCoalStyle plan answers CLOUDY_EUNSUPPORTED (step it stage by stage: cloudy_coal_rhs + cloudy_cond_evap).
+ * Behaviour after a mode has evaporated completely is not specified (max_steps bounds the loop whatever happens).
+ * Argument checks precede any device work, the plan last (CLOUDY_EINVAL, the message names the argument): those of
+ * cloudy_tsit5_adaptive_saveat in its order, then sources outside {COAL, COND, COAL | COND} and xi NaN, then the plan.
+ * Plane types as cloudy_box_ssprk33_steps: CLOUDY_F64 / CLOUDY_F64_RELAXED / CLOUDY_F32 (state and control in fp64 registers
+ * either way); CLOUDY_F32_FAST: CLOUDY_EUNSUPPORTED.  The kernels are compiled for the plan on the first call that needs them
+ * (cloudy_jit_box_adaptive_*, one with and one without snapshots per source set) and have no ahead-of-time instance: without
+ * plan-time compilation the call answers CLOUDY_EUNSUPPORTED with the compiler's log.  A refusal writes nothing. */
+int cloudy_box_tsit5_adaptive(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *u_in_dev, void *u_out_dev,
+                              int sources, const double *s_dev, double s, double xi, double t_span,
+                              const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
+                              size_t n_save, const double *t_save, void *u_save_dev);
+
 /* The adiabatic parcel of test/examples/Analytical/parcel_example.jl: Y = (S, p, T, q_v, mom[0..nmom)) -- saturation ratio over
  * liquid water, pressure, temperature, vapour specific humidity and the plan's moments (physical units, the plan's plane order) --
  * rising at speed w.  With the constants below:

@@ -468,6 +468,49 @@ function solve_box_ssprk33!(u, plan::Plan, dt, n_steps, xi, s; coal::Bool = true
 end
 
 """
+    solve_box_tsit5_adaptive!(u, plan, t_span, xi, s; coal = true, cond = true, saveat = nothing, u_save = nothing, reltol = 1e-6,
+                              abstol = 1e-9, dt = 0.0, max_steps = 10000, dt_dev = nothing, t_dev = nothing, info_dev = nothing,
+                              stream = nothing, sync = true)
+
+Every parcel of `u` from t = 0 to `t_span` with adaptive Tsit5 under a step-size controller of its own, the right-hand side the
+sum of the selected sources: `rhs_coal!` (`coal`) and `rhs_condensation!(dm, m, p, s)` (`cond`) -- `cloudy_box_tsit5_adaptive`,
+the error-controlled counterpart of `solve_box_ssprk33!`.  `xi` = `p.ξ`; `s` a number, or a device `Vector{Float64}` with one
+supersaturation per parcel.  Controller, error norm, statuses and the optional `dt_dev`, `t_dev`, `info_dev` as
+`solve_tsit5_adaptive!`; `saveat` (a HOST vector within [0, `t_span`], strictly increasing) with `u_save` as
+`solve_tsit5_adaptive_saveat!`.  `cond` alone serves every plan; with `coal` a NumericalCoalStyle plan answers
+CLOUDY_EUNSUPPORTED.  Returns `u`.
+"""
+function solve_box_tsit5_adaptive!(u, plan::Plan, t_span, xi, s; coal::Bool = true, cond::Bool = true, saveat = nothing,
+                                   u_save = nothing, reltol = 1e-6, abstol = 1e-9, dt = 0.0, max_steps = 10000, dt_dev = nothing,
+                                   t_dev = nothing, info_dev = nothing, stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(u, plan.nmom)
+    st = stream === nothing ? current_stream() : stream
+    o = AdaptiveOpts()
+    o.reltol, o.abstol, o.dt_init, o.max_steps = reltol, abstol, dt, max_steps
+    sources = (coal ? SRC_COAL : 0) | (cond ? SRC_COND : 0)
+    s_dev = s isa Number ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(s))
+    s_val = s isa Number ? Float64(s) : 0.0
+    ts = saveat === nothing ? Float64[] : convert(Vector{Float64}, collect(saveat))
+    if !isempty(ts)
+        u_save === nothing && error("saveat needs u_save")
+        length(u_save) >= length(ts) * plan.nmom * ld || error("u_save holds fewer than length(saveat) * nmom planes of ld elements")
+        eltype(u_save) == eltype(u) || error("u_save must have the element type of u")
+    end
+    sptr = isempty(ts) ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(u_save))
+    dptr = dt_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(dt_dev))
+    tptr = t_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(t_dev))
+    iptr = info_dev === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(info_dev))
+    GC.@preserve ts check(ccall((:cloudy_box_tsit5_adaptive, lib), Cint,
+                                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Cdouble,
+                                 Ref{AdaptiveOpts}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cvoid}, Csize_t, Ptr{Cdouble},
+                                 Ptr{Cvoid}),
+                                plan.handle, n, ld, pointer(u), pointer(u), sources, s_dev, s_val, xi, t_span, o, dptr, tptr, iptr, st,
+                                length(ts), isempty(ts) ? Ptr{Cdouble}(C_NULL) : pointer(ts), sptr))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return u
+end
+
+"""
     ParcelParams()
 
 `cloudy_parcel_params` with the defaults of `cloudy_parcel_params_init` (ClimaParams' values as recalled): the constants of the

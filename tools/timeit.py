@@ -26,6 +26,9 @@ every experiment switch of the library is an environment variable, so an A/B run
         cloudy_tsit5_adaptive on the cfg3a plan, n log-uniform over three decades: (a) the adaptive call, (b) cloudy_tsit5_steps at
         the fixed dt the densest parcels need for the same measured end-state error -- the caller's only alternative without (a);
         and the active-lane fraction of (a) from the info planes, sum(attempts) / sum over waves of 64 max(attempts)
+  python tools/timeit.py boxadaptive [--parcels P] [--t-span T] [--reltol R] [--xi X]
+        cloudy_box_tsit5_adaptive on the batch of `adaptive` against cloudy_tsit5_adaptive in the same run: COAL | COND, COND alone,
+        COAL | COND with 16 save times; ms per call, ratios and active-lane fractions
   python tools/timeit.py saveat [--parcels P] [--t-span T] [--reltol R]
         cloudy_tsit5_adaptive_saveat on the batch of `adaptive`: cloudy_tsit5_adaptive itself, then the new entry point with n_save =
         0, 1 and 16 equidistant save times (the last at t_span), and the algorithmic snapshot traffic per parcel
@@ -285,6 +288,42 @@ def cmd_saveat(a, pkg, L):
           f"{2 * plan.nmom * 8} B)", flush=True)
 
 
+def cmd_boxadaptive(a, pkg, L):
+    """ms per call on the batch of cmd_adaptive: cloudy_tsit5_adaptive, and cloudy_box_tsit5_adaptive with COAL | COND, COND alone and
+    COAL | COND with 16 save times (a supersaturation per parcel, U(-0.02, 0.05)); the active-lane fraction of each from its info planes"""
+    n, t_span = a.parcels or 10_000_000, a.t_span
+    wl = bench.make_workload("cfg3a", 1)
+    plan = wl["coal_data"].plan(wl["dist_types"])
+    mom = bench.synth_moments(2, n, 7, degenerate_frac=0.0)
+    u0, out = pkg.DeviceArray.from_numpy(mom), pkg.DeviceArray.zeros(*mom.shape)
+    s_dev = pkg.DeviceArray.from_numpy(np.random.default_rng(0).uniform(-0.02, 0.05, n)[None, :])
+    info, t_dev = pkg.DeviceArray.zeros(3, n, np.int32), pkg.DeviceArray.zeros(1, n)
+    opts = pkg._lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol = a.reltol
+
+    def lane_fraction():
+        counts = info.to_numpy()
+        attempts = (counts[0] + counts[1]).astype(np.int64)
+        waves = np.pad(attempts, (0, -n % 64)).reshape(-1, 64)
+        return attempts.sum() / (64 * waves.max(axis=1)).sum(), int((counts[2] != 0).sum())
+
+    plain = lambda: pkg._lib.check(L.cloudy_tsit5_adaptive(plan.handle, n, n, u0.ptr, out.ptr, t_span, C.byref(opts), None, t_dev.ptr,   # noqa: E731
+                                                           info.ptr, None))
+    ms = {"cloudy_tsit5_adaptive": (bench._sustained_ms(pkg, plain, min_reps=3),) + lane_fraction()}
+    for name, sources, n_save in (("COAL | COND", 3, 0), ("COND", 2, 0), ("COAL | COND, n_save = 16", 3, 16)):
+        times = (C.c_double * max(n_save, 1))(*[t_span * (j + 1) / n_save for j in range(n_save)])
+        saved = pkg.DeviceArray(max(n_save, 1) * plan.nmom, n)
+        call = lambda: pkg._lib.check(L.cloudy_box_tsit5_adaptive(plan.handle, n, n, u0.ptr, out.ptr, sources, s_dev.ptr, 0.0, a.xi, t_span,   # noqa: E731
+                                                                  C.byref(opts), None, t_dev.ptr, info.ptr, None, n_save,
+                                                                  times if n_save else None, saved.ptr if n_save else None))
+        ms[name] = (bench._sustained_ms(pkg, call, min_reps=3),) + lane_fraction()
+        saved.free()
+    base = ms["cloudy_tsit5_adaptive"][0]
+    print(f"cfg3a, {n} parcels to t = {t_span:g}, reltol {a.reltol:g}, xi {a.xi:g}: " +
+          " | ".join(f"{k} {v[0]:.3f} ms ({v[0] / base:.3f} x), active lanes {v[1]:.3f}, status != 0: {v[2]}" for k, v in ms.items()), flush=True)
+
+
 def cmd_box(a, pkg, L):
     """ms per call of S steps: (a) cloudy_ssprk33_steps, (b) / (c) cloudy_box_ssprk33_steps with COAL | COND / COND, (d) the same
     steps stage by stage: two right-hand-side launches and the update on the planes (torch, on the same stream) per stage"""
@@ -458,12 +497,17 @@ def main():
     sv.add_argument("--parcels", type=int, default=0)
     sv.add_argument("--t-span", type=float, default=5e-3)
     sv.add_argument("--reltol", type=float, default=1e-6)
+    ba = sub.add_parser("boxadaptive")
+    ba.add_argument("--parcels", type=int, default=0)
+    ba.add_argument("--t-span", type=float, default=5e-3)
+    ba.add_argument("--reltol", type=float, default=1e-6)
+    ba.add_argument("--xi", type=float, default=1e-5)
     hh = sub.add_parser("host")
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
     {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "adaptive": cmd_adaptive,
-     "saveat": cmd_saveat,
+     "saveat": cmd_saveat, "boxadaptive": cmd_boxadaptive,
      "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
