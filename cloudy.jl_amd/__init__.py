@@ -27,7 +27,7 @@ from .Sedimentation import (get_sedimentation_flux, make_rainshaft_cond_rhs, mak
                             rhs_condensation, solve_rainshaft_cond_ssprk33, solve_rainshaft_ssprk33)
 from .box_model import (ODEParameters, make_box_model_rhs, rhs_coal, solve_box_ssprk33, solve_box_tsit5_adaptive, solve_ssprk33, solve_tsit5,
                         solve_tsit5_adaptive, solve_tsit5_adaptive_saveat)
-from .parcel import ParcelParams, parcel_rhs, solve_parcel_ssprk33
+from .parcel import ParcelParams, parcel_rhs, solve_parcel_ssprk33, solve_parcel_tsit5_adaptive
 from .sharding import Communicator, allreduce_sums, mode_sums, moment_sums, shard_range
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -93,6 +93,8 @@ SYMBOLS = {
     "cloudy_parcel_params_init": (None, [C.POINTER(ParcelParamsC)]),
     "cloudy_parcel_rhs": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.POINTER(ParcelParamsC), _i, _vp, _vp]),
     "cloudy_parcel_ssprk33_steps": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.POINTER(ParcelParamsC), C.c_double, _i, _vp]),
+    "cloudy_parcel_tsit5_adaptive": (_i, [_vp, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.POINTER(ParcelParamsC), C.c_double,
+                                          C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp, _sz, _dp, _vp]),
     "cloudy_parcel_thermo_host": (_i, [C.POINTER(ParcelParamsC), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp]),
     "cloudy_update_dist_from_moments": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "cloudy_closure_stats": (_i, [_vp, _sz, _sz, _vp, C.POINTER(C.c_uint64), _vp]),

@@ -92,6 +92,35 @@ enum { ADAPT_DONE = 0, ADAPT_MAX_STEPS = 1, ADAPT_DT_MIN = 2 };   // the status 
 namespace adaptive {
 constexpr double kBeta1 = 7.0 / 50.0, kBeta2 = 2.0 / 25.0, kSafety = 9.0 / 10.0 /* gamma */, kQmin = 1.0 / 5.0, kQmax = 10.0, kQold0 = 1e-4;
 __device__ __forceinline__ bool is_finite(double x) { return fabs(x) < INFINITY; }   // (false for NaN)
+
+// The state of one parcel in the loop: the [N][3] moment arrays and, beside them, X further scalars that the plan's norms do not
+// touch (X = 0: none -- the member is never read or written, and so is not there).  each() applies f to one component of several
+// states at a time, the scalars first, then every slot of the arrays (the padded third slot of a two-moment mode included: its
+// tendency is zero); counted() likewise over the components that count in the norms (the planes a mode has).
+template <int N, int X>
+struct State {
+    double x[X > 0 ? X : 1];
+    double m[N][3];
+};
+template <int N, int X, typename F, typename... S>
+__device__ __forceinline__ void each(F f, S &...s) {
+#pragma unroll
+    for (int q = 0; q < X; ++q) f(s.x[q]...);
+#pragma unroll
+    for (int m = 0; m < N; ++m)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) f(s.m[m][q]...);
+}
+template <int N, int X, typename F, typename... S>
+__device__ __forceinline__ void counted(const int (&np)[N], F f, S &...s) {
+#pragma unroll
+    for (int q = 0; q < X; ++q) f(s.x[q]...);
+#pragma unroll
+    for (int m = 0; m < N; ++m)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            if (q < 2 || np[m] == 3) f(s.m[m][q]...);
+}
 }  // namespace adaptive
 
 // The loop itself -- the seven-stage step, the error estimate, the controller, the FSAL hand-over, the snapshots and the final
@@ -107,101 +136,118 @@ __device__ __forceinline__ bool is_finite(double x) { return fabs(x) < INFINITY;
 // ld, aliasing neither u_in nor u_out) as above; without it they are not read.
 // KEEP0: the right-hand side leaves the number plane of every mode alone (condensation without coalescence: dM0/dt is zero
 // identically), so u_out and every snapshot get that plane's value as loaded, not its round trip through the normalised units.
-template <int N, int P, typename TIO, bool RANKED, int BS, bool SAVE, bool KEEP0 = false, typename RHS>
+// X: a right-hand side with X scalars of state beside the moments (RANKED = false; the parcel's S, p, T, q_v: adaptive_thermo.hpp)
+// is rhs(live, x, state, dx, deriv); the scalars are planes 0 .. X - 1 of u_in / u_out / every snapshot and the plan's planes follow
+// them; they are never normalised (abstol_i = abstol in their own units), count in the norms (n_moms), and are advanced, interpolated
+// and stored like the rest.
+template <int N, int P, typename TIO, bool RANKED, int BS, bool SAVE, bool KEEP0 = false, int X = 0, typename RHS>
 __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t n, size_t ld, const TIO *u_in, TIO *u_out,
                                                     double t_span, AdaptiveOpts o, double *dt_dev, double *t_dev, int *info_dev,
                                                     size_t n_save, const double *__restrict__ t_save, TIO *__restrict__ u_save,
                                                     RHS rhs_of) {
     using namespace tsit5;
+    using St = adaptive::State<N, X>;
+    static_assert(X == 0 || !RANKED, "extra state belongs to the per-lane loop");
     const size_t i = (size_t)blockIdx.x * BS + threadIdx.x;
     const bool valid = i < n;
     constexpr bool kRanked = RANKED;
     constexpr bool kNormalisedState = !kRanked;  // see rhs_normalised
     // SAVE: snapshot js of this lane's parcel from v (the units of the state) as the final store writes u -- physical units, the
     // planes a mode has
-    size_t planes = 0;
+    size_t planes = X;
 #pragma unroll
     for (int m = 0; m < N; ++m) planes += A.np[m] == 3 ? 3 : 2;
     double number_in[N];   // KEEP0: the number planes as loaded
-    auto snapshot = [&](size_t js, const double (&v)[N][3]) {
+    auto snapshot = [&](size_t js, const St &v) {
+#pragma unroll
+        for (int q = 0; q < X; ++q) u_save[(js * planes + (size_t)q) * ld + i] = (TIO)v.x[q];
 #pragma unroll
         for (int m = 0; m < N; ++m)
 #pragma unroll
             for (int q = 0; q < 3; ++q)
                 if (q < 2 || A.np[m] == 3) {
-                    double x = v[m][q];
+                    double x = v.m[m][q];
                     if (kNormalisedState) x *= A.norm[3 * m + q];
                     if constexpr (KEEP0)
                         if (q == 0) x = number_in[m];
-                    u_save[(js * planes + (size_t)(A.off[m] + q)) * ld + i] = (TIO)x;
+                    u_save[(js * planes + (size_t)(X + A.off[m] + q)) * ld + i] = (TIO)x;
                 }
     };
     if (!(t_span > 0.0)) {   // (wave- and workgroup-uniform: a kernel argument) nothing to integrate, the planes as they are
         if (!valid) return;
+        auto copy = [&](size_t p) {
+            const TIO v = u_in[p * ld + i];
+            u_out[p * ld + i] = v;
+            if (SAVE)   // (every save time is 0)
+                for (size_t js = 0; js < n_save; ++js) u_save[(js * planes + p) * ld + i] = v;
+        };
+#pragma unroll
+        for (int q = 0; q < X; ++q) copy((size_t)q);
 #pragma unroll
         for (int m = 0; m < N; ++m)
 #pragma unroll
             for (int q = 0; q < 3; ++q)
-                if (q < 2 || A.np[m] == 3) {
-                    const TIO v = u_in[(size_t)(A.off[m] + q) * ld + i];
-                    u_out[(size_t)(A.off[m] + q) * ld + i] = v;
-                    if (SAVE)   // (every save time is 0)
-                        for (size_t js = 0; js < n_save; ++js) u_save[(js * planes + (size_t)(A.off[m] + q)) * ld + i] = v;
-                }
+                if (q < 2 || A.np[m] == 3) copy((size_t)(X + A.off[m] + q));
         if (t_dev) t_dev[i] = 0.0;
         if (info_dev) info_dev[i] = 0, info_dev[ld + i] = 0, info_dev[2 * ld + i] = ADAPT_DONE;
         return;
     }
     if (!kRanked && !valid) return;
-    double u[N][3], atol[N][3];
-    int count = 0;
+    St u, atol;
+    int count = X;
     const bool save0 = SAVE && valid && n_save > 0 && t_save[0] == 0.0;
     size_t j = save0 ? 1 : 0;   // SAVE: the lane's cursor into t_save
 #pragma unroll
+    for (int q = 0; q < X; ++q) {
+        u.x[q] = (double)u_in[(size_t)q * ld + i];
+        atol.x[q] = o.abstol;
+        if constexpr (SAVE)
+            if (save0) u_save[(size_t)q * ld + i] = (TIO)u.x[q];
+    }
+#pragma unroll
     for (int m = 0; m < N; ++m) {
-        const int off = A.off[m];
-        u[m][0] = valid ? (double)u_in[(size_t)(off + 0) * ld + i] : 0.0;
-        u[m][1] = valid ? (double)u_in[(size_t)(off + 1) * ld + i] : 0.0;
-        u[m][2] = (valid && A.np[m] == 3) ? (double)u_in[(size_t)(off + 2) * ld + i] : 0.0;
+        const int off = X + A.off[m];
+        u.m[m][0] = valid ? (double)u_in[(size_t)(off + 0) * ld + i] : 0.0;
+        u.m[m][1] = valid ? (double)u_in[(size_t)(off + 1) * ld + i] : 0.0;
+        u.m[m][2] = (valid && A.np[m] == 3) ? (double)u_in[(size_t)(off + 2) * ld + i] : 0.0;
         count += A.np[m] == 3 ? 3 : 2;   // (the planes a mode has: the third slot of a two-moment mode is padding)
-        if constexpr (KEEP0) number_in[m] = u[m][0];
+        if constexpr (KEEP0) number_in[m] = u.m[m][0];
         if constexpr (SAVE)   // a save time 0: the values as loaded, before any normalisation
             if (save0) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
-                    if (q < 2 || A.np[m] == 3) u_save[(size_t)(off + q) * ld + i] = (TIO)u[m][q];
+                    if (q < 2 || A.np[m] == 3) u_save[(size_t)(off + q) * ld + i] = (TIO)u.m[m][q];
             }
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            if (kNormalisedState) u[m][q] = div_by_const(u[m][q], A.norm[3 * m + q], A.inv_norm[3 * m + q]);
-            atol[m][q] = kNormalisedState ? o.abstol : o.abstol * A.norm[3 * m + q];
+            if (kNormalisedState) u.m[m][q] = div_by_const(u.m[m][q], A.norm[3 * m + q], A.inv_norm[3 * m + q]);
+            atol.m[m][q] = kNormalisedState ? o.abstol : o.abstol * A.norm[3 * m + q];
         }
     }
     const double n_moms = (double)count;
     // live: the lane's result is wanted (ranked: every lane calls, idle ones sit through the ranking's barriers)
     bool active = valid;
-    auto rhs = [&](const double (&state)[N][3], double (&deriv)[N][3]) { rhs_of(valid && active, state, deriv); };
-    double k1[N][3], k2[N][3], k3[N][3], k4[N][3], k5[N][3], k6[N][3], w[N][3];
+    auto rhs = [&](const St &state, St &deriv) {
+        if constexpr (X == 0) rhs_of(valid && active, state.m, deriv.m);
+        else rhs_of(valid && active, state.x, state.m, deriv.x, deriv.m);
+    };
+    St k1, k2, k3, k4, k5, k6, w;
     // where the error combination and k7 go: k2 and k3, which are dead by then -- SAVE keeps k1 .. k7 for the interpolant and
     // gives both an array of its own (not touched, and so not there, without it)
-    double ke_own[N][3], k7_own[N][3];
-    double(&ke)[N][3] = *[&]() -> double(*)[N][3] { if constexpr (SAVE) return &ke_own; else return &k2; }();
-    double(&k7)[N][3] = *[&]() -> double(*)[N][3] { if constexpr (SAVE) return &k7_own; else return &k3; }();
+    St ke_own, k7_own;
+    St &ke = *[&]() -> St * { if constexpr (SAVE) return &ke_own; else return &k2; }();
+    St &k7 = *[&]() -> St * { if constexpr (SAVE) return &k7_own; else return &k3; }();
     rhs(u, k1);
     // ---- the first step
     double dt = dt_dev && valid ? dt_dev[i] : o.dt_init;
     if (!(dt > 0.0 && adaptive::is_finite(dt))) {
         double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                if (q < 2 || A.np[m] == 3) {
-                    const double sc = fma(o.reltol, fabs(u[m][q]), atol[m][q]);
-                    const double r0 = u[m][q] / sc, r1 = k1[m][q] / sc;
-                    s0 = fma(r0, r0, s0);
-                    s1 = fma(r1, r1, s1);
-                }
+        adaptive::counted<N, X>(A.np, [&](double uu, double kk, double at) {
+            const double sc = fma(o.reltol, fabs(uu), at);
+            const double r0 = uu / sc, r1 = kk / sc;
+            s0 = fma(r0, r0, s0);
+            s1 = fma(r1, r1, s1);
+        }, u, k1, atol);
         const double d0 = sqrt(s0 / n_moms), d1 = sqrt(s1 / n_moms);
         dt = d1 == 0.0 ? t_span : 0.01 * d0 / d1;
     }
@@ -222,57 +268,36 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
         }
         const bool last = t + dt >= t_last;
         const double h = last ? t_span - t : dt;
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) w[m][q] = fma(h * a21, k1[m][q], u[m][q]);
+        adaptive::each<N, X>([&](double &ww, double c1, double uu) { ww = fma(h * a21, c1, uu); }, w, k1, u);
         rhs(w, k2);
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) w[m][q] = fma(h, fma(a31, k1[m][q], a32 * k2[m][q]), u[m][q]);
+        adaptive::each<N, X>([&](double &ww, double c1, double c2, double uu) { ww = fma(h, fma(a31, c1, a32 * c2), uu); }, w, k1, k2, u);
         rhs(w, k3);
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) w[m][q] = fma(h, fma(a41, k1[m][q], fma(a42, k2[m][q], a43 * k3[m][q])), u[m][q]);
+        adaptive::each<N, X>([&](double &ww, double c1, double c2, double c3, double uu) {
+            ww = fma(h, fma(a41, c1, fma(a42, c2, a43 * c3)), uu);
+        }, w, k1, k2, k3, u);
         rhs(w, k4);
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                w[m][q] = fma(h, fma(a51, k1[m][q], fma(a52, k2[m][q], fma(a53, k3[m][q], a54 * k4[m][q]))), u[m][q]);
+        adaptive::each<N, X>([&](double &ww, double c1, double c2, double c3, double c4, double uu) {
+            ww = fma(h, fma(a51, c1, fma(a52, c2, fma(a53, c3, a54 * c4))), uu);
+        }, w, k1, k2, k3, k4, u);
         rhs(w, k5);
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                w[m][q] = fma(h, fma(a61, k1[m][q], fma(a62, k2[m][q], fma(a63, k3[m][q], fma(a64, k4[m][q], a65 * k5[m][q])))),
-                              u[m][q]);
+        adaptive::each<N, X>([&](double &ww, double c1, double c2, double c3, double c4, double c5, double uu) {
+            ww = fma(h, fma(a61, c1, fma(a62, c2, fma(a63, c3, fma(a64, c4, a65 * c5)))), uu);
+        }, w, k1, k2, k3, k4, k5, u);
         rhs(w, k6);
         // u_new into w; the k1 .. k6 part of the error estimate into k2, which is dead from here; then k7 into k3 (ke, k7 above)
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                w[m][q] = fma(h, fma(a71, k1[m][q], fma(a72, k2[m][q], fma(a73, k3[m][q], fma(a74, k4[m][q],
-                                                                                            fma(a75, k5[m][q], a76 * k6[m][q]))))),
-                              u[m][q]);
-                ke[m][q] = fma(bt1, k1[m][q], fma(bt2, k2[m][q], fma(bt3, k3[m][q], fma(bt4, k4[m][q],
-                                                                                        fma(bt5, k5[m][q], bt6 * k6[m][q])))));
-            }
+        // (ke may be k2: the lambda takes its k2 by value)
+        adaptive::each<N, X>([&](double &ww, double &ee, double c1, double c2, double c3, double c4, double c5, double c6, double uu) {
+            ww = fma(h, fma(a71, c1, fma(a72, c2, fma(a73, c3, fma(a74, c4, fma(a75, c5, a76 * c6))))), uu);
+            ee = fma(bt1, c1, fma(bt2, c2, fma(bt3, c3, fma(bt4, c4, fma(bt5, c5, bt6 * c6)))));
+        }, w, ke, k1, k2, k3, k4, k5, k6, u);
         rhs(w, k7);
         double s = 0.0;
-#pragma unroll
-        for (int m = 0; m < N; ++m)
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                if (q < 2 || A.np[m] == 3) {
-                    const double err = h * fma(bt7, k7[m][q], ke[m][q]);
-                    const double sc = fma(o.reltol, fmax(fabs(u[m][q]), fabs(w[m][q])), atol[m][q]);
-                    const double r = err / sc;
-                    s = fma(r, r, s);
-                }
+        adaptive::counted<N, X>(A.np, [&](double c7, double ee, double uu, double ww, double at) {
+            const double err = h * fma(bt7, c7, ee);
+            const double sc = fma(o.reltol, fmax(fabs(uu), fabs(ww)), at);
+            const double r = err / sc;
+            s = fma(r, r, s);
+        }, k7, ke, u, w, atol);
         const double eest = sqrt(s / n_moms);
         if (!active) continue;   // (an idle lane of a thresholded plan: it only sat through the barriers)
         if (!adaptive::is_finite(eest)) {
@@ -293,14 +318,14 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
                     if (ts == t_new) {   // (the end of the step: u_new itself, what the final store writes at t_span)
                         snapshot(j, w);
                     } else {
-                        double b[7], v[N][3];
+                        double b[7];
+                        St v;
                         interp_weights((ts - t) / h, b);
-#pragma unroll
-                        for (int m = 0; m < N; ++m)
-#pragma unroll
-                            for (int qq = 0; qq < 3; ++qq)
-                                v[m][qq] = fma(h, fma(b[0], k1[m][qq], fma(b[1], k2[m][qq], fma(b[2], k3[m][qq], fma(b[3], k4[m][qq],
-                                                      fma(b[4], k5[m][qq], fma(b[5], k6[m][qq], b[6] * k7[m][qq])))))), u[m][qq]);
+                        adaptive::each<N, X>([&](double &vv, double c1, double c2, double c3, double c4, double c5, double c6, double c7,
+                                                 double uu) {
+                            vv = fma(h, fma(b[0], c1, fma(b[1], c2, fma(b[2], c3, fma(b[3], c4, fma(b[4], c5, fma(b[5], c6, b[6] * c7)))))),
+                                     uu);
+                        }, v, k1, k2, k3, k4, k5, k6, k7, u);
                         snapshot(j, v);
                     }
                     ++j;
@@ -309,10 +334,7 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
             t = last ? t_span : t + h;
             dt = fmax(h / q, fmin(dt, dt / q));
             qold = fmax(eest, adaptive::kQold0);
-#pragma unroll
-            for (int m = 0; m < N; ++m)
-#pragma unroll
-                for (int qq = 0; qq < 3; ++qq) u[m][qq] = w[m][qq], k1[m][qq] = k7[m][qq];
+            adaptive::each<N, X>([&](double &uu, double &c1, double ww, double c7) { uu = ww, c1 = c7; }, u, k1, w, k7);
             if (last) active = false;   // status 0
         } else {
             ++n_rej;
@@ -322,24 +344,29 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
     if (!valid) return;
     if constexpr (SAVE) {   // what a parcel stopped by the budget or by dt did not reach (status 0: the cursor is at n_save)
         const TIO nan = (TIO)__builtin_nan("");
-        for (; j < n_save; ++j)
+        for (; j < n_save; ++j) {
+#pragma unroll
+            for (int q = 0; q < X; ++q) u_save[(j * planes + (size_t)q) * ld + i] = nan;
 #pragma unroll
             for (int m = 0; m < N; ++m)
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
-                    if (q < 2 || A.np[m] == 3) u_save[(j * planes + (size_t)(A.off[m] + q)) * ld + i] = nan;
+                    if (q < 2 || A.np[m] == 3) u_save[(j * planes + (size_t)(X + A.off[m] + q)) * ld + i] = nan;
+        }
     }
 #pragma unroll
+    for (int q = 0; q < X; ++q) u_out[(size_t)q * ld + i] = (TIO)u.x[q];
+#pragma unroll
     for (int m = 0; m < N; ++m) {
-        const int off = A.off[m];
+        const int off = X + A.off[m];
         if (kNormalisedState) {
 #pragma unroll
-            for (int q = 0; q < 3; ++q) u[m][q] *= A.norm[3 * m + q];
+            for (int q = 0; q < 3; ++q) u.m[m][q] *= A.norm[3 * m + q];
         }
-        if constexpr (KEEP0) u[m][0] = number_in[m];
-        u_out[(size_t)(off + 0) * ld + i] = (TIO)u[m][0];
-        u_out[(size_t)(off + 1) * ld + i] = (TIO)u[m][1];
-        if (A.np[m] == 3) u_out[(size_t)(off + 2) * ld + i] = (TIO)u[m][2];
+        if constexpr (KEEP0) u.m[m][0] = number_in[m];
+        u_out[(size_t)(off + 0) * ld + i] = (TIO)u.m[m][0];
+        u_out[(size_t)(off + 1) * ld + i] = (TIO)u.m[m][1];
+        if (A.np[m] == 3) u_out[(size_t)(off + 2) * ld + i] = (TIO)u.m[m][2];
     }
     if (dt_dev) dt_dev[i] = dt;
     if (t_dev) t_dev[i] = t;

@@ -321,6 +321,8 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_TSIT5_SAVEAT: return JIT_ADAPTIVE;
     case OP_BOX_TSIT5_ADAPTIVE:
     case OP_BOX_TSIT5_SAVEAT: return JIT_BOX_ADAPTIVE;
+    case OP_PARCEL_TSIT5_ADAPTIVE:
+    case OP_PARCEL_TSIT5_SAVEAT: return JIT_PARCEL_ADAPTIVE;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
@@ -347,6 +349,7 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
     case JIT_BOX: return coal ? BOX_COALCOND : BOX_COND;
     case JIT_ADAPTIVE: return r.op == OP_TSIT5_SAVEAT ? ADAPTIVE_SAVEAT : ADAPTIVE_PLAIN;
     case JIT_BOX_ADAPTIVE: return (coal ? BOXAD_COALCOND : BOXAD_COND) + (r.op == OP_BOX_TSIT5_SAVEAT ? 1 : 0);
+    case JIT_PARCEL_ADAPTIVE: return (coal ? PARAD_COALCOND : PARAD_COND) + (r.op == OP_PARCEL_TSIT5_SAVEAT ? 1 : 0);
     case JIT_PARCEL: return r.op == OP_PARCEL_RHS ? (coal ? PARCEL_RHS_COAL : PARCEL_RHS) : (coal ? PARCEL_COALCOND : PARCEL_COND);
     case JIT_DIAG:
         return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
@@ -577,6 +580,10 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         return refuse_without_unit(plan, JIT_BOX_ADAPTIVE, "cloudy_box_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and "
                                                            "has no ahead-of-time instance: step such a plan stage by stage with "
                                                            "cloudy_coal_rhs and cloudy_cond_evap");
+    if (r.op == OP_PARCEL_TSIT5_ADAPTIVE || r.op == OP_PARCEL_TSIT5_SAVEAT)
+        return refuse_without_unit(plan, JIT_PARCEL_ADAPTIVE, "cloudy_parcel_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) "
+                                                              "and has no ahead-of-time instance: step such a parcel stage by stage with "
+                                                              "cloudy_cond_evap (and cloudy_coal_rhs) and cloudy_parcel_thermo_host");
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
@@ -650,7 +657,7 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
             return fail(CLOUDY_EUNSUPPORTED, "the combined coalescence + condensation kernel is not built for quadrature "
                                              "(NumericalCoalStyle) plans: %s, or pass CLOUDY_SRC_COND alone", kStaged);
     }
-    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS) {
+    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS || r.op == OP_PARCEL_TSIT5_ADAPTIVE || r.op == OP_PARCEL_TSIT5_SAVEAT) {
         static const char kStaged[] = "step such a parcel stage by stage: cloudy_cond_evap (and cloudy_coal_rhs) per stage with the "
                                       "thermodynamics of cloudy_parcel_thermo_host on the host's side";
         if (plan->h.dtype != CLOUDY_F64)
@@ -1177,10 +1184,10 @@ void cloudy_adaptive_opts_init(cloudy_adaptive_opts *o) {
 }
 
 // the checks of cloudy_tsit5_adaptive that need no device.  The plan comes last (parcel_request says why): `more` -- the checks an
-// entry point has beyond these, nullptr: none -- runs between the last of these and the plan's.
+// entry point has beyond these, a callable -- runs between the last of these and the plan's.  (A template: C++ linkage.)
+extern "C++" template <typename More>
 static int adaptive_request(const cloudy_plan *plan, size_t n, size_t ld, const void *in, void *out, double t_span,
-                            const cloudy_adaptive_opts *o, AdaptiveOpts &c, int (*more)(int, double) = nullptr, int more_i = 0,
-                            double more_d = 0.0) {
+                            const cloudy_adaptive_opts *o, AdaptiveOpts &c, More more) {
     if (!o) return fail(CLOUDY_EINVAL, "opts is NULL");
     if (o->struct_size != sizeof(cloudy_adaptive_opts))
         return fail(CLOUDY_EINVAL, "opts.struct_size (%u) is not sizeof(cloudy_adaptive_opts) (%zu): call cloudy_adaptive_opts_init",
@@ -1197,9 +1204,12 @@ static int adaptive_request(const cloudy_plan *plan, size_t n, size_t ld, const 
     if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
     if (n > 0 && (!in || !out)) return fail(CLOUDY_EINVAL, "device buffer is NULL");
     c = {o->reltol, o->abstol, o->dt_init, (int)o->max_steps};
-    if (more)
-        if (int rc = more(more_i, more_d)) return rc;
+    if (int rc = more()) return rc;
     return check_batch(plan, n, ld, in, out);
+}
+static int adaptive_request(const cloudy_plan *plan, size_t n, size_t ld, const void *in, void *out, double t_span,
+                            const cloudy_adaptive_opts *o, AdaptiveOpts &c) {
+    return adaptive_request(plan, n, ld, in, out, t_span, o, c, [] { return (int)CLOUDY_OK; });
 }
 
 int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, double t_span,
@@ -1219,11 +1229,13 @@ int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const vo
 // the checks of the save times of a call with dense output: they need no device either and precede the plan's (t_span is
 // checked after them; a save time compared with a t_span that is not finite or negative fails here or there, with an EINVAL
 // either way)
-static int check_save_times(size_t n_save, const double *t_save, const void *u_save_dev, double t_span) {
+// (save_name: what the entry point calls its snapshot planes)
+static int check_save_times(size_t n_save, const double *t_save, const void *u_save_dev, double t_span,
+                            const char *save_name = "u_save_dev") {
     if (n_save > CLOUDY_MAX_SAVE_TIMES)
         return fail(CLOUDY_EINVAL, "n_save (%zu) must be <= CLOUDY_MAX_SAVE_TIMES (%d)", n_save, CLOUDY_MAX_SAVE_TIMES);
     if (n_save > 0 && !t_save) return fail(CLOUDY_EINVAL, "t_save is NULL with n_save = %zu", n_save);
-    if (n_save > 0 && !u_save_dev) return fail(CLOUDY_EINVAL, "u_save_dev is NULL with n_save = %zu", n_save);
+    if (n_save > 0 && !u_save_dev) return fail(CLOUDY_EINVAL, "%s is NULL with n_save = %zu", save_name, n_save);
     for (size_t j = 0; j < n_save; ++j) {
         if (!std::isfinite(t_save[j]) || t_save[j] < 0.0 || t_save[j] > t_span)
             return fail(CLOUDY_EINVAL, "t_save[%zu] (%g) must be finite and within [0, t_span] (t_span = %g)", j, t_save[j], t_span);
@@ -1276,7 +1288,8 @@ int cloudy_box_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, cons
     // the checks of cloudy_tsit5_adaptive_saveat in its order, then the box's, then the plan
     if (int rc = check_save_times(n_save, t_save, u_save_dev, t_span)) return rc;
     AdaptiveOpts c;
-    if (int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c, check_box_sources, sources, xi)) return rc;
+    if (int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c, [&] { return check_box_sources(sources, xi); }))
+        return rc;
     if (sources == SRC_COAL)   // coalescence alone is cloudy_tsit5_adaptive[_saveat]: the same request, the same kernel
         return cloudy_tsit5_adaptive_saveat(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, dt_dev, t_dev, info_dev, stream, n_save,
                                             t_save, u_save_dev);
@@ -1378,6 +1391,39 @@ int cloudy_parcel_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, co
     r.s_dev = w_dev;
     r.dt = dt;
     r.n_steps = n_steps;
+    return run(plan, r);
+}
+
+int cloudy_parcel_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const void *y_in_dev, void *y_out_dev, int sources,
+                                 const double *w_dev, double w, const cloudy_parcel_params *params, double t_span,
+                                 const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
+                                 size_t n_save, const double *t_save, void *y_save_dev) {
+    // the checks of cloudy_tsit5_adaptive_saveat in its order, then the parcel's, then the plan
+    if (int rc = check_save_times(n_save, t_save, y_save_dev, t_span, "y_save_dev")) return rc;
+    AdaptiveOpts c;
+    ParcelParams pc;
+    const auto parcel_checks = [&] {
+        if (int rc = parcel_params(params, pc)) return rc;
+        if (sources != SRC_COND && sources != (SRC_COAL | SRC_COND))
+            return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COND or CLOUDY_SRC_COAL | CLOUDY_SRC_COND (coalescence alone is "
+                                       "not a parcel: cloudy_tsit5_adaptive)", sources);
+        return (int)CLOUDY_OK;
+    };
+    if (int rc = adaptive_request(plan, n, ld, y_in_dev, y_out_dev, t_span, opts, c, parcel_checks)) return rc;
+    LaunchReq r(n_save > 0 ? OP_PARCEL_TSIT5_SAVEAT : OP_PARCEL_TSIT5_ADAPTIVE, n, ld, y_in_dev, y_out_dev, stream);
+    r.sources = sources;
+    r.parcel = &pc;
+    r.coef = parcel_coef0(plan, pc);
+    r.s_scalar = w;
+    r.s_dev = w_dev;
+    r.dt = t_span;
+    r.adaptive = &c;
+    r.dt_dev = dt_dev;
+    r.t_dev = t_dev;
+    r.info_dev = info_dev;
+    r.n_save = n_save;
+    r.t_save = t_save;
+    r.out2 = y_save_dev;
     return run(plan, r);
 }
 

@@ -58,7 +58,9 @@ enum Op {
     OP_TSIT5_ADAPTIVE = 16 /* per-parcel adaptive Tsit5 to t_span (cloudy_tsit5_adaptive, adaptive.hpp) */,
     OP_TSIT5_SAVEAT = 17 /* the same with snapshots at the caller's save times (cloudy_tsit5_adaptive_saveat) */,
     OP_BOX_TSIT5_ADAPTIVE = 18 /* per-parcel adaptive Tsit5 with the condensation source (cloudy_box_tsit5_adaptive, adaptive_box.hpp) */,
-    OP_BOX_TSIT5_SAVEAT = 19 /* the same with snapshots at the caller's save times (its n_save > 0) */
+    OP_BOX_TSIT5_SAVEAT = 19 /* the same with snapshots at the caller's save times (its n_save > 0) */,
+    OP_PARCEL_TSIT5_ADAPTIVE = 20 /* per-parcel adaptive Tsit5 of the adiabatic parcel (cloudy_parcel_tsit5_adaptive, adaptive_thermo.hpp) */,
+    OP_PARCEL_TSIT5_SAVEAT = 21 /* the same with snapshots at the caller's save times (its n_save > 0) */
 };
 
 struct LaunchReq {

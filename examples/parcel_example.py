@@ -4,7 +4,10 @@ adiabatic parcel rising at w = 10 m/s from T = 280.15 K, p = 800 hPa, S = 1, wit
 Monodisperse, a Gamma (k = 2) and an Exponential + Gamma size distribution; SSPRK33 with dt = 0.5 s over 40 steps.  The
 saturation ratio, pressure, temperature and vapour content are prognostic beside the moments (cloudy_parcel_ssprk33_steps).
 
-    python examples/parcel_example.py
+    python examples/parcel_example.py [--adaptive]
+
+--adaptive: the same 0.5 s series from ONE launch of the per-parcel adaptive Tsit5 (cloudy_parcel_tsit5_adaptive, reltol 1e-6)
+through its dense output at the 41 save times, instead of 40 calls of one fixed step.
 
 Needs a GPU (the package has no CPU path).  The Julia original plots; this prints the supersaturation [%] and the mean radius
 [um] of the first mode every 2 s.  Unlike the driver as written, condensation acts on the distributions updated from the
@@ -60,9 +63,17 @@ if __name__ == "__main__":
         par = cl.ODEParameters(pdists, cd, NProgMoms, norms)
         y = cl.DeviceArray.from_numpy(np.ascontiguousarray(Y0[:, None]))
         print(f"{kind}:  t [s]   supersaturation [%]   mean radius [um]   T [K]")
-        for step in range(int(round(t_max / const_dt)) + 1):
-            Y = y.to_numpy()[:, 0]
+        n_out = int(round(t_max / const_dt)) + 1
+        series = None
+        if "--adaptive" in sys.argv[1:]:
+            saved, acc, rej, _, _ = cl.solve_parcel_tsit5_adaptive(par, y, w, t_max, params=params, times=const_dt * np.arange(n_out),
+                                                                   info=True)
+            series = saved.to_numpy().reshape(n_out, len(Y0))
+            print(f"    (adaptive: {int(acc[0])} accepted, {int(rej[0])} rejected steps)")
+        for step in range(n_out):
+            Y = y.to_numpy()[:, 0] if series is None else series[step]
             if step % 4 == 0:
                 r_l = (Y[5] / Y[4] / rho_l / 4 / math.pi * 3) ** (1 / 3) * 1e6   # :246-249
                 print(f"    {step * const_dt:6.1f}   {(Y[0] - 1) * 100:10.5f}   {r_l:14.5f}   {Y[2]:12.5f}")
-            cl.solve_parcel_ssprk33(par, y, w, const_dt, 1, params=params)
+            if series is None:
+                cl.solve_parcel_ssprk33(par, y, w, const_dt, 1, params=params)

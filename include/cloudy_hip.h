@@ -471,6 +471,39 @@ int cloudy_parcel_rhs(const cloudy_plan *plan, size_t n_parcels, size_t ld, cons
 int cloudy_parcel_ssprk33_steps(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *y_in_dev, void *y_out_dev,
                                 int sources, const double *w_dev, double w, const cloudy_parcel_params *params, double dt,
                                 int n_steps, void *stream);
+/* Per-parcel ADAPTIVE Tsit5 of the adiabatic parcel: dY/dt above from t = 0 to t = t_span, every parcel under a step-size
+ * controller of its own (csrc/adaptive_thermo.hpp).  The parcel's fastest time scale is the relaxation of the supersaturation,
+ * about 1 / (4 pi D_vapor N r) -- 2 s for the driver's N = 2e8, a tenth of that at 2e9 -- and it moves as the droplets grow: a
+ * batch whose droplet numbers and updraft speeds span a decade each has no common dt that is both safe and cheap.  It is the
+ * loop of cloudy_tsit5_adaptive on the right-hand side of cloudy_parcel_ssprk33_steps (the updated-distribution form, xi(T) formed
+ * per evaluation, the moments in normalised units between load and store).
+ *   y_in_dev, y_out_dev, sources, w_dev, w, params   what they mean in cloudy_parcel_ssprk33_steps, the layout included: 4 + nmom
+ *                fp64 planes of leading dimension ld; y_out_dev may equal y_in_dev.
+ *   t_span .. stream   what they mean in cloudy_tsit5_adaptive: tableau, PI controller and its constants, first-step rule,
+ *                last-step rule, statuses 0 / 1 / 2, max_steps, dt_dev in/out for a warm start -- stated there, not again here.
+ *   error norm   EEst = sqrt(mean_i (err_i / sc_i)^2) over the 4 + nmom prognostic components, sc_i = abstol_i + reltol
+ *                max(|y_i|, |y_new,i|).  The moments: abstol_i = abstol in the plan's normalised units (mom ./ norms), as for every
+ *                plan whose thresholds are all Inf.  S, p, T, q_v: abstol_i = abstol in their own units.  Consequence: p (~1e5) and
+ *                T (~3e2) are controlled relatively, S (~1) to reltol + abstol, and q_v (~1e-2) to max(reltol, abstol / q_v).
+ *   n_save, t_save, y_save_dev   every rule of cloudy_tsit5_adaptive_saveat: a host pointer, its checks, its NaN rule, its bit-equal
+ *                rules at 0, at t_span and at step ends, the plan-owned save-time scratch; n_save = 0 with NULL pointers means "no
+ *                snapshots".  y_save_dev holds snapshot j, plane p, parcel i at [(j * (4 + nmom) + p) * ld + i], fp64, physical
+ *                units; it overlaps neither y_in_dev nor y_out_dev; columns n_parcels .. ld are not written.
+ *   sources = CLOUDY_SRC_COND: dM0/dt is zero identically -- the number planes of y_out_dev and of every snapshot carry the bits
+ *     of the input.
+ * n_parcels = 0: CLOUDY_OK at once.  t_span = 0: a copy, status 0, zero counts, every snapshot is the input.
+ * Argument checks precede any device work, the plan last (CLOUDY_EINVAL, the message names the argument): those of
+ * cloudy_tsit5_adaptive_saveat in its order, then those of cloudy_parcel_ssprk33_steps (params NULL or of another struct_size, a
+ * constant that is not positive, sources without CLOUDY_SRC_COND), then the plan.
+ * Deliberate limits (CLOUDY_EUNSUPPORTED, nothing written; step such a parcel stage by stage with cloudy_cond_evap /
+ * cloudy_coal_rhs and cloudy_parcel_thermo_host): those of cloudy_parcel_ssprk33_steps -- COAL | COND on plans with finite or
+ * moving thresholds and on NumericalCoalStyle plans; CLOUDY_F32 / CLOUDY_F32_FAST planes.  The kernels are compiled for the plan on
+ * the first call that needs them (cloudy_jit_parcel_adaptive_*, one with and one without snapshots per source set) and have no
+ * ahead-of-time instance: without plan-time compilation the call answers CLOUDY_EUNSUPPORTED with the compiler's log. */
+int cloudy_parcel_tsit5_adaptive(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *y_in_dev, void *y_out_dev,
+                                 int sources, const double *w_dev, double w, const cloudy_parcel_params *params, double t_span,
+                                 const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
+                                 size_t n_save, const double *t_save, void *y_save_dev);
 /* the closure alone, on the host (the same source as the kernels'): out = (rho, R, cp, L, p_vs, xi, a1, a3) for a state
  * (S, p, T, q_v) and m_liq = the sum of the modes' mass moments in physical units */
 int cloudy_parcel_thermo_host(const cloudy_parcel_params *params, double S, double p, double T, double q_v, double m_liq,

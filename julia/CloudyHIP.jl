@@ -581,6 +581,46 @@ function solve_parcel_ssprk33!(y, plan::Plan, w, dt, n_steps; params::ParcelPara
 end
 
 """
+    solve_parcel_tsit5_adaptive!(y, plan, w, t_span; params = ParcelParams(), coal = false, saveat = nothing, y_save = nothing,
+                                 reltol = 1e-6, abstol = 1e-9, dt = 0.0, max_steps = 10000, dt_dev = nothing, t_dev = nothing,
+                                 info_dev = nothing, stream = nothing, sync = true)
+
+Every parcel of `y` from t = 0 to `t_span` with adaptive Tsit5 under a step-size controller of its own --
+`cloudy_parcel_tsit5_adaptive`, the error-controlled counterpart of `solve_parcel_ssprk33!`; `w`, `params` and `coal` as it takes
+them.  Controller, statuses and the optional `dt_dev`, `t_dev`, `info_dev` as `solve_tsit5_adaptive!`; `abstol` applies to S, p, T,
+q_v in their own units and to the moments in the plan's normalised units.  `saveat` (a HOST vector within [0, `t_span`], strictly
+increasing) with `y_save` (`length(saveat) * (4 + nmom)` planes of the leading dimension of `y`) as `solve_tsit5_adaptive_saveat!`.
+Returns `y`.
+"""
+function solve_parcel_tsit5_adaptive!(y, plan::Plan, w, t_span; params::ParcelParams = ParcelParams(), coal::Bool = false,
+                                      saveat = nothing, y_save = nothing, reltol = 1e-6, abstol = 1e-9, dt = 0.0, max_steps = 10000,
+                                      dt_dev = nothing, t_dev = nothing, info_dev = nothing, stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(y, plan.nmom + 4)
+    st = stream === nothing ? current_stream() : stream
+    o = AdaptiveOpts()
+    o.reltol, o.abstol, o.dt_init, o.max_steps = reltol, abstol, dt, max_steps
+    w_dev, w_val = parcel_updraft(w)
+    ts = saveat === nothing ? Float64[] : convert(Vector{Float64}, collect(saveat))
+    if !isempty(ts)
+        y_save === nothing && error("saveat needs y_save")
+        length(y_save) >= length(ts) * (plan.nmom + 4) * ld || error("y_save holds fewer than length(saveat) * (4 + nmom) planes of ld elements")
+        eltype(y_save) == Float64 || error("y_save must be Float64")
+    end
+    sptr = isempty(ts) ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(y_save))
+    dptr = dt_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(dt_dev))
+    tptr = t_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(t_dev))
+    iptr = info_dev === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(info_dev))
+    GC.@preserve ts check(ccall((:cloudy_parcel_tsit5_adaptive, lib), Cint,
+                                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cdouble, Ref{ParcelParams},
+                                 Cdouble, Ref{AdaptiveOpts}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cvoid}, Csize_t, Ptr{Cdouble},
+                                 Ptr{Cvoid}),
+                                plan.handle, n, ld, pointer(y), pointer(y), SRC_COND | (coal ? SRC_COAL : 0), w_dev, w_val, params,
+                                t_span, o, dptr, tptr, iptr, st, length(ts), isempty(ts) ? Ptr{Cdouble}(C_NULL) : pointer(ts), sptr))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return y
+end
+
+"""
     solve_rainshaft_ssprk33!(u, plan, nz, dz, dt, n_steps; stream = nothing, sync = true)
 
 `solve(ODEProblem(make_rainshaft_rhs(AnalyticalCoalStyle()), m, tspan, p), SSPRK33(), dt = p.dt)` of

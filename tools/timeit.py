@@ -29,6 +29,11 @@ every experiment switch of the library is an environment variable, so an A/B run
   python tools/timeit.py boxadaptive [--parcels P] [--t-span T] [--reltol R] [--xi X]
         cloudy_box_tsit5_adaptive on the batch of `adaptive` against cloudy_tsit5_adaptive in the same run: COAL | COND, COND alone,
         COAL | COND with 16 save times; ms per call, ratios and active-lane fractions
+  python tools/timeit.py parceladaptive [--parcels P] [--t-span T] [--reltol R]
+        cloudy_parcel_tsit5_adaptive on one Monodisperse mode: the decade batch (N = 2e8 10^U(-1, 1), w = U(0.5, 10), default_rng(5))
+        and the driver's uniform batch (N = 2e8, w = 10); for each the new entry point with 0 and 41 save times and
+        cloudy_parcel_ssprk33_steps with the driver's 40 steps of t_span / 40; ms per call and active-lane fractions.  The two
+        integrators do different amounts of work for different accuracy
   python tools/timeit.py saveat [--parcels P] [--t-span T] [--reltol R]
         cloudy_tsit5_adaptive_saveat on the batch of `adaptive`: cloudy_tsit5_adaptive itself, then the new entry point with n_save =
         0, 1 and 16 equidistant save times (the last at t_span), and the algorithmic snapshot traffic per parcel
@@ -324,6 +329,57 @@ def cmd_boxadaptive(a, pkg, L):
           " | ".join(f"{k} {v[0]:.3f} ms ({v[0] / base:.3f} x), active lanes {v[1]:.3f}, status != 0: {v[2]}" for k, v in ms.items()), flush=True)
 
 
+def cmd_parceladaptive(a, pkg, L):
+    """ms per call of cloudy_parcel_tsit5_adaptive (n_save = 0 and 41) beside cloudy_parcel_ssprk33_steps (40 fixed steps) on the
+    decade batch and on the driver's uniform batch; the active-lane fraction of the adaptive calls from their info planes"""
+    n, t_span = a.parcels or 10_000_000, a.t_span
+    c = pkg.ParcelParams()
+    d, keep = pkg.Plan.make_desc([2], np.array([[1.0]]), (float("inf"),), (1e8, 1e-12), 0)
+    handle = C.c_void_p()
+    pkg._lib.check(L.cloudy_plan_create(C.byref(d), C.byref(handle)))
+    m0_drop = 4 / 3 * np.pi * 8e-6**3 * 1000.0
+    dcp = c.cp_v - c.cp_l
+    T0, p0 = 280.15, 8e4
+    e = c.press_triple * (T0 / c.T_triple) ** (dcp / c.R_v) * np.exp((c.LH_v0 - dcp * c.T_0) / c.R_v * (1 / c.T_triple - 1 / T0))
+    m_d, m_v = (p0 - e) / c.R_d / T0, e / c.R_v / T0
+
+    def batch(N, w):   # parcel_example.jl:174-179, 218 per parcel
+        M1 = N * m0_drop
+        return np.ascontiguousarray(np.stack([np.ones(n), np.full(n, p0), np.full(n, T0), m_v / (m_d + m_v + M1), N, M1])), w
+
+    rng = np.random.default_rng(5)
+    batches = {"decade batch": batch(2e8 * 10.0 ** rng.uniform(-1.0, 1.0, n), rng.uniform(0.5, 10.0, n)),
+               "uniform batch (N = 2e8, w = 10)": batch(np.full(n, 2e8), np.full(n, 10.0))}
+    opts = pkg._lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol = a.reltol
+    cc = c.to_c()
+    info, t_dev, out = pkg.DeviceArray.zeros(3, n, np.int32), pkg.DeviceArray.zeros(1, n), pkg.DeviceArray.zeros(6, n)
+    n_save = 41
+    times = (C.c_double * n_save)(*[t_span * j / (n_save - 1) for j in range(n_save)])
+    saved = pkg.DeviceArray(n_save * 6, n)
+    for name, (y, w) in batches.items():
+        y0, w_dev = pkg.DeviceArray.from_numpy(y), pkg.DeviceArray.from_numpy(w[None, :])
+        res = []
+        for k in (0, n_save):
+            call = lambda: pkg._lib.check(L.cloudy_parcel_tsit5_adaptive(handle, n, n, y0.ptr, out.ptr, pkg.SRC_COND, w_dev.ptr, 0.0,   # noqa: E731
+                                                                         C.byref(cc), t_span, C.byref(opts), None, t_dev.ptr, info.ptr,
+                                                                         None, k, times if k else None, saved.ptr if k else None))
+            ms = bench._sustained_ms(pkg, call, min_reps=3)
+            counts = info.to_numpy()
+            attempts = (counts[0] + counts[1]).astype(np.int64)
+            waves = np.pad(attempts, (0, -n % 64)).reshape(-1, 64)
+            res.append(f"adaptive, n_save = {k}: {ms:.3f} ms, attempts {attempts.min()} .. {attempts.max()} (mean {attempts.mean():.1f}), "
+                       f"active lanes {attempts.sum() / (64 * waves.max(axis=1)).sum():.3f}, status != 0: {int((counts[2] != 0).sum())}")
+        fixed = lambda: pkg._lib.check(L.cloudy_parcel_ssprk33_steps(handle, n, n, y0.ptr, out.ptr, pkg.SRC_COND, w_dev.ptr, 0.0,   # noqa: E731
+                                                                     C.byref(cc), t_span / 40, 40, None))
+        res.append(f"cloudy_parcel_ssprk33_steps, 40 steps of {t_span / 40:g}: {bench._sustained_ms(pkg, fixed, min_reps=3):.3f} ms")
+        print(f"{name}, {n} parcels to t = {t_span:g}, reltol {a.reltol:g}: " + " | ".join(res), flush=True)
+        y0.free()
+        w_dev.free()
+    L.cloudy_plan_destroy(handle)
+
+
 def cmd_box(a, pkg, L):
     """ms per call of S steps: (a) cloudy_ssprk33_steps, (b) / (c) cloudy_box_ssprk33_steps with COAL | COND / COND, (d) the same
     steps stage by stage: two right-hand-side launches and the update on the planes (torch, on the same stream) per stage"""
@@ -502,12 +558,16 @@ def main():
     ba.add_argument("--t-span", type=float, default=5e-3)
     ba.add_argument("--reltol", type=float, default=1e-6)
     ba.add_argument("--xi", type=float, default=1e-5)
+    pa = sub.add_parser("parceladaptive")
+    pa.add_argument("--parcels", type=int, default=0)
+    pa.add_argument("--t-span", type=float, default=20.0)
+    pa.add_argument("--reltol", type=float, default=1e-6)
     hh = sub.add_parser("host")
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
     {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "adaptive": cmd_adaptive,
-     "saveat": cmd_saveat, "boxadaptive": cmd_boxadaptive,
+     "saveat": cmd_saveat, "boxadaptive": cmd_boxadaptive, "parceladaptive": cmd_parceladaptive,
      "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
