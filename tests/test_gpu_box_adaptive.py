@@ -4,7 +4,8 @@ rhs_condensation_batch (tests/test_box_adaptive_host.py holds the batches and me
 a Monodisperse mode under condensation, the fixed-step tableau (_tsit5_host) at a fine step, and cloudy_tsit5_adaptive itself.
 
 Run with `-m gpu`.  Batch sizes 1, 65 and 257: a single parcel, a partial wave past one wave, a partial workgroup past one
-workgroup."""
+workgroup of 256 threads -- the 512-thread kernel of COAL | COND on the `fixed` plan still runs a single, partly filled workgroup at
+257 (tests/test_gpu_ranked_adaptive.py runs it at 513 and 1025)."""
 import ctypes as C
 import functools
 
