@@ -137,3 +137,56 @@ def solve_rainshaft_cond_ssprk33(par, u, n_steps, xi, s, out=None, stream=None):
     _lib.check(_lib.lib().cloudy_rainshaft_cond_ssprk33_steps(plan.handle, nz, n // nz, ld, ptr, optr, sptr, sval, float(xi),
                                                               float(par.dz), float(par.dt), int(n_steps), stream))
     return out if out is not None else u
+
+
+def solve_rainshaft_tsit5_adaptive(par, u, t_span, xi=0.0, s=None, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000, out=None,
+                                   dt_dev=None, info=False, stream=None):
+    """Every column of `u` (`par.nz` cells each, stacked along the cell axis) from t = 0 to t = t_span with adaptive Tsit5 under
+    a step-size controller per COLUMN (cloudy_rainshaft_tsit5_adaptive) -- the error-controlled counterpart of
+    solve_rainshaft_ssprk33 / solve_rainshaft_cond_ssprk33.  `s` None: coalescence + sedimentation; otherwise the condensation
+    source as well, `xi` and `s` as solve_rainshaft_cond_ssprk33 takes them (`s`: a float or an (1, n) fp64 device array, one
+    supersaturation per cell).  `reltol`, `abstol`, `dt`, `max_steps` and `out` as solve_tsit5_adaptive; `dt_dev`: an
+    (1, n_columns) fp64 device array, the proposed step of every column (in/out).  Returns the state -- `u` advanced in place
+    unless `out` is given -- or with info=True (accepted, rejected, status, t_reached), one entry per column; then a column that
+    did not reach t_span raises a RuntimeError, after the call."""
+    import ctypes as C
+
+    from .box_model import ADAPTIVE_STATUS, _plan_for
+    from .device import dtype_code
+
+    plan = _plan_for(par, dtype_code(u))
+    uptr, planes, n, ld = as_device(u)
+    nz = int(getattr(par, "nz", n))
+    if n % nz:
+        raise ValueError("number of cells must be a multiple of par.nz")
+    ncol = n // nz
+    o = out if out is not None else u
+    optr, oplanes, on, old = as_device(o)
+    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
+        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    sources = _lib.SRC_COAL | (0 if s is None else _lib.SRC_COND)
+    sptr, sval = (None, 0.0) if s is None else _cell_supersaturation(s, n)
+    dptr = None
+    if dt_dev is not None:
+        dptr, dplanes, dn, _ = as_device(dt_dev)
+        if dplanes != 1 or dn != ncol or dtype_code(dt_dev) != 0:
+            raise ValueError("dt_dev must be an (1, n_columns) fp64 device array")
+    L = _lib.lib()
+    opts = _lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
+    t_arr = DeviceArray.zeros(1, max(ncol, 1)) if info else None
+    i_arr = DeviceArray.zeros(3, max(ncol, 1), dtype=np.int32) if info else None
+    _lib.check(L.cloudy_rainshaft_tsit5_adaptive(plan.handle, nz, ncol, ld, uptr, optr, sources, sptr, sval, float(xi), float(par.dz),
+                                                 float(t_span), C.byref(opts), dptr, t_arr.ptr if info else None,
+                                                 i_arr.ptr if info else None, stream))
+    if not info:
+        return o
+    _lib.check(L.cloudy_stream_synchronize(stream))
+    counts = i_arr.to_numpy()[:, :ncol]
+    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise RuntimeError(f"solve_rainshaft_tsit5_adaptive: {bad.size} of {ncol} columns did not reach t_span; the first is column "
+                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
+    return accepted, rejected, status, t_arr.to_numpy()[0, :ncol]

@@ -24,7 +24,8 @@ from .Coalescence import (CoalescenceData, NumericalPlan, Plan, get_coal_ints, g
                           kernel_func_code, numerical_plan, QUAD_CONVERGED, QUAD_FIXED, F64, F32, F32_FAST,
                           F64_RELAXED)
 from .Sedimentation import (get_sedimentation_flux, make_rainshaft_cond_rhs, make_rainshaft_rhs, rainshaft_sources,
-                            rhs_condensation, solve_rainshaft_cond_ssprk33, solve_rainshaft_ssprk33)
+                            rhs_condensation, solve_rainshaft_cond_ssprk33, solve_rainshaft_ssprk33,
+                            solve_rainshaft_tsit5_adaptive)
 from .box_model import (ODEParameters, make_box_model_rhs, rhs_coal, solve_box_ssprk33, solve_box_tsit5_adaptive, solve_ssprk33, solve_tsit5,
                         solve_tsit5_adaptive, solve_tsit5_adaptive_saveat)
 from .parcel import ParcelParams, parcel_rhs, solve_parcel_ssprk33, solve_parcel_tsit5_adaptive

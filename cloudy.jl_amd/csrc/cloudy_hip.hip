@@ -278,6 +278,20 @@ JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, boo
     return JIT_UNITS;
 }
 
+// The adaptive column unit that serves columns of nz cells, picked as pick_rainshaft picks among its own sizes (jit_column_adaptive_part,
+// then every smaller size that still holds a column and fits the LDS).  cond: the kernel with the condensation source.
+JitUnit pick_column_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, bool cond) {
+    if (!plan->jit_on || nz < 1 || nz > 1024) return JIT_UNITS;
+    const int pref = jit_column_adaptive_part(plan->h, nz, n_columns);
+    bool reached = false;
+    for (int bs : {1024, 512, 256}) {
+        reached = reached || bs == pref;
+        const JitUnit u = jit_column_adaptive_unit(bs);
+        if (reached && jit_column_adaptive_fits(plan->h, bs, nz) && jit_unit(plan, u).k[cond ? COLAD_COALCOND : COLAD_COAL].fn != nullptr) return u;
+    }
+    return JIT_UNITS;
+}
+
 // Whether the calls with the condensation source take the stage-by-stage form because NO column unit could hold the columns
 // (whatever compiles): MovingThreshold plans, columns taller than a workgroup, LDS rows that fit no workgroup size that holds a
 // column.  Every other case belongs to the units compiled for the plan, and without them the call is refused (there are no
@@ -324,6 +338,7 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_PARCEL_TSIT5_ADAPTIVE:
     case OP_PARCEL_TSIT5_SAVEAT: return JIT_PARCEL_ADAPTIVE;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
+    case OP_RAINSHAFT_TSIT5_ADAPTIVE: return pick_column_adaptive(plan, r.nz, r.n / r.nz, (r.sources & SRC_COND) != 0);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
         return rainshaft_cond_staged(h, r.nz) ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, r.op == OP_RAINSHAFT_COND_RHS, true);
@@ -354,7 +369,9 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
     case JIT_DIAG:
         return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
                : r.op == OP_COND      ? DIAG_COND_EVAP   : r.op == OP_NQ        ? DIAG_STANDARD_NQ : DIAG_COAL_INTS;
-    default: return jit_is_column(u) && (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) ? COL_RHS : 0;
+    default:
+        if (jit_is_column_adaptive(u)) return (r.sources & SRC_COND) ? COLAD_COALCOND : COLAD_COAL;
+        return jit_is_column(u) && (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) ? COL_RHS : 0;
     }
 }
 
@@ -584,6 +601,10 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         return refuse_without_unit(plan, JIT_PARCEL_ADAPTIVE, "cloudy_parcel_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) "
                                                               "and has no ahead-of-time instance: step such a parcel stage by stage with "
                                                               "cloudy_cond_evap (and cloudy_coal_rhs) and cloudy_parcel_thermo_host");
+    if (r.op == OP_RAINSHAFT_TSIT5_ADAPTIVE)
+        return refuse_without_unit(plan, jit_column_adaptive_unit(jit_column_adaptive_part(plan->h, r.nz, r.n / r.nz)),
+                                   "cloudy_rainshaft_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and has no ahead-of-time "
+                                   "instance: cloudy_rainshaft_cond_ssprk33_steps steps such columns with a fixed dt");
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
@@ -1641,6 +1662,58 @@ int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size
     r.coef = cond_coef(plan, xi);
     r.s_scalar = s;
     r.s_dev = s_dev;
+    return run(plan, r);
+}
+
+int cloudy_rainshaft_tsit5_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev, void *u_out_dev,
+                                    int sources, const double *s_dev, double s, double xi, double dz, double t_span,
+                                    const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream) {
+    const size_t n = nz * n_columns;
+    AdaptiveOpts c;
+    // the checks of cloudy_tsit5_adaptive in its order, then the column's, then the plan and what it must carry
+    int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c, [&] {
+        if (sources != SRC_COAL && sources != (SRC_COAL | SRC_COND))
+            return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COAL or CLOUDY_SRC_COAL | CLOUDY_SRC_COND", sources);
+        if (nz < 1 || !(dz > 0)) return fail(CLOUDY_EINVAL, "nz must be >= 1 and dz positive");
+        if (!(xi == xi)) return fail(CLOUDY_EINVAL, "xi must not be NaN");
+        return (int)CLOUDY_OK;
+    });
+    if (rc) return rc;
+    // the deliberate limits: refused before anything is written, with the fixed-step integrator that serves the case
+    static const char kFixed[] = "cloudy_rainshaft_cond_ssprk33_steps steps such columns with a fixed dt";
+    const HostPlan &h = plan->h;
+    if (h.coal_style == CLOUDY_NUMERICAL_COAL)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_rainshaft_tsit5_adaptive: %s (nor by cloudy_rainshaft_cond_ssprk33_steps, the fixed-step "
+                                         "column integrator)", kNoNumericalColumns);
+    if ((rc = check_velocity(plan, false))) return rc;
+    if (h.mode == MODE_MOVING)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_rainshaft_tsit5_adaptive is not built for MovingThreshold plans: %s", kFixed);
+    if (h.dtype == CLOUDY_F32_FAST)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_rainshaft_tsit5_adaptive serves CLOUDY_F64, CLOUDY_F64_RELAXED and CLOUDY_F32 plans (state and "
+                                         "step control in fp64 registers; CLOUDY_F32_FAST is the single-pass operator's mode): %s", kFixed);
+    if (nz > 1024)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_rainshaft_tsit5_adaptive keeps a column inside one workgroup (nz = %zu > 1024): %s", nz, kFixed);
+    if (jit_column_adaptive_part(h, nz, n_columns) == 0)
+        return fail(CLOUDY_EUNSUPPORTED, "cloudy_rainshaft_tsit5_adaptive: the LDS rows of this plan fit no workgroup that holds a column of "
+                                         "%zu cells: %s", nz, kFixed);
+    if (!plan->jit_on)
+        return refuse_without_unit(plan, JIT_COLAD256, "cloudy_rainshaft_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and "
+                                                       "has no ahead-of-time instance: cloudy_rainshaft_cond_ssprk33_steps steps such "
+                                                       "columns with a fixed dt");
+    if (n == 0) return CLOUDY_OK;
+    LaunchReq r(OP_RAINSHAFT_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
+    r.rainshaft = 1;
+    r.sources = sources;
+    r.nz = nz;
+    r.dz = dz;
+    r.coef = cond_coef(plan, xi);
+    r.s_scalar = s;
+    r.s_dev = s_dev;
+    r.dt = t_span;
+    r.adaptive = &c;
+    r.dt_dev = dt_dev;
+    r.t_dev = t_dev;
+    r.info_dev = info_dev;
     return run(plan, r);
 }
 

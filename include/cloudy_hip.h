@@ -620,6 +620,43 @@ int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size
                                         const void *u_in_dev, void *u_out_dev, const double *s_dev, double s, double xi,
                                         double dz, double dt, int n_steps, void *stream);
 
+/* Per-COLUMN adaptive Tsit5 for the rainshaft columns: every column of nz cells -- one ODE system, its cells couple through the
+ * upwind flux -- from t = 0 to t_span under a step-size controller of its own (csrc/adaptive_column.hpp).  The sedimentation CFL
+ * limit dz / v(x), the coalescence rate of the cloud slab and evaporation below cloud base differ from column to column; the
+ * fixed-step integrators above take one dt for the batch.  Everything shared with cloudy_tsit5_adaptive -- the stages, err and
+ * sc, the controller and its constants, the last-step rule, the first-step rule, the statuses 0 / 1 / 2, max_steps -- is stated
+ * in its comment and not again here; what follows is what a column changes.
+ *   right-hand side   one evaluation of the column right-hand side on a CLAMPED COPY of its argument: sources = CLOUDY_SRC_COAL is
+ *                coalescence + sedimentation, what cloudy_rainshaft_rhs computes; CLOUDY_SRC_COAL | CLOUDY_SRC_COND adds get_cond_evap
+ *                at the cell's supersaturation, what cloudy_rainshaft_cond_rhs computes, and s_dev (one fp64 value per cell, or
+ *                NULL for the scalar `s`), s and xi mean what they mean there.  Any other `sources`: CLOUDY_EINVAL.
+ *   clamping     the stage arguments are not mutated.  u is clamped to >= 0 on load and u_new before k7 = f(u_new); the clamped
+ *                u_new is what the error scale, the acceptance and the store see: what the reference's in-place clamp
+ *                (rainshaft_helpers.jl:52) does to the state under a FSAL method.  The returned state is therefore clamped, as
+ *                cloudy_rainshaft_ssprk33_steps returns it.
+ *   state units  physical for every plan: abstol_i = abstol norm_i, as the thresholded per-parcel kernels have it.
+ *   error norm   per column: EEst = sqrt(sum over the column's nz cells and the planes a mode has of (err / sc)^2 / (nz n_moms));
+ *                empty cells count in the mean.  Hairer's first-step guess uses the same two column means.
+ *   outputs      one controller state per column: dt_dev [n_columns] (in/out), t_dev [n_columns] and info_dev [3][n_columns]
+ *                (accepted, rejected, status) hold one entry per COLUMN; each may be NULL.  A column's result depends neither on
+ *                the other columns of the batch nor on the workgroup size.
+ * t_span = 0 copies the input to the output with status 0 and zero counts; n_columns = 0 returns CLOUDY_OK at once; u_out_dev
+ * may equal u_in_dev.
+ * Argument checks precede any device work, the plan last (CLOUDY_EINVAL, the message names the argument): those of
+ * cloudy_tsit5_adaptive for opts and t_span, ld < nz * n_columns and NULL buffers; then `sources`, nz < 1, dz <= 0, xi NaN; then
+ * the plan, which must carry terminal-velocity terms.
+ * Served: AnalyticalCoalStyle plans whose thresholds are all Inf, or FixedThreshold plans; CLOUDY_F64, CLOUDY_F64_RELAXED and
+ * CLOUDY_F32 planes (state and control in fp64 registers either way); nz up to 1024, provided a workgroup can hold a column.
+ * Deliberate limits, each CLOUDY_EUNSUPPORTED with a message that names cloudy_rainshaft_cond_ssprk33_steps as the alternative,
+ * nothing written: MovingThreshold plans; NumericalCoalStyle plans; CLOUDY_F32_FAST planes; nz > 1024, or a plan whose LDS rows
+ * fit no workgroup that holds a column; plans without plan-time compilation (the kernels -- cloudy_jit_column_adaptive_*, one
+ * unit per workgroup size of 256 / 512 / 1024 threads, picked by the rule of cloudy_rainshaft_rhs -- have no ahead-of-time
+ * instance).  Dense output at save times and a stage-by-stage form for taller columns are not built. */
+int cloudy_rainshaft_tsit5_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev,
+                                    void *u_out_dev, int sources, const double *s_dev, double s, double xi, double dz,
+                                    double t_span, const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev,
+                                    int32_t *info_dev, void *stream);
+
 /* sums_dev[q] = sum over parcels of plane q (fp64 accumulate); `planes` planes are reduced.
  * The multi-GPU conservation check all-reduces these nmom doubles (RCCL), see INTEGRATION.md. */
 int cloudy_moment_sums(const cloudy_plan *plan, size_t n_parcels, size_t ld, int planes, const void *arr_dev,

@@ -659,6 +659,39 @@ function solve_rainshaft_cond_ssprk33!(u, plan::Plan, nz, dz, dt, n_steps, xi, s
 end
 
 """
+    solve_rainshaft_tsit5_adaptive!(u, plan, nz, dz, t_span; xi = 0.0, s = nothing, reltol = 1e-6, abstol = 1e-9, dt = 0.0,
+                                    max_steps = 10000, dt_dev = nothing, t_dev = nothing, info_dev = nothing, stream = nothing,
+                                    sync = true)
+
+Every column of `u` (`nz` cells each) from t = 0 to `t_span` with adaptive Tsit5 under a step-size controller per COLUMN
+(`cloudy_rainshaft_tsit5_adaptive`), the error-controlled counterpart of `solve_rainshaft_ssprk33!` /
+`solve_rainshaft_cond_ssprk33!`.  `s === nothing`: coalescence + sedimentation; otherwise the condensation source as well, `xi`
+and `s` as `solve_rainshaft_cond_ssprk33!` takes them.  Controller, statuses and options as `solve_tsit5_adaptive!`, the error norm
+a mean over the column's cells and planes; the optional device vectors `dt_dev`, `t_dev` (`n_columns` `Float64`) and `info_dev`
+(`3 n_columns` `Int32`: accepted, rejected, status) hold one entry per column.  Returns `u`, clamped to >= 0.
+"""
+function solve_rainshaft_tsit5_adaptive!(u, plan::Plan, nz, dz, t_span; xi = 0.0, s = nothing, reltol = 1e-6, abstol = 1e-9, dt = 0.0,
+                                         max_steps = 10000, dt_dev = nothing, t_dev = nothing, info_dev = nothing, stream = nothing,
+                                         sync::Bool = true)
+    n, ld = batch_shape(u, plan.nmom)
+    st = stream === nothing ? current_stream() : stream
+    o = AdaptiveOpts()
+    o.reltol, o.abstol, o.dt_init, o.max_steps = reltol, abstol, dt, max_steps
+    sources = s === nothing ? SRC_COAL : (SRC_COAL | SRC_COND)
+    s_dev = (s === nothing || s isa Number) ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(s))
+    s_val = s isa Number ? Float64(s) : 0.0
+    dptr = dt_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(dt_dev))
+    tptr = t_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(t_dev))
+    iptr = info_dev === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(info_dev))
+    check(ccall((:cloudy_rainshaft_tsit5_adaptive, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Cdouble,
+                 Ref{AdaptiveOpts}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cvoid}),
+                plan.handle, nz, n ÷ nz, ld, pointer(u), pointer(u), sources, s_dev, s_val, xi, dz, t_span, o, dptr, tptr, iptr, st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return u
+end
+
+"""
     rainshaft_cond_rhs!(dm, flux, m, plan, nz, dz, xi, s; stream = nothing, sync = true)
 
 One evaluation of that right-hand side on device arrays (`cloudy_rainshaft_cond_rhs`): `dm` receives the tendency of the

@@ -1,0 +1,354 @@
+"""CPU-only checks of the per-column adaptive Tsit5 for rainshaft columns (cloudy_rainshaft_tsit5_adaptive, csrc/adaptive_column.hpp):
+a NumPy restatement of its rules (`adaptive_tsit5_column_host`: one controller per column, the clamp of u and u_new, the column
+norm; the tableau and the controller constants are those of test_tsit5_adaptive_host), the restatement against the per-parcel one
+for columns of one cell, the batch the GPU tests use -- picked on the oracle alone -- with the range of its attempts and the
+sensitivity of its accept / reject decisions to the last bit of the right-hand side, the symbol in the header, the ctypes table,
+the Julia shim and the Python wrapper, every argument check of the C entry point, and the plan-time units compiling for gfx950
+without a device.
+
+tests/test_gpu_column_adaptive.py runs the same restatement on the oracle's column right-hand side as the device's reference."""
+import ctypes as C
+import functools
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import bench
+from test_gpu_column_sources import DZ, GOLOVIN, NCOL, NZ, VEL, XI, column_set, supersaturation
+from test_host_abi import INF, ROOT, _c_prototypes, _julia_ccalls
+from test_tsit5_adaptive_host import (A_ROWS, BETA1, BETA2, BTILDE, DONE, DT_MIN, EPS, GAMMA, MAX_STEPS, QMAX, QMIN, QOLD0,
+                                      adaptive_tsit5_host, default_opts, last_bit_noise, plane_norms)
+
+NAME = "cloudy_rainshaft_tsit5_adaptive"
+
+
+def adaptive_tsit5_column_host(rhs, u0, nz, t_span, opts):
+    """Every column of u0 (planes, nz * n_columns; column c holds cells c nz .. (c + 1) nz) from t = 0 to t_span.  rhs(u) -> du/dt
+    on the whole batch, physical units, evaluated on a clamped copy of its argument by the caller's function.  opts: reltol,
+    abstol, max_steps; dt (None / 0: automatic, a float, or one value per column); plane_norms (planes,): the plan's mom_norms
+    (the state is physical: abstol_i = abstol norm_i).  Returns dict(u, t, dt, accepted, rejected, status, evals), one entry per
+    column but for u."""
+    reltol, abstol, max_steps = float(opts["reltol"]), float(opts["abstol"]), int(opts["max_steps"])
+    norms = np.asarray(opts["plane_norms"], dtype=np.float64)[:, None]
+    planes, n = u0.shape
+    ncol = n // nz
+    assert ncol * nz == n
+    count = planes * nz
+    cells = lambda x: np.repeat(x, nz)   # noqa: E731  a column's value on its cells
+
+    def column_sum(x):
+        """(planes, n) -> (ncol,): the planes of a cell first, then the column's cells in cell order"""
+        part = x.sum(axis=0).reshape(ncol, nz)
+        s = np.zeros(ncol)
+        for j in range(nz):
+            s = s + part[:, j]
+        return s
+
+    t = np.zeros(ncol)
+    accepted, rejected, status = np.zeros(ncol, np.int64), np.zeros(ncol, np.int64), np.zeros(ncol, np.int64)
+    evals = np.zeros(ncol, np.int64)
+    if not t_span > 0:
+        return dict(u=u0.copy(), t=t, dt=np.zeros(ncol), accepted=accepted, rejected=rejected, status=status, evals=evals)
+    with np.errstate(all="ignore"):
+        u = np.where(u0 < 0, 0.0, u0)   # the clamp of the first evaluation, in place in the reference
+        atol = abstol * norms * np.ones_like(u)
+        k1 = rhs(u)
+        evals += 1
+        dt0 = opts.get("dt")
+        dt = np.zeros(ncol) if dt0 is None else np.broadcast_to(np.asarray(dt0, dtype=np.float64), (ncol,)).copy()
+        auto = ~((dt > 0) & np.isfinite(dt))
+        sc = atol + reltol * np.abs(u)
+        d0, d1 = np.sqrt(column_sum((u / sc) ** 2) / count), np.sqrt(column_sum((k1 / sc) ** 2) / count)
+        dt = np.where(auto, np.where(d1 == 0, t_span, 0.01 * d0 / d1), dt)
+        dt = np.where(dt > t_span, t_span, dt)
+        qold = np.full(ncol, QOLD0)
+        active = np.ones(ncol, bool)
+        t_last, dt_min = t_span * (1 - 4 * EPS), 1e-14 * t_span
+        while True:
+            over = active & (accepted + rejected >= max_steps)
+            status[over], active[over] = MAX_STEPS, False
+            small = active & (~(dt >= dt_min) | ~np.isfinite(dt))
+            status[small], active[small] = DT_MIN, False
+            if not active.any():
+                break
+            last = t + dt >= t_last
+            h = np.where(last, t_span - t, dt)
+            hc = cells(h)
+            k = [k1]
+            for row in A_ROWS[:-1]:
+                k.append(rhs(u + hc * sum(a * ki for a, ki in zip(row, k))))
+            u_new = u + hc * sum(a * ki for a, ki in zip(A_ROWS[-1], k))
+            u_new = np.where(u_new < 0, 0.0, u_new)
+            k.append(rhs(u_new))
+            evals[active] += 6
+            err = hc * sum(b * ki for b, ki in zip(BTILDE, k))
+            sc = atol + reltol * np.maximum(np.abs(u), np.abs(u_new))
+            eest = np.sqrt(column_sum((err / sc) ** 2) / count)
+            fin = np.isfinite(eest)
+            q11 = np.where(eest > 0, np.where(fin, eest, 1.0) ** BETA1, 0.0)
+            q = np.clip(q11 / qold ** BETA2 / GAMMA, 1 / QMAX, 1 / QMIN)
+            acc = active & fin & (eest <= 1)
+            rej = active & ~acc
+            dt_acc = np.maximum(h / q, np.minimum(dt, dt / q))
+            dt_rej = np.where(fin, h / np.minimum(1 / QMIN, q11 / GAMMA), h / 5.0)
+            t = np.where(acc, np.where(last, t_span, t + h), t)
+            dt = np.where(acc, dt_acc, np.where(rej, dt_rej, dt))
+            qold = np.where(acc, np.maximum(eest, QOLD0), qold)
+            u = np.where(cells(acc), u_new, u)
+            k1 = np.where(cells(acc), k[6], k1)
+            accepted += acc
+            rejected += rej
+            active &= ~(acc & last)
+    return dict(u=u, t=t, dt=dt, accepted=accepted, rejected=rejected, status=status, evals=evals)
+
+
+def column_rhs_host(oracle, op, nz, dz, xi=0.0, s=None):
+    """-> f(x): the column right-hand side on a clamped COPY of x -- oracle.rainshaft_cell_batch, the upwind divergence, and (s not
+    None) oracle.rhs_condensation_batch: the f of test_gpu_column_sources.oracle_stepping without the in-place mutation"""
+    def f(x):
+        x = np.where(x < 0, 0.0, x)
+        nmom, n = x.shape
+        cs, sf = oracle.rainshaft_cell_batch(op, x)
+        fl = np.concatenate([sf.reshape(nmom, n // nz, nz), np.zeros((nmom, n // nz, 1))], axis=2)
+        out = cs + (-(fl[:, :, 1:] - fl[:, :, :-1]) / dz).reshape(nmom, n)
+        return out if s is None else out + oracle.rhs_condensation_batch(op, xi, s, x)
+
+    return f
+
+
+# ---- the batch (shared with the GPU tests): picked on the oracle alone
+# the 20-cell, dz = 150 columns of test_gpu_column_sources.column_set, column c scaled by 10^(c / 26 - 1 / 2): amplitudes over a
+# decade (times the factors the set has already), supersaturation() on.  T_SPAN: at reltol = 1e-6 the columns take 7 .. 22
+# (gamma_mixture) and 8 .. 15 (single_gamma) attempts from the automatic first step.  Under this controller these columns reject
+# nothing from there (scanned on the oracle: t_span 5 .. 400, reltol 1e-3 .. 1e-6, amplitudes down to a thirtieth: no rejection),
+# so the batch is run a second time from a caller's first step DT0 = t_span / 2, which the denser columns reject up to three
+# times: 3 .. 16 and 3 .. 8 attempts (test_the_batch_of_the_gpu_tests asserts the ranges and the rejections and prints the counts).
+T_SPAN = {"gamma_mixture": 12.0, "single_gamma": 12.0}
+DT0 = 6.0
+FIRST = {"auto": None, "dt0": DT0}
+CASES = ("gamma_mixture", "single_gamma")
+
+
+def oracle_case(oracle, case):
+    """-> (oracle params, dist_types, thresholds, amplitudes) of the reference's two column plans (test_gpu_column_sources.reference_case)"""
+    if case == "gamma_mixture":
+        dist_types, thr, amp = [1, 1], (2e-10, INF), np.array([1e7, 1e-3, 2e-13, 0.0, 0.0, 0.0])
+    else:
+        dist_types, thr, amp = [1], (INF,), np.array([1e7, 1e-3, 2e-13])
+    N = len(dist_types)
+    kc = np.broadcast_to(np.asarray(GOLOVIN, dtype=np.float64), (N, N, 2, 2)).copy()
+    return oracle.make_params(dist_types, kc, thr, norms=bench.NORMS, vel=VEL), dist_types, thr, amp
+
+
+def column_batch(amp, ncol=NCOL):
+    u0 = column_set(amp)
+    scale = 10.0 ** (np.arange(NCOL) / (NCOL - 1) - 0.5)
+    return np.ascontiguousarray((u0 * np.repeat(scale, NZ))[:, : ncol * NZ])
+
+
+def column_reference(oracle, case, reltol=1e-6, max_steps=10000, dt=None, t_span=None, cond=True, ncol=NCOL, perturb=None, xi=XI, u0=None):
+    """-> (u0, s, the restatement's result) of the batch"""
+    op, dist_types, _, amp = oracle_case(oracle, case)
+    u0 = column_batch(amp, ncol) if u0 is None else u0
+    s = supersaturation(NZ, DZ, NCOL)[: u0.shape[1]]
+    f = column_rhs_host(oracle, op, NZ, DZ, xi, s if cond else None)
+    rhs = f if perturb is None else (lambda u: f(u) * perturb(u.shape))
+    res = adaptive_tsit5_column_host(rhs, u0, NZ, T_SPAN[case] if t_span is None else t_span,
+                                     dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, dt=dt,
+                                          plane_norms=plane_norms((3,) * len(dist_types))))
+    return u0, s, res
+
+
+@functools.lru_cache(maxsize=None)
+def column_reference_cached(case, first="auto", reltol=1e-6, max_steps=10000, cond=True):
+    """the unperturbed reference of the batch, computed once per session and shared (treat the arrays as read-only)"""
+    from oracle import cloudy_oracle
+
+    u0, s, res = column_reference(cloudy_oracle, case, reltol=reltol, max_steps=max_steps, cond=cond, dt=FIRST[first])
+    for a in (u0, s) + tuple(res.values()):
+        a.setflags(write=False)
+    return u0, s, res
+
+
+# ---- 1. the restatement against the per-parcel one
+def test_columns_of_one_cell_are_the_per_parcel_restatement(oracle):
+    """nz = 1: the column norm is the parcel's, nothing couples the cells, and -- on an input on which the clamp never acts (a
+    Golovin box: M0 falls towards a positive limit, M1 stays, M2 grows) -- the restatement reproduces
+    adaptive_tsit5_host(normalised=False) bit for bit: state, t, dt and counts."""
+    from test_tsit5_adaptive_host import GOLOVIN_KC, GOLOVIN_T, golovin_batch
+
+    op = oracle.make_params([oracle.GAMMA], np.array(GOLOVIN_KC), (INF,), norms=bench.NORMS)
+    u0 = golovin_batch("gamma", 33)
+    seen = []
+
+    def rhs(u):
+        seen.append(float(u.min()))
+        return oracle.rhs_coal_batch(op, u)
+
+    o = dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=plane_norms((3,)), dt=GOLOVIN_T / 6)   # (a first step the dense parcels reject)
+    want = adaptive_tsit5_host(rhs, u0, GOLOVIN_T, dict(o, normalised=False))
+    got = adaptive_tsit5_column_host(rhs, u0, 1, GOLOVIN_T, o)
+    assert min(seen) > 0.0                              # the clamp never acted, in either run
+    assert want["rejected"].sum() > 0 and want["accepted"].max() > 4 * want["accepted"].min()
+    for key in ("u", "t", "dt", "accepted", "rejected", "status", "evals"):
+        assert np.array_equal(got[key], want[key]), key
+
+
+# ---- 2. the batch of the GPU tests
+@pytest.mark.parametrize("first", sorted(FIRST))
+@pytest.mark.parametrize("case", CASES)
+def test_the_batch_of_the_gpu_tests(oracle, case, first):
+    """On the restatement alone: every column reaches t_span in between 3 and 40 attempts, from the caller's first step there are
+    rejections, and the counts differ between columns; with every entry of the right-hand side multiplied by 1 +- 1e-15 NO column changes its
+    (accepted, rejected) -- the GPU tests compare them column by column, and the device's right-hand side differs from the
+    oracle's in the last bits -- and the end state of the batch moves by no more than 1e-10 of the plane maxima: a reference
+    resolves the 1e-9 the GPU tests ask the device for only if its own response to the last bit of its right-hand side is well
+    below, a tenth (measured: 3.7e-11 on the thresholded plan, whose nearly empty rain mode amplifies it)."""
+    u0, s, base = column_reference_cached(case, first)
+    att = base["accepted"] + base["rejected"]
+    print(f"{case}, first step {first}: t_span = {T_SPAN[case]}, attempts {att.min()} .. {att.max()}, rejected {base['rejected'].sum()} in "
+          f"{(base['rejected'] > 0).sum()} columns; accepted {base['accepted'].tolist()}")
+    assert np.all(base["status"] == DONE) and np.all(base["t"] == T_SPAN[case])
+    assert att.min() >= 3 and att.max() <= 40
+    assert base["rejected"].sum() >= (1 if first == "dt0" else 0)
+    assert len(set(att[:25].tolist())) > 1              # (the 25 columns of the first 512-thread workgroup)
+    assert base["u"].min() >= 0.0
+    _, _, pert = column_reference(oracle, case, perturb=last_bit_noise(1), dt=FIRST[first])
+    changed = (base["accepted"] != pert["accepted"]) | (base["rejected"] != pert["rejected"])
+    moved = (np.abs(pert["u"] - base["u"]).max(axis=1) / (np.abs(base["u"]).max(axis=1) + 1e-300)).max()
+    print(f"{case}: {int(changed.sum())} of {NCOL} columns change (accepted, rejected) under last-bit noise of the right-hand side; "
+          f"the end state moves by {moved:.1e} of the plane maxima")
+    assert not changed.any(), np.flatnonzero(changed)
+    assert moved <= 1e-10
+    # the proposed next step: from the caller's first step the reference resolves the 1e-6 the GPU tests ask for (a tenth: 1e-7;
+    # measured 1e-9).  From the automatic first step it does not: the first steps are so short that their error estimates are
+    # rounding noise, and q = EEst^(7/50) of such a step moves dt by up to 7e-3 -- which is why the GPU tests compare dt_dev on the
+    # runs from DT0 and hold the automatic runs to counts and state.
+    dt_moved = (np.abs(pert["dt"] - base["dt"]) / base["dt"]).max()
+    print(f"{case}, first step {first}: dt moves by {dt_moved:.1e} relative")
+    assert dt_moved <= (1e-7 if first == "dt0" else 5e-2)
+
+
+# ---- 3. ABI
+ARGS = ["ptr", "size_t", "size_t", "size_t", "ptr", "ptr", "int", "ptr", "double", "double", "double", "double", "ptr", "ptr", "ptr", "ptr",
+        "ptr"]
+
+
+def test_symbol_in_header_ctypes_table_julia_shim_and_python(cloudy):
+    protos = _c_prototypes()
+    assert protos[NAME] == ("int", ARGS)
+    res, argtypes = cloudy._lib.SYMBOLS[NAME]
+    assert res is C.c_int and len(argtypes) == len(ARGS) and hasattr(cloudy.lib(), NAME)
+    ctype_of = {"ptr": (C.c_void_p, C.POINTER(cloudy._lib.AdaptiveOptsC)), "size_t": (C.c_size_t,), "int": (C.c_int,), "double": (C.c_double,)}
+    for a, c in zip(argtypes, ARGS):
+        assert a in ctype_of[c], (a, c)
+    src = open(os.path.join(ROOT, "julia", "CloudyHIP.jl")).read()
+    calls = [c for c in _julia_ccalls(src) if c[0] == NAME]
+    assert len(calls) == 1 and calls[0][1] == "Cint" and len(calls[0][2]) == len(ARGS)
+    assert "function solve_rainshaft_tsit5_adaptive!(u, plan::Plan, nz, dz, t_span;" in src
+    assert "solve_rainshaft_tsit5_adaptive" in cloudy.__all__
+    sig = inspect.signature(cloudy.solve_rainshaft_tsit5_adaptive).parameters
+    assert list(sig) == ["par", "u", "t_span", "xi", "s", "reltol", "abstol", "dt", "max_steps", "out", "dt_dev", "info", "stream"]
+    assert (sig["xi"].default, sig["s"].default, sig["reltol"].default, sig["abstol"].default) == (0.0, None, 1e-6, 1e-9)
+    assert (sig["dt"].default, sig["max_steps"].default, sig["out"].default, sig["dt_dev"].default) == (None, 10000, None, None)
+    assert sig["info"].default is False
+    header = open(os.path.join(ROOT, "include", "cloudy_hip.h")).read()
+    assert "cloudy_rainshaft_cond_ssprk33_steps as the alternative" in header and "[3][n_columns]" in header
+
+
+def test_argument_checks_answer_einval_with_a_message(cloudy):
+    L, E = cloudy.lib(), cloudy._lib
+    nan, inf = float("nan"), float("inf")
+    dummy = C.c_void_p(64)   # never dereferenced: every check below precedes any device work
+
+    def call(opts="default", nz=20, ncol=2, ld=40, t_span=1.0, u_in=dummy, u_out=dummy, sources=3, xi=1e-8, dz=150.0, **kw):
+        o = default_opts(cloudy, **kw) if opts == "default" else opts
+        return L.cloudy_rainshaft_tsit5_adaptive(None, nz, ncol, ld, u_in, u_out, sources, None, 0.01, xi, dz, t_span,
+                                                 None if o is None else C.byref(o), None, None, None, None)
+
+    def msg():
+        return L.cloudy_last_error().decode()
+
+    assert call() == E.EINVAL and msg() == "plan is NULL"          # everything else is in order
+    assert call(sources=1) == E.EINVAL and msg() == "plan is NULL"
+    assert call(ncol=0, ld=0, u_in=None, u_out=None) == E.EINVAL and msg() == "plan is NULL"
+    assert call(opts=None) == E.EINVAL and msg() == "opts is NULL"
+    short = default_opts(cloudy)
+    short.struct_size -= 8
+    assert call(opts=short) == E.EINVAL and "struct_size" in msg()
+    for bad in (0.0, -1e-6, nan, inf):
+        assert call(reltol=bad) == E.EINVAL and "reltol" in msg(), bad
+    for bad in (-1e-9, nan, inf):
+        assert call(abstol=bad) == E.EINVAL and "abstol" in msg(), bad
+    assert call(abstol=0.0) == E.EINVAL and msg() == "plan is NULL"
+    for bad in (-1.0, nan, inf):
+        assert call(dt_init=bad) == E.EINVAL and "dt_init" in msg(), bad
+    for bad in (-1.0, nan, inf, -inf):
+        assert call(t_span=bad) == E.EINVAL and "t_span" in msg(), bad
+    assert call(t_span=0.0) == E.EINVAL and msg() == "plan is NULL"
+    for bad in (0, -1, 1000001):
+        assert call(max_steps=bad) == E.EINVAL and "max_steps" in msg(), bad
+    assert call(ld=39) == E.EINVAL and "ld (39) must be >= n_parcels (40)" in msg()
+    assert call(u_in=None) == E.EINVAL and msg() == "device buffer is NULL"
+    assert call(u_out=None) == E.EINVAL and msg() == "device buffer is NULL"
+    for bad in (0, 2, 4, -1):                           # CLOUDY_SRC_COND alone is not a column right-hand side
+        assert call(sources=bad) == E.EINVAL and "sources" in msg(), bad
+    assert call(nz=0, ncol=2, ld=40) == E.EINVAL and "nz" in msg()
+    for bad in (0.0, -150.0, nan):
+        assert call(dz=bad) == E.EINVAL and "dz" in msg(), bad
+    assert call(xi=nan) == E.EINVAL and "xi" in msg()
+    assert call(xi=0.0) == E.EINVAL and msg() == "plan is NULL"
+
+
+# ---- 4. the plan-time units
+def _units(tmp_path):
+    return [f for f in sorted(os.listdir(tmp_path)) if f.endswith(".hip") and " cloudy_jit_column_adaptive_" in open(tmp_path / f).read()]
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_adaptive_column_units_compile_without_a_gpu(cloudy, case, tmp_path, monkeypatch):
+    """cloudy_jit_selfcheck compiles every unit the runtime could request for a plan: for the reference's two column plans that
+    includes one adaptive column unit per workgroup size, each with the kernel without and the kernel with the condensation
+    source as instances of column_tsit5_adaptive_body; kept through CLOUDY_HIP_JIT_DUMP, they name adaptive_column.hpp, define no
+    kernel of another unit, and their code objects exist."""
+    monkeypatch.setenv("CLOUDY_HIP_JIT_DUMP", str(tmp_path))
+    L = cloudy.lib()
+    nm = 1 if case == "single_gamma" else 2
+    d, keep = cloudy.Plan.make_desc([1] * nm, np.array(GOLOVIN), (2e-10, INF)[2 - nm:], bench.NORMS, 0, vel=VEL)
+    assert L.cloudy_jit_selfcheck(C.byref(d), b"gfx950") == 0, L.cloudy_last_error().decode()
+    units = _units(tmp_path)
+    assert len(units) == 3, units
+    mode = "MODE_ALLINF" if nm == 1 else "MODE_FIXED"
+    tails = set()
+    for u in units:
+        text = open(tmp_path / u).read()
+        m = re.search(r" cloudy_jit_column_adaptive_coal_n%dp2_f64(_b512|_b1024|)\(" % nm, text)
+        assert m, u
+        tails.add(m.group(1))
+        assert " cloudy_jit_column_adaptive_coalcond_n%dp2_f64%s(" % (nm, m.group(1)) in text
+        bs = m.group(1)[2:] or "256"
+        assert text.count(f"__launch_bounds__({bs})") == 2
+        assert re.search(r"column_tsit5_adaptive_body<%d, 2, cloudy::%s, double, true, %s, false>" % (nm, mode, bs), text)
+        assert re.search(r"column_tsit5_adaptive_body<%d, 2, cloudy::%s, double, true, %s, true>" % (nm, mode, bs), text)
+        assert '#include "adaptive_column.hpp"' in text and "SediArgs kS" in text
+        assert "cloudy_jit_rainshaft" not in text and "cloudy_jit_adaptive_tsit5" not in text and "cloudy_jit_box" not in text
+        assert os.path.getsize(tmp_path / u.replace(".hip", ".co")) > 1000
+    assert tails == {"", "_b512", "_b1024"}
+
+
+@pytest.mark.parametrize("case", ["moving", "numerical"])
+def test_plans_that_are_not_served_have_no_such_unit(cloudy, case, tmp_path, monkeypatch):
+    """A MovingThreshold plan (with a velocity term) and a NumericalCoalStyle plan: none of their units defines an adaptive column
+    kernel (the entry point refuses them)."""
+    monkeypatch.setenv("CLOUDY_HIP_JIT_DUMP", str(tmp_path))
+    L = cloudy.lib()
+    if case == "numerical":
+        d = cloudy.NumericalPlan.make_desc([1, 1], cloudy.LinearKernelFunction(5e-3), bench.NORMS, 10, quad_mode=cloudy.QUAD_FIXED)
+    else:
+        d, keep = cloudy.Plan.make_desc([1, 1], np.array(GOLOVIN), (0.9, 1.0), bench.NORMS, 1, vel=VEL)
+    assert L.cloudy_jit_selfcheck(C.byref(d), b"gfx950") == 0, L.cloudy_last_error().decode()
+    assert any(f.endswith(".hip") for f in os.listdir(tmp_path))
+    assert _units(tmp_path) == []

@@ -13,6 +13,10 @@ every experiment switch of the library is an environment variable, so an A/B run
   python tools/timeit.py colcond [--nz NZ] [--cells N] [--workload cfg3b] [--steps S]
         cloudy_rainshaft_cond_ssprk33_steps on the bench's column batch: (a) cloudy_rainshaft_ssprk33_steps, (b) the three sources
         fused, (c) the sequence (b) replaces -- cloudy_rainshaft_rhs + cloudy_cond_evap + torch updates per stage
+  python tools/timeit.py coladaptive [--nz NZ] [--cells N] [--workload cfg3b] [--t-span T] [--reltol R] [--max-steps M]
+        cloudy_rainshaft_tsit5_adaptive (COAL | COND) on the batch of `colcond` to t = T (2 s), against
+        cloudy_rainshaft_cond_ssprk33_steps with the driver's 2 steps of T / 2 in the same run; statuses, attempts and the
+        active-lane fraction from the info planes, sum(attempts) / sum over workgroups of (columns x max(attempts))
   python tools/timeit.py integrators [--parcels P]
         cloudy_ssprk33_steps / cloudy_tsit5_steps of the tensor plans cfg3a, cfg3b, cfg2
   python tools/timeit.py box [--parcels P] [--steps S]
@@ -208,6 +212,42 @@ def cmd_host(a, pkg, L):
     gb = 2 * plan.nmom * 8 * n / 1e9
     print(f"cloudy_coal_rhs_host, cfg3a, {n} parcels (pageable host arrays, {gb:.2f} GB over PCIe): {best * 1e3:.1f} ms = {n / best:.3e} parcel-RHS/s "
           f"= {gb / best:.1f} GB/s of host traffic", flush=True)
+
+
+def cmd_coladaptive(a, pkg, L):
+    """ms per call on the batch of colcond: the per-column adaptive integrator to t_span, and the fixed-step integrator with the
+    driver's two steps over the same span (different amounts of work for different accuracy: the second has no error control)"""
+    nz, ncol = a.nz, max(a.cells // a.nz, 1)
+    n, xi, dz = nz * ncol, 1e-8, 150.0
+    wl = bench.make_workload(a.workload, n, seed=7)
+    plan = wl["coal_data"].plan(wl["dist_types"], vel=((50.0, 1.0 / 6),))
+    u0, out = pkg.DeviceArray.from_numpy(wl["mom"]), pkg.DeviceArray.zeros(*wl["mom"].shape)
+    z = (np.arange(nz) + 0.5) * dz
+    s = pkg.DeviceArray.from_numpy(np.tile(np.where(z >= 0.45 * z.max(), 0.03, -0.2), ncol)[None, :])
+    o = pkg._lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(o))
+    o.reltol, o.max_steps = a.reltol, a.max_steps
+    info, t_dev = pkg.DeviceArray.zeros(3, ncol, dtype=np.int32), pkg.DeviceArray.zeros(1, ncol)
+    ms_a = bench._sustained_ms(pkg, lambda: pkg._lib.check(L.cloudy_rainshaft_tsit5_adaptive(
+        plan.handle, nz, ncol, n, u0.ptr, out.ptr, 3, s.ptr, 0.0, xi, dz, a.t_span, C.byref(o), None, t_dev.ptr, info.ptr, None)), min_reps=3)
+    ms_f = bench._sustained_ms(pkg, lambda: pkg._lib.check(L.cloudy_rainshaft_cond_ssprk33_steps(
+        plan.handle, nz, ncol, n, u0.ptr, out.ptr, s.ptr, 0.0, xi, dz, a.t_span / 2, 2, None)), min_reps=3)
+    acc, rej, status = info.to_numpy()
+    att = (acc + rej).astype(np.int64)
+    # the workgroup size jit_column_adaptive_part gives this batch: 256 for a batch that fits one workgroup, else the size with the
+    # fewest idle lanes among 256 / 512 / 1024 (CLOUDY_HIP_RS_BLOCK: that size)
+    env = os.environ.get("CLOUDY_HIP_RS_BLOCK")
+    bs = int(env) if env in ("256", "512", "1024") else 256 if ncol <= 256 // nz else min(
+        (256, 512, 1024), key=lambda b: (13.7, 13.25, 14.6)[(256, 512, 1024).index(b)] * b / ((b // nz) * nz) if b >= nz else 1e300)
+    cpb = bs // nz
+    pad = (-ncol) % cpb
+    per_wg = np.concatenate([att, np.zeros(pad, np.int64)]).reshape(-1, cpb)
+    frac = float(att.sum() * nz) / float(per_wg.max(axis=1).sum() * bs)
+    print(f"{a.workload} columns nz={nz} x {ncol}, t_span {a.t_span:g}, reltol {a.reltol:g}, max_steps {a.max_steps}: "
+          f"cloudy_rainshaft_tsit5_adaptive {ms_a:.3f} ms per call | cloudy_rainshaft_cond_ssprk33_steps, 2 steps {ms_f:.3f} ms | ratio "
+          f"{ms_a / ms_f:.2f} | status 0 / 1 / 2: {int((status == 0).sum())} / {int((status == 1).sum())} / {int((status == 2).sum())} | "
+          f"attempts mean {att.mean():.1f}, max {int(att.max())}, rejected {int(rej.sum())} | active-lane fraction {frac:.3f} at {bs} "
+          f"threads  (CLOUDY_HIP_RS_BLOCK={env or 'auto'})", flush=True)
 
 
 def cmd_integrators(a, pkg, L):
@@ -537,6 +577,13 @@ def main():
     cc.add_argument("--cells", type=int, default=10_000_000)
     cc.add_argument("--workload", default="cfg3b")
     cc.add_argument("--steps", type=int, default=2)
+    ca = sub.add_parser("coladaptive")
+    ca.add_argument("--nz", type=int, default=20)
+    ca.add_argument("--cells", type=int, default=10_000_000)
+    ca.add_argument("--workload", default="cfg3b")
+    ca.add_argument("--t-span", type=float, default=2.0)
+    ca.add_argument("--reltol", type=float, default=1e-6)
+    ca.add_argument("--max-steps", type=int, default=200)
     i = sub.add_parser("integrators")
     i.add_argument("--parcels", type=int, default=0)
     b = sub.add_parser("box")
@@ -566,7 +613,7 @@ def main():
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
-    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "adaptive": cmd_adaptive,
+    {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "coladaptive": cmd_coladaptive, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "adaptive": cmd_adaptive,
      "saveat": cmd_saveat, "boxadaptive": cmd_boxadaptive, "parceladaptive": cmd_parceladaptive,
      "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
