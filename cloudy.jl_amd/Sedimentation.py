@@ -190,3 +190,71 @@ def solve_rainshaft_tsit5_adaptive(par, u, t_span, xi=0.0, s=None, reltol=1e-6, 
         raise RuntimeError(f"solve_rainshaft_tsit5_adaptive: {bad.size} of {ncol} columns did not reach t_span; the first is column "
                            f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
     return accepted, rejected, status, t_arr.to_numpy()[0, :ncol]
+
+
+def solve_rainshaft_tsit5_adaptive_saveat(par, u, t_span, t_save, xi=0.0, s=None, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000,
+                                          out=None, save_out=None, dt_dev=None, info=False, stream=None):
+    """solve_rainshaft_tsit5_adaptive with dense output (cloudy_rainshaft_tsit5_adaptive_saveat): the same integration -- every column
+    takes the steps solve_rainshaft_tsit5_adaptive takes, bit for bit, and none is clamped to a save time -- and the state of every
+    cell at the batch-wide times `t_save` (host floats in [0, t_span], strictly increasing), from the free 4th-order interpolant of
+    Tsit5 inside the accepted step that holds the time, clamped to >= 0 as the returned state is.  Returns (state, saved): the state
+    as solve_rainshaft_tsit5_adaptive returns it, and the snapshots as a DeviceArray of n_save * planes rows of the leading dimension
+    and plane type of `u` (`save_out`, where given, must be one): snapshot j, plane p is row j * planes + p; a snapshot at 0 equals
+    the input and one at t_span the final state bit for bit; a column that stopped early has NaN in the snapshots it did not reach.
+    With info=True returns (state, saved, accepted, rejected, status, t_reached), one entry per column, and raises as
+    solve_rainshaft_tsit5_adaptive does -- keep the snapshots of a run that may stop early with info=False.  Everything else as
+    solve_rainshaft_tsit5_adaptive."""
+    import ctypes as C
+
+    from .box_model import ADAPTIVE_STATUS, _plan_for
+    from .device import dtype_code
+
+    plan = _plan_for(par, dtype_code(u))
+    uptr, planes, n, ld = as_device(u)
+    nz = int(getattr(par, "nz", n))
+    if n % nz:
+        raise ValueError("number of cells must be a multiple of par.nz")
+    ncol = n // nz
+    o = out if out is not None else u
+    optr, oplanes, on, old = as_device(o)
+    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
+        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    sources = _lib.SRC_COAL | (0 if s is None else _lib.SRC_COND)
+    sptr, sval = (None, 0.0) if s is None else _cell_supersaturation(s, n)
+    dptr = None
+    if dt_dev is not None:
+        dptr, dplanes, dn, _ = as_device(dt_dev)
+        if dplanes != 1 or dn != ncol or dtype_code(dt_dev) != 0:
+            raise ValueError("dt_dev must be an (1, n_columns) fp64 device array")
+    times = np.ascontiguousarray(np.atleast_1d(np.asarray(t_save, dtype=np.float64)))
+    if times.ndim != 1:
+        raise ValueError("t_save must be a sequence of times")
+    n_save = int(times.size)
+    if save_out is None:
+        saved = DeviceArray(n_save * planes, ld, dtype=np.float32 if dtype_code(u) else np.float64)
+    else:
+        saved = save_out
+        vptr, vplanes, vn, vld = as_device(saved)
+        if vplanes != n_save * planes or vn != n or vld != ld or dtype_code(saved) != dtype_code(u):
+            raise ValueError(f"save_out must be ({n_save * planes}, n) with the leading dimension and plane type of u")
+    L = _lib.lib()
+    opts = _lib.AdaptiveOptsC()
+    L.cloudy_adaptive_opts_init(C.byref(opts))
+    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
+    t_arr = DeviceArray.zeros(1, max(ncol, 1)) if info else None
+    i_arr = DeviceArray.zeros(3, max(ncol, 1), dtype=np.int32) if info else None
+    _lib.check(L.cloudy_rainshaft_tsit5_adaptive_saveat(plan.handle, nz, ncol, ld, uptr, optr, sources, sptr, sval, float(xi), float(par.dz),
+                                                        float(t_span), C.byref(opts), dptr, t_arr.ptr if info else None,
+                                                        i_arr.ptr if info else None, stream, n_save,
+                                                        times.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        as_device(saved)[0] if n_save else None))
+    if not info:
+        return o, saved
+    _lib.check(L.cloudy_stream_synchronize(stream))
+    counts = i_arr.to_numpy()[:, :ncol]
+    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise RuntimeError(f"solve_rainshaft_tsit5_adaptive_saveat: {bad.size} of {ncol} columns did not reach t_span; the first is column "
+                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
+    return o, saved, accepted, rejected, status, t_arr.to_numpy()[0, :ncol]

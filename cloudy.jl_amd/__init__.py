@@ -25,7 +25,7 @@ from .Coalescence import (CoalescenceData, NumericalPlan, Plan, get_coal_ints, g
                           F64_RELAXED)
 from .Sedimentation import (get_sedimentation_flux, make_rainshaft_cond_rhs, make_rainshaft_rhs, rainshaft_sources,
                             rhs_condensation, solve_rainshaft_cond_ssprk33, solve_rainshaft_ssprk33,
-                            solve_rainshaft_tsit5_adaptive)
+                            solve_rainshaft_tsit5_adaptive, solve_rainshaft_tsit5_adaptive_saveat)
 from .box_model import (ODEParameters, make_box_model_rhs, rhs_coal, solve_box_ssprk33, solve_box_tsit5_adaptive, solve_ssprk33, solve_tsit5,
                         solve_tsit5_adaptive, solve_tsit5_adaptive_saveat)
 from .parcel import ParcelParams, parcel_rhs, solve_parcel_ssprk33, solve_parcel_tsit5_adaptive

@@ -111,6 +111,8 @@ SYMBOLS = {
                                                  C.c_double, C.c_int, _vp]),
     "cloudy_rainshaft_tsit5_adaptive": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, C.c_double,
                                              C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp]),
+    "cloudy_rainshaft_tsit5_adaptive_saveat": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _i, _vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                    C.POINTER(AdaptiveOptsC), _vp, _vp, _vp, _vp, _sz, _dp, _vp]),
     "cloudy_moment_sums": (_i, [_vp, _sz, _sz, _i, _vp, _vp, _vp]),
     "cloudy_moment_sums_workspace_bytes": (_sz, [_i]),
     "cloudy_moment_sums_ws": (_i, [_vp, _sz, _sz, _i, _vp, _vp, _vp, _sz, _vp]),

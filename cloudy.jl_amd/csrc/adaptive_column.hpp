@@ -34,6 +34,28 @@
 // Registers: u, k1 .. k6 and the stage state are eight [N][3] arrays per lane; the error combination goes into k2 and k7 into k3
 // as in tsit5_adaptive_loop.  Nothing is parked in LDS.
 //
+// Dense output (SAVE = true, cloudy_rainshaft_tsit5_adaptive_saveat): the rules of tsit5_adaptive_loop's SAVE, restated for a
+// column; the same loop, the same expressions, the same controller and the same barriers -- nothing of it feeds back into a step.
+//   cursor     every lane keeps a cursor j into t_save[0 .. n_save) (device doubles, strictly increasing, within [0, t_span]); the
+//              lanes of a column hold equal t, h and t_new, so their cursors stay equal and they take the same branches.
+//   snapshots  after an accepted step t -> t_new, while t_save[j] <= t_new: where t_save[j] == t_new the clamped u_new (w) through
+//              the expressions of the final store (a snapshot at t_span has the bits of u_out); otherwise u + h sum_i b_i(th) k_i,
+//              i = 1 .. 7, th = (t_save[j] - t) / h (tsit5::interp_weights), CLAMPED to >= 0 on the way out: the clamped u_new is
+//              what the integrator returns and what k7 was evaluated at, and without the clamp a snapshot just inside a step
+//              whose u_new was clamped would be negative where the one at its end is not.  A save time 0: the bits of u_in as
+//              loaded, before the clamp.  t_span = 0: every snapshot is the input.  A column that stops with status 1 or 2 leaves
+//              a quiet NaN in every plane of every cell for every snapshot beyond the time it reached.
+//   layout     snapshot j, plane p, cell i = col nz + iz at u_save[((size_t)j planes + p) ld + i], physical units, the plan's plane
+//              type, planes = the plan's; the lanes of a wave write neighbouring elements of a plane; columns nz n_columns .. ld
+//              are not written, and neither does a lane without a cell write anything.
+//   registers  k1 .. k7, u and w are all live when a step is accepted.  k7 has an array of its own (a ninth); the k1 .. k6 part of the
+//              error estimate has none: k1 .. k6 are still there after k7 = f(u_new), and the norm forms the same expression
+//              from the same operands there -- the same bits as the copy SAVE = false keeps in k2.  What does not fit the
+//              architectural registers goes to the accumulation registers or to scratch (DESIGN 3.5 has the figures); no LDS row
+//              is parked, so the LDS is that of SAVE = false.
+//   barriers   the snapshot code sits after `if (!active) continue;`, outside column_rhs and column_sum, and holds no barrier:
+//              the sequence of barriers per loop trip is that of SAVE = false.
+//
 // This header includes adaptive.hpp alone; kernels.hpp, adaptive.hpp and the fixed-step column units do not know it.
 #pragma once
 #include "adaptive.hpp"
@@ -112,13 +134,16 @@ __device__ __forceinline__ void column_rhs(const KArgs<N, P> &A, const SediArgs 
 }
 
 // The loop.  u_in / u_out: the plan's planes (they may alias: a lane reads and writes its own cell).  s_dev: one supersaturation
-// per cell, loaded once (null: s_scalar).
-template <int N, int P, int MODE, typename TIO, bool SPEC, int BS, bool COND>
+// per cell, loaded once (null: s_scalar).  SAVE: n_save, t_save and u_save (n_save x planes planes of leading dimension ld,
+// aliasing neither u_in nor u_out) as above; without it they are not read.
+template <int N, int P, int MODE, typename TIO, bool SPEC, int BS, bool COND, bool SAVE = false>
 __device__ __forceinline__ void column_tsit5_adaptive_body(const KArgs<N, P> *__restrict__ Ag, const SediArgs *__restrict__ Sg,
                                                            const double *__restrict__ nodes, int nz, size_t n_columns, size_t ld,
                                                            const TIO *u_in, TIO *u_out, double dz, double t_span, AdaptiveOpts o,
                                                            double *dt_dev, double *t_dev, int *info_dev, double coef = 0.0,
-                                                           double s_scalar = 0.0, const double *__restrict__ s_dev = nullptr) {
+                                                           double s_scalar = 0.0, const double *__restrict__ s_dev = nullptr,
+                                                           size_t n_save = 0, const double *__restrict__ t_save = nullptr,
+                                                           TIO *__restrict__ u_save = nullptr) {
     using namespace tsit5;
     using St = adaptive::State<N, 0>;
     __shared__ double sh_sum[BS];   // the cells' partial sums of a column norm
@@ -130,13 +155,27 @@ __device__ __forceinline__ void column_tsit5_adaptive_body(const KArgs<N, P> *__
     const bool valid = (cl < cpb) && (col < n_columns);
     const size_t i = col * (size_t)nz + iz;
     const bool top = iz == nz - 1, first = iz == 0;
+    // SAVE: component (m, q) of snapshot js of this lane's cell, as the final store writes u -- physical units, the planes a mode has
+    size_t planes = 0;
+    if constexpr (SAVE) {
+#pragma unroll
+        for (int m = 0; m < N; ++m) planes += A.np[m] == 3 ? 3 : 2;
+    }
+    auto save = [&](size_t js, int m, int q, TIO x) {
+        if (q < A.np[m]) u_save[(js * planes + (size_t)(A.off[m] + q)) * ld + i] = x;
+    };
     if (!(t_span > 0.0)) {   // (workgroup-uniform: a kernel argument) nothing to integrate, the planes as they are
         if (!valid) return;
 #pragma unroll
         for (int m = 0; m < N; ++m)
 #pragma unroll
             for (int q = 0; q < 3; ++q)
-                if (q < A.np[m]) u_out[(size_t)(A.off[m] + q) * ld + i] = u_in[(size_t)(A.off[m] + q) * ld + i];
+                if (q < A.np[m]) {
+                    const TIO v = u_in[(size_t)(A.off[m] + q) * ld + i];
+                    u_out[(size_t)(A.off[m] + q) * ld + i] = v;
+                    if constexpr (SAVE)   // (every save time is 0)
+                        for (size_t js = 0; js < n_save; ++js) save(js, m, q, v);
+                }
         if (first) {
             if (t_dev) t_dev[col] = 0.0;
             if (info_dev) info_dev[col] = 0, info_dev[n_columns + col] = 0, info_dev[2 * n_columns + col] = ADAPT_DONE;
@@ -145,12 +184,16 @@ __device__ __forceinline__ void column_tsit5_adaptive_body(const KArgs<N, P> *__
     }
     St u, atol;
     int count = 0;
+    const bool save0 = SAVE && valid && n_save > 0 && t_save[0] == 0.0;
+    size_t j = save0 ? 1 : 0;   // SAVE: the lane's cursor into t_save
 #pragma unroll
     for (int m = 0; m < N; ++m) {
         count += A.np[m] == 3 ? 3 : 2;   // (the planes a mode has: the third slot of a two-moment mode is padding)
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const double v = (valid && q < A.np[m]) ? (double)u_in[(size_t)(A.off[m] + q) * ld + i] : 0.0;
+            if constexpr (SAVE)   // a save time 0: the values as loaded, before the clamp
+                if (save0) save(0, m, q, (TIO)v);
             u.m[m][q] = v < 0.0 ? 0.0 : v;   // the clamp of the first evaluation, in place in the reference
             atol.m[m][q] = o.abstol * A.norm[3 * m + q];
         }
@@ -177,7 +220,12 @@ __device__ __forceinline__ void column_tsit5_adaptive_body(const KArgs<N, P> *__
         return s;
     };
     St k1, k2, k3, k4, k5, k6, w;
-    St &ke = k2, &k7 = k3;   // where the error combination and k7 go: dead by then (see tsit5_adaptive_loop)
+    // where the error combination and k7 go: k2 and k3, dead by then (see tsit5_adaptive_loop) -- SAVE keeps k1 .. k7 for the
+    // interpolant: k7 gets an array of its own (not touched, and so not there, without it) and the error combination is formed
+    // in the norm, from k1 .. k6
+    St k7_own;
+    St &ke = k2;
+    St &k7 = *[&]() -> St * { if constexpr (SAVE) return &k7_own; else return &k3; }();
     rhs(u, k1);
     // ---- the first step
     double dt = dt_dev && valid ? dt_dev[col] : o.dt_init;
@@ -226,19 +274,37 @@ __device__ __forceinline__ void column_tsit5_adaptive_body(const KArgs<N, P> *__
         }, w, k1, k2, k3, k4, k5, u);
         rhs(w, k6);
         // u_new, clamped, into w; the k1 .. k6 part of the error estimate into k2, which is dead from here; then k7 into k3
-        adaptive::each<N, 0>([&](double &ww, double &ee, double c1, double c2, double c3, double c4, double c5, double c6, double uu) {
-            const double un = fma(h, fma(a71, c1, fma(a72, c2, fma(a73, c3, fma(a74, c4, fma(a75, c5, a76 * c6))))), uu);
-            ww = un < 0.0 ? 0.0 : un;
-            ee = fma(bt1, c1, fma(bt2, c2, fma(bt3, c3, fma(bt4, c4, fma(bt5, c5, bt6 * c6)))));
-        }, w, ke, k1, k2, k3, k4, k5, k6, u);
+        if constexpr (!SAVE) {
+            adaptive::each<N, 0>([&](double &ww, double &ee, double c1, double c2, double c3, double c4, double c5, double c6, double uu) {
+                const double un = fma(h, fma(a71, c1, fma(a72, c2, fma(a73, c3, fma(a74, c4, fma(a75, c5, a76 * c6))))), uu);
+                ww = un < 0.0 ? 0.0 : un;
+                ee = fma(bt1, c1, fma(bt2, c2, fma(bt3, c3, fma(bt4, c4, fma(bt5, c5, bt6 * c6)))));
+            }, w, ke, k1, k2, k3, k4, k5, k6, u);
+        } else {
+            adaptive::each<N, 0>([&](double &ww, double c1, double c2, double c3, double c4, double c5, double c6, double uu) {
+                const double un = fma(h, fma(a71, c1, fma(a72, c2, fma(a73, c3, fma(a74, c4, fma(a75, c5, a76 * c6))))), uu);
+                ww = un < 0.0 ? 0.0 : un;
+            }, w, k1, k2, k3, k4, k5, k6, u);
+        }
         rhs(w, k7);
         double s = 0.0;
-        adaptive::counted<N, 0>(A.np, [&](double c7, double ee, double uu, double ww, double at) {
-            const double err = h * fma(bt7, c7, ee);
-            const double sc = fma(o.reltol, fmax(fabs(uu), fabs(ww)), at);
-            const double r = err / sc;
-            s = fma(r, r, s);
-        }, k7, ke, u, w, atol);
+        if constexpr (!SAVE) {
+            adaptive::counted<N, 0>(A.np, [&](double c7, double ee, double uu, double ww, double at) {
+                const double err = h * fma(bt7, c7, ee);
+                const double sc = fma(o.reltol, fmax(fabs(uu), fabs(ww)), at);
+                const double r = err / sc;
+                s = fma(r, r, s);
+            }, k7, ke, u, w, atol);
+        } else {   // (ee: the expression above, on the same operands)
+            adaptive::counted<N, 0>(A.np, [&](double c7, double c1, double c2, double c3, double c4, double c5, double c6, double uu,
+                                              double ww, double at) {
+                const double ee = fma(bt1, c1, fma(bt2, c2, fma(bt3, c3, fma(bt4, c4, fma(bt5, c5, bt6 * c6)))));
+                const double err = h * fma(bt7, c7, ee);
+                const double sc = fma(o.reltol, fmax(fabs(uu), fabs(ww)), at);
+                const double r = err / sc;
+                s = fma(r, r, s);
+            }, k7, k1, k2, k3, k4, k5, k6, u, w, atol);
+        }
         const double eest = sqrt(column_sum(s) / n_norm);
         if (!active) continue;   // (a finished column, a lane without a cell: it only sat through the barriers)
         if (!adaptive::is_finite(eest)) {
@@ -251,6 +317,31 @@ __device__ __forceinline__ void column_tsit5_adaptive_body(const KArgs<N, P> *__
             double q = q11 / exp_fin(adaptive::kBeta2 * log_pos(qold)) / adaptive::kSafety;
             q = fmin(fmax(q, 1.0 / adaptive::kQmax), 1.0 / adaptive::kQmin);
             ++n_acc;
+            if constexpr (SAVE) {
+                const double t_new = last ? t_span : t + h;
+                while (j < n_save) {
+                    const double ts = t_save[j];
+                    if (!(ts <= t_new)) break;
+                    if (ts == t_new) {   // (the end of the step: u_new itself, what the final store writes at t_span)
+#pragma unroll
+                        for (int m = 0; m < N; ++m)
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) save(j, m, q, (TIO)w.m[m][q]);
+                    } else {
+                        double b[7];
+                        interp_weights((ts - t) / h, b);
+#pragma unroll
+                        for (int m = 0; m < N; ++m)
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) {
+                                const double v = fma(h, fma(b[0], k1.m[m][q], fma(b[1], k2.m[m][q], fma(b[2], k3.m[m][q], fma(b[3], k4.m[m][q],
+                                                    fma(b[4], k5.m[m][q], fma(b[5], k6.m[m][q], b[6] * k7.m[m][q])))))), u.m[m][q]);
+                                save(j, m, q, (TIO)(v < 0.0 ? 0.0 : v));
+                            }
+                    }
+                    ++j;
+                }
+            }
             t = last ? t_span : t + h;
             dt = fmax(h / q, fmin(dt, dt / q));
             qold = fmax(eest, adaptive::kQold0);
@@ -262,6 +353,15 @@ __device__ __forceinline__ void column_tsit5_adaptive_body(const KArgs<N, P> *__
         }
     }
     if (!valid) return;
+    if constexpr (SAVE) {   // what a column stopped by the budget or by dt did not reach (status 0: the cursor is at n_save)
+        const TIO nan = (TIO)__builtin_nan("");
+        for (; j < n_save; ++j) {
+#pragma unroll
+            for (int m = 0; m < N; ++m)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) save(j, m, q, nan);
+        }
+    }
 #pragma unroll
     for (int m = 0; m < N; ++m)
 #pragma unroll

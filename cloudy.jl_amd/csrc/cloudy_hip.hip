@@ -279,14 +279,16 @@ JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, boo
 }
 
 // The adaptive column unit that serves columns of nz cells, picked as pick_rainshaft picks among its own sizes (jit_column_adaptive_part,
-// then every smaller size that still holds a column and fits the LDS).  cond: the kernel with the condensation source.
-JitUnit pick_column_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, bool cond) {
+// then every smaller size that still holds a column and fits the LDS).  cond: the kernel with the condensation source.  dense: among
+// the units with the saving kernels (cloudy_rainshaft_tsit5_adaptive_saveat) -- the same sizes, the same LDS, the same rule, so a call
+// with and a call without save times run the same geometry.
+JitUnit pick_column_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, bool cond, bool dense = false) {
     if (!plan->jit_on || nz < 1 || nz > 1024) return JIT_UNITS;
     const int pref = jit_column_adaptive_part(plan->h, nz, n_columns);
     bool reached = false;
     for (int bs : {1024, 512, 256}) {
         reached = reached || bs == pref;
-        const JitUnit u = jit_column_adaptive_unit(bs);
+        const JitUnit u = dense ? jit_column_dense_unit(bs) : jit_column_adaptive_unit(bs);
         if (reached && jit_column_adaptive_fits(plan->h, bs, nz) && jit_unit(plan, u).k[cond ? COLAD_COALCOND : COLAD_COAL].fn != nullptr) return u;
     }
     return JIT_UNITS;
@@ -339,6 +341,7 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_PARCEL_TSIT5_SAVEAT: return JIT_PARCEL_ADAPTIVE;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_TSIT5_ADAPTIVE: return pick_column_adaptive(plan, r.nz, r.n / r.nz, (r.sources & SRC_COND) != 0);
+    case OP_RAINSHAFT_TSIT5_SAVEAT: return pick_column_adaptive(plan, r.nz, r.n / r.nz, (r.sources & SRC_COND) != 0, true);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
         return rainshaft_cond_staged(h, r.nz) ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, r.op == OP_RAINSHAFT_COND_RHS, true);
@@ -370,7 +373,7 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
         return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
                : r.op == OP_COND      ? DIAG_COND_EVAP   : r.op == OP_NQ        ? DIAG_STANDARD_NQ : DIAG_COAL_INTS;
     default:
-        if (jit_is_column_adaptive(u)) return (r.sources & SRC_COND) ? COLAD_COALCOND : COLAD_COAL;
+        if (jit_is_column_adaptive(u) || jit_is_column_dense(u)) return (r.sources & SRC_COND) ? COLAD_COALCOND : COLAD_COAL;
         return jit_is_column(u) && (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) ? COL_RHS : 0;
     }
 }
@@ -601,10 +604,12 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         return refuse_without_unit(plan, JIT_PARCEL_ADAPTIVE, "cloudy_parcel_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) "
                                                               "and has no ahead-of-time instance: step such a parcel stage by stage with "
                                                               "cloudy_cond_evap (and cloudy_coal_rhs) and cloudy_parcel_thermo_host");
-    if (r.op == OP_RAINSHAFT_TSIT5_ADAPTIVE)
-        return refuse_without_unit(plan, jit_column_adaptive_unit(jit_column_adaptive_part(plan->h, r.nz, r.n / r.nz)),
+    if (r.op == OP_RAINSHAFT_TSIT5_ADAPTIVE || r.op == OP_RAINSHAFT_TSIT5_SAVEAT) {
+        const int bs = jit_column_adaptive_part(plan->h, r.nz, r.n / r.nz);
+        return refuse_without_unit(plan, r.op == OP_RAINSHAFT_TSIT5_SAVEAT ? jit_column_dense_unit(bs) : jit_column_adaptive_unit(bs),
                                    "cloudy_rainshaft_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and has no ahead-of-time "
                                    "instance: cloudy_rainshaft_cond_ssprk33_steps steps such columns with a fixed dt");
+    }
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
@@ -1665,9 +1670,12 @@ int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size
     return run(plan, r);
 }
 
-int cloudy_rainshaft_tsit5_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev, void *u_out_dev,
-                                    int sources, const double *s_dev, double s, double xi, double dz, double t_span,
-                                    const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream) {
+// cloudy_rainshaft_tsit5_adaptive (n_save = 0) and cloudy_rainshaft_tsit5_adaptive_saveat (n_save > 0, its save times checked): one
+// request, the same checks and refusals in the same words, the kernel with or without snapshots
+static int rainshaft_adaptive_call(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev, void *u_out_dev,
+                                   int sources, const double *s_dev, double s, double xi, double dz, double t_span,
+                                   const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
+                                   size_t n_save, const double *t_save, void *u_save_dev) {
     const size_t n = nz * n_columns;
     AdaptiveOpts c;
     // the checks of cloudy_tsit5_adaptive in its order, then the column's, then the plan and what it must carry
@@ -1701,7 +1709,7 @@ int cloudy_rainshaft_tsit5_adaptive(const cloudy_plan *plan, size_t nz, size_t n
                                                        "has no ahead-of-time instance: cloudy_rainshaft_cond_ssprk33_steps steps such "
                                                        "columns with a fixed dt");
     if (n == 0) return CLOUDY_OK;
-    LaunchReq r(OP_RAINSHAFT_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
+    LaunchReq r(n_save > 0 ? OP_RAINSHAFT_TSIT5_SAVEAT : OP_RAINSHAFT_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
     r.rainshaft = 1;
     r.sources = sources;
     r.nz = nz;
@@ -1714,7 +1722,28 @@ int cloudy_rainshaft_tsit5_adaptive(const cloudy_plan *plan, size_t nz, size_t n
     r.dt_dev = dt_dev;
     r.t_dev = t_dev;
     r.info_dev = info_dev;
+    r.n_save = n_save;
+    r.t_save = t_save;
+    r.out2 = n_save > 0 ? u_save_dev : nullptr;
     return run(plan, r);
+}
+
+int cloudy_rainshaft_tsit5_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev, void *u_out_dev,
+                                    int sources, const double *s_dev, double s, double xi, double dz, double t_span,
+                                    const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream) {
+    return rainshaft_adaptive_call(plan, nz, n_columns, ld, u_in_dev, u_out_dev, sources, s_dev, s, xi, dz, t_span, opts, dt_dev, t_dev,
+                                   info_dev, stream, 0, nullptr, nullptr);
+}
+
+int cloudy_rainshaft_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev,
+                                           void *u_out_dev, int sources, const double *s_dev, double s, double xi, double dz,
+                                           double t_span, const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev,
+                                           int32_t *info_dev, void *stream, size_t n_save, const double *t_save, void *u_save_dev) {
+    // the save times first, as in the other _saveat entry points; then every check of cloudy_rainshaft_tsit5_adaptive in its order,
+    // the plan last.  Nothing to save: that entry point, its kernel.
+    if (int rc = check_save_times(n_save, t_save, u_save_dev, t_span)) return rc;
+    return rainshaft_adaptive_call(plan, nz, n_columns, ld, u_in_dev, u_out_dev, sources, s_dev, s, xi, dz, t_span, opts, dt_dev, t_dev,
+                                   info_dev, stream, n_save, t_save, u_save_dev);
 }
 
 size_t cloudy_moment_sums_workspace_bytes(int planes) {

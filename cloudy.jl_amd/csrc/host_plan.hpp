@@ -61,7 +61,8 @@ enum Op {
     OP_BOX_TSIT5_SAVEAT = 19 /* the same with snapshots at the caller's save times (its n_save > 0) */,
     OP_PARCEL_TSIT5_ADAPTIVE = 20 /* per-parcel adaptive Tsit5 of the adiabatic parcel (cloudy_parcel_tsit5_adaptive, adaptive_thermo.hpp) */,
     OP_PARCEL_TSIT5_SAVEAT = 21 /* the same with snapshots at the caller's save times (its n_save > 0) */,
-    OP_RAINSHAFT_TSIT5_ADAPTIVE = 22 /* per-column adaptive Tsit5 of the rainshaft columns (cloudy_rainshaft_tsit5_adaptive, adaptive_column.hpp) */
+    OP_RAINSHAFT_TSIT5_ADAPTIVE = 22 /* per-column adaptive Tsit5 of the rainshaft columns (cloudy_rainshaft_tsit5_adaptive, adaptive_column.hpp) */,
+    OP_RAINSHAFT_TSIT5_SAVEAT = 23 /* the same with snapshots at the caller's save times (cloudy_rainshaft_tsit5_adaptive_saveat, n_save > 0) */
 };
 
 struct LaunchReq {
@@ -83,7 +84,7 @@ struct LaunchReq {
     const void *parcel = nullptr;       // OP_PARCEL_*: the ParcelParams (parcel.hpp); coef = coef0, s_scalar / s_dev = w / w_dev
     const void *adaptive = nullptr;     // OP_*TSIT5_ADAPTIVE, OP_*TSIT5_SAVEAT: the AdaptiveOpts (adaptive.hpp) ...
     double *dt_dev = nullptr, *t_dev = nullptr;   // ... and its optional per-parcel planes: next dt (in/out), time reached,
-    int32_t *info_dev = nullptr;                  // accepted / rejected / status ([3][ld]); OP_RAINSHAFT_TSIT5_ADAPTIVE: per column ([3][n_columns])
+    int32_t *info_dev = nullptr;                  // accepted / rejected / status ([3][ld]); OP_RAINSHAFT_TSIT5_ADAPTIVE / _SAVEAT: per column ([3][n_columns])
     size_t n_save = 0;                  // OP_*TSIT5_SAVEAT: the save times (host; run() uploads them into the plan's scratch) and,
     const double *t_save = nullptr;     // in `out2`, the snapshot planes
     size_t nz = 0;    // OP_RAINSHAFT_*: cells per column (n = nz * n_columns)

@@ -651,11 +651,38 @@ int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size
  * nothing written: MovingThreshold plans; NumericalCoalStyle plans; CLOUDY_F32_FAST planes; nz > 1024, or a plan whose LDS rows
  * fit no workgroup that holds a column; plans without plan-time compilation (the kernels -- cloudy_jit_column_adaptive_*, one
  * unit per workgroup size of 256 / 512 / 1024 threads, picked by the rule of cloudy_rainshaft_rhs -- have no ahead-of-time
- * instance).  Dense output at save times and a stage-by-stage form for taller columns are not built. */
+ * instance).  The state at the caller's save times: cloudy_rainshaft_tsit5_adaptive_saveat below.  A stage-by-stage form for
+ * taller columns is not built. */
 int cloudy_rainshaft_tsit5_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev,
                                     void *u_out_dev, int sources, const double *s_dev, double s, double xi, double dz,
                                     double t_span, const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev,
                                     int32_t *info_dev, void *stream);
+
+/* cloudy_rainshaft_tsit5_adaptive with dense output: the same integration -- u_out_dev, dt_dev, t_dev and info_dev have the bits
+ * that entry point gives, the workgroup size is picked by the same rule -- and the state of every cell at the batch-wide save
+ * times t_save[0 .. n_save), in one launch and with no step clamped to a save time.  The save times, their checks, the
+ * interpolant (the free 4th-order one of the pair, no further right-hand-side evaluation), the end points (a snapshot at 0 has the
+ * bits of u_in_dev, one at t_span the bits of u_out_dev), t_span = 0 (every snapshot is the input) and the layout
+ * u_save_dev[((size_t)j * planes + p) * ld + i], planes = cloudy_plan_nmom, in the plan's plane type, are those of
+ * cloudy_tsit5_adaptive_saveat; what a column changes:
+ *   i            is a cell index, col * nz + iz; the cells nz * n_columns .. ld of a snapshot plane are not written.
+ *   clamping     a snapshot inside a step, u + h sum_i b_i(th) k_i, is clamped to >= 0 on the way out, as the returned state is:
+ *                the clamped u_new is what the step ends on and what k7 was evaluated at, and a snapshot just inside a step whose
+ *                u_new was clamped would be negative without it where the snapshot at its end is not.
+ *   stopped columns   a COLUMN that stops with status 1 or 2 leaves a quiet NaN in every plane of every one of its cells for every
+ *                snapshot beyond the time it reached (t_dev[col]); the snapshots it passed stay.
+ * u_save_dev must overlap neither u_in_dev nor u_out_dev (not checked).  n_save = 0 (t_save and u_save_dev may be NULL) is
+ * cloudy_rainshaft_tsit5_adaptive: the same kernel, the same bits.
+ * Argument checks: the save times first (CLOUDY_EINVAL: n_save > CLOUDY_MAX_SAVE_TIMES, NULL t_save or u_save_dev with
+ * n_save > 0, a time that is not finite, negative, beyond t_span or not above the one before), then every check of
+ * cloudy_rainshaft_tsit5_adaptive in its order, the plan last.  Served and refused exactly as that entry point, each refusal
+ * CLOUDY_EUNSUPPORTED in its words with nothing written, u_save_dev included.  The kernels -- cloudy_jit_column_dense_*, the SAVE
+ * instances of the same body -- sit in three units of their own, compiled on the first call with save times. */
+int cloudy_rainshaft_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t nz, size_t n_columns, size_t ld, const void *u_in_dev,
+                                           void *u_out_dev, int sources, const double *s_dev, double s, double xi, double dz,
+                                           double t_span, const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev,
+                                           int32_t *info_dev, void *stream, size_t n_save, const double *t_save,
+                                           void *u_save_dev);
 
 /* sums_dev[q] = sum over parcels of plane q (fp64 accumulate); `planes` planes are reduced.
  * The multi-GPU conservation check all-reduces these nmom doubles (RCCL), see INTEGRATION.md. */

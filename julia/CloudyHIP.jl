@@ -692,6 +692,45 @@ function solve_rainshaft_tsit5_adaptive!(u, plan::Plan, nz, dz, t_span; xi = 0.0
 end
 
 """
+    solve_rainshaft_tsit5_adaptive_saveat!(u, usave, plan, nz, dz, t_span, t_save; xi = 0.0, s = nothing, reltol = 1e-6,
+                                           abstol = 1e-9, dt = 0.0, max_steps = 10000, dt_dev = nothing, t_dev = nothing,
+                                           info_dev = nothing, stream = nothing, sync = true)
+
+`solve_rainshaft_tsit5_adaptive!` with dense output (`cloudy_rainshaft_tsit5_adaptive_saveat`): the same steps of every column, bit
+for bit, none clamped to a save time, and the state of every cell at the batch-wide times `t_save` (a HOST vector within
+[0, `t_span`], strictly increasing) from the free 4th-order interpolant of Tsit5, clamped to >= 0 as the returned state is.
+`usave`: a device array of the element type of `u` with room for `length(t_save) * nmom` planes of leading dimension ld, laid out
+as `solve_tsit5_adaptive_saveat!` lays out its `u_save` with a cell index for `i`; it must not overlap `u`.  A snapshot at 0 has
+the bits of the input, one at `t_span` those of `u`; a column that stopped early has NaN in every cell of the snapshots it did not
+reach (see `info_dev`, one entry per column).  Returns `(u, usave)`.
+"""
+function solve_rainshaft_tsit5_adaptive_saveat!(u, usave, plan::Plan, nz, dz, t_span, t_save; xi = 0.0, s = nothing, reltol = 1e-6,
+                                                abstol = 1e-9, dt = 0.0, max_steps = 10000, dt_dev = nothing, t_dev = nothing,
+                                                info_dev = nothing, stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(u, plan.nmom)
+    st = stream === nothing ? current_stream() : stream
+    o = AdaptiveOpts()
+    o.reltol, o.abstol, o.dt_init, o.max_steps = reltol, abstol, dt, max_steps
+    ts = convert(Vector{Float64}, collect(t_save))
+    length(usave) >= length(ts) * plan.nmom * ld || error("usave holds fewer than length(t_save) * nmom planes of ld elements")
+    eltype(usave) == eltype(u) || error("usave must have the element type of u")
+    sources = s === nothing ? SRC_COAL : (SRC_COAL | SRC_COND)
+    s_dev = (s === nothing || s isa Number) ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(s))
+    s_val = s isa Number ? Float64(s) : 0.0
+    dptr = dt_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(dt_dev))
+    tptr = t_dev === nothing ? Ptr{Cdouble}(C_NULL) : Ptr{Cdouble}(pointer(t_dev))
+    iptr = info_dev === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(info_dev))
+    GC.@preserve ts check(ccall((:cloudy_rainshaft_tsit5_adaptive_saveat, lib), Cint,
+                                (Ptr{Cvoid}, Csize_t, Csize_t, Csize_t, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Cdouble,
+                                 Cdouble, Ref{AdaptiveOpts}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cvoid}, Csize_t, Ptr{Cdouble},
+                                 Ptr{Cvoid}),
+                                plan.handle, nz, n ÷ nz, ld, pointer(u), pointer(u), sources, s_dev, s_val, xi, dz, t_span, o, dptr, tptr,
+                                iptr, st, length(ts), pointer(ts), pointer(usave)))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return u, usave
+end
+
+"""
     rainshaft_cond_rhs!(dm, flux, m, plan, nz, dz, xi, s; stream = nothing, sync = true)
 
 One evaluation of that right-hand side on device arrays (`cloudy_rainshaft_cond_rhs`): `dm` receives the tendency of the

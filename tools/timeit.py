@@ -13,10 +13,12 @@ every experiment switch of the library is an environment variable, so an A/B run
   python tools/timeit.py colcond [--nz NZ] [--cells N] [--workload cfg3b] [--steps S]
         cloudy_rainshaft_cond_ssprk33_steps on the bench's column batch: (a) cloudy_rainshaft_ssprk33_steps, (b) the three sources
         fused, (c) the sequence (b) replaces -- cloudy_rainshaft_rhs + cloudy_cond_evap + torch updates per stage
-  python tools/timeit.py coladaptive [--nz NZ] [--cells N] [--workload cfg3b] [--t-span T] [--reltol R] [--max-steps M]
+  python tools/timeit.py coladaptive [--nz NZ] [--cells N] [--workload cfg3b] [--t-span T] [--reltol R] [--max-steps M] [--n-save K]
         cloudy_rainshaft_tsit5_adaptive (COAL | COND) on the batch of `colcond` to t = T (2 s), against
         cloudy_rainshaft_cond_ssprk33_steps with the driver's 2 steps of T / 2 in the same run; statuses, attempts and the
-        active-lane fraction from the info planes, sum(attempts) / sum over workgroups of (columns x max(attempts))
+        active-lane fraction from the info planes, sum(attempts) / sum over workgroups of (columns x max(attempts)); --n-save K:
+        cloudy_rainshaft_tsit5_adaptive_saveat with 0, 1 and K equidistant save times in the same run, ms per call beside the
+        algorithmic snapshot traffic per cell
   python tools/timeit.py integrators [--parcels P]
         cloudy_ssprk33_steps / cloudy_tsit5_steps of the tensor plans cfg3a, cfg3b, cfg2
   python tools/timeit.py box [--parcels P] [--steps S]
@@ -248,6 +250,21 @@ def cmd_coladaptive(a, pkg, L):
           f"{ms_a / ms_f:.2f} | status 0 / 1 / 2: {int((status == 0).sum())} / {int((status == 1).sum())} / {int((status == 2).sum())} | "
           f"attempts mean {att.mean():.1f}, max {int(att.max())}, rejected {int(rej.sum())} | active-lane fraction {frac:.3f} at {bs} "
           f"threads  (CLOUDY_HIP_RS_BLOCK={env or 'auto'})", flush=True)
+    if a.n_save < 1:
+        return
+    # --n-save K: the same batch through cloudy_rainshaft_tsit5_adaptive_saveat with 0 (the kernel above), 1 and K equidistant save
+    # times, the last at t_span, in the same run; beside each the algorithmic snapshot traffic, n_save x planes x sizeof(plane type)
+    # per cell
+    planes, esz = wl["mom"].shape[0], wl["mom"].dtype.itemsize
+    snap = pkg.DeviceArray.zeros(a.n_save * planes, n)
+    line = [f"cloudy_rainshaft_tsit5_adaptive {ms_a:.3f} ms"]
+    for k in sorted({0, 1, a.n_save}):
+        ts = (C.c_double * max(k, 1))(*[a.t_span * (j + 1) / k for j in range(k)])
+        ms = bench._sustained_ms(pkg, lambda: pkg._lib.check(L.cloudy_rainshaft_tsit5_adaptive_saveat(
+            plan.handle, nz, ncol, n, u0.ptr, out.ptr, 3, s.ptr, 0.0, xi, dz, a.t_span, C.byref(o), None, t_dev.ptr, info.ptr, None, k,
+            ts if k else None, snap.ptr if k else None)), min_reps=3)
+        line.append(f"n_save = {k}: {ms:.3f} ms ({ms / ms_a:.3f} x, {k * planes * esz} B per cell of snapshots)")
+    print(f"{a.workload} columns nz={nz} x {ncol}, cloudy_rainshaft_tsit5_adaptive_saveat in the same run: " + " | ".join(line), flush=True)
 
 
 def cmd_integrators(a, pkg, L):
@@ -584,6 +601,7 @@ def main():
     ca.add_argument("--t-span", type=float, default=2.0)
     ca.add_argument("--reltol", type=float, default=1e-6)
     ca.add_argument("--max-steps", type=int, default=200)
+    ca.add_argument("--n-save", type=int, default=0, help="K > 0: cloudy_rainshaft_tsit5_adaptive_saveat with 0, 1 and K save times as well")
     i = sub.add_parser("integrators")
     i.add_argument("--parcels", type=int, default=0)
     b = sub.add_parser("box")
