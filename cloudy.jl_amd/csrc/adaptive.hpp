@@ -60,6 +60,9 @@ namespace tsit5 {
 // btilde = b - b^ ; sum_j bt_j c_j^p = 0 for p = 0 .. 3 with c = (0, 0.161, 0.327, 0.9, 0.9800255409045097, 1, 1)
 constexpr double bt1 = -0.00178001105222577714, bt2 = -0.0008164344596567469, bt3 = 0.007880878010261995,
                  bt4 = -0.1447110071732629, bt5 = 0.5823571654525552, bt6 = -0.45808210592918697, bt7 = 0.015151515151515152;
+__device__ __forceinline__ double err_k1_k6(double c1, double c2, double c3, double c4, double c5, double c6) {   // (bt7 k7 is added in the norm)
+    return fma(bt1, c1, fma(bt2, c2, fma(bt3, c3, fma(bt4, c4, fma(bt5, c5, bt6 * c6)))));
+}
 // the interpolant over k1 .. k7, th in [0, 1]: b1 = s th (th - r1)(th^2 - p th + q); b2, b3 = s th^2 (th^2 - p th + q);
 // b4 .. b7 = s th^2 (th - r1)(th - r2).  b_i(1) = a7i, b7(1) = 0; sum_i b_i(th) c_i^p = th^(p+1) / (p+1) for p = 0 .. 3
 constexpr double bi1_s = -1.0530884977290216, bi1_r1 = 1.3299890189751412, bi1_p = 1.4364028541716351, bi1_q = 0.7139816917074209;
@@ -121,6 +124,60 @@ __device__ __forceinline__ void counted(const int (&np)[N], F f, S &...s) {
         for (int q = 0; q < 3; ++q)
             if (q < 2 || np[m] == 3) f(s.m[m][q]...);
 }
+
+// Who shares a controller.  The loop keeps t, dt, qold, the counts and the status in every lane; a GROUP says which lanes hold one
+// ODE system between them and therefore one of each:
+//   i, valid       the element of the planes this lane loads, advances and stores, and whether there is one
+//   ctl, ctl_ld    the group's index into dt_dev / t_dev / info_dev, and the leading dimension of info_dev's three rows
+//   leader         this lane writes them
+//   count          lanes per group: the norms are means over count x (the components a lane counts)
+//   sum(part)      the group's sum of its lanes' partial sums, the same bits in every lane of the group
+//   kBarriers      sum holds workgroup barriers: every lane of the workgroup calls it, each time (RANKED loops only)
+//   kClamp         the state is clamped to >= 0 wherever the loop forms one: on load, u_new before k7 = f(u_new), and an
+//                  interpolated snapshot on the way out
+//   kOwnErr        SAVE: the k1 .. k6 part of the error estimate has an array of its own (otherwise the norm forms it again from
+//                  k1 .. k6, which SAVE keeps: the same expression on the same operands, one array less)
+// LaneGroup: a lane is a parcel and a group -- element blockIdx.x BS + threadIdx.x of n, the planes' ld for the control planes.
+// Every member folds: no barrier, no LDS and no clamp reaches a kernel that uses it.
+template <int BS>
+struct LaneGroup {
+    static constexpr bool kBarriers = false, kClamp = false, kOwnErr = true, leader = true;
+    static constexpr int count = 1;
+    size_t i, ctl, ctl_ld;
+    bool valid;
+    __device__ __forceinline__ LaneGroup(size_t n, size_t ld) : i((size_t)blockIdx.x * BS + threadIdx.x), ctl(i), ctl_ld(ld), valid(i < n) {}
+    __device__ __forceinline__ double sum(double part) const { return part; }
+};
+// ColumnGroup: the nz lanes that hold the cells of a column (adaptive_column.hpp).  A workgroup of BS threads owns cpb = floor(BS /
+// nz) whole columns, one lane per cell, cell iz of column col at element col nz + iz; the control planes have one entry per column.
+template <int BS>
+struct ColumnGroup {
+    static constexpr bool kBarriers = true, kClamp = true, kOwnErr = false;
+    size_t i, ctl, ctl_ld;
+    bool valid, leader;
+    int count, iz, cl, cpb;   // (count = nz; iz: the lane's level; cl: its column's slot in the workgroup)
+    __device__ __forceinline__ ColumnGroup(int nz, size_t n_columns) : ctl_ld(n_columns), count(nz), cpb(BS / nz) {
+        cl = (int)threadIdx.x / nz, iz = (int)threadIdx.x - cl * nz;
+        ctl = (size_t)blockIdx.x * cpb + cl;
+        valid = (cl < cpb) && (ctl < n_columns);
+        i = ctl * (size_t)nz + iz;
+        leader = iz == 0;
+    }
+    // every lane puts its cell's partial sum into an LDS row, and after a barrier every lane of the column adds the column's nz
+    // entries in cell order: the order depends on nz alone (a lane without a cell: 0)
+    __device__ __forceinline__ double sum(double part) const {
+        __shared__ double sh_sum[BS];
+        __syncthreads();   // (whoever still reads the row's last sums)
+        sh_sum[threadIdx.x] = part;
+        __syncthreads();
+        double s = 0.0;
+        if (cl < cpb) {
+            const int base = cl * count;
+            for (int j = 0; j < count; ++j) s += sh_sum[base + j];
+        }
+        return s;
+    }
+};
 }  // namespace adaptive
 
 // The loop itself -- the seven-stage step, the error estimate, the controller, the FSAL hand-over, the snapshots and the final
@@ -130,9 +187,10 @@ __device__ __forceinline__ void counted(const int (&np)[N], F f, S &...s) {
 //   RANKED = true: rhs holds workgroup barriers, so every lane of the workgroup makes the same sequence of calls and the loop
 //     runs while ANY lane is active; `live` = the lane's result is wanted (false: a lane without a parcel or one that has
 //     finished, which only sits through the barriers); the state is physical.
+// g: who shares a controller (adaptive::LaneGroup, adaptive::ColumnGroup above).
 // A: the plan constants the loop itself reads (off, np, norm, inv_norm).  u_in / u_out: the plan's planes (they may alias);
-// dt_dev (in/out, one double per parcel: the next proposed dt), t_dev (out: the time reached) and info_dev (out, int32 [3][ld]:
-// accepted, rejected, status) may each be null.  SAVE: n_save, t_save and u_save (n_save x planes planes of leading dimension
+// dt_dev (in/out, one double per group: the next proposed dt), t_dev (out: the time reached) and info_dev (out, int32
+// [3][g.ctl_ld]: accepted, rejected, status) may each be null.  SAVE: n_save, t_save and u_save (n_save x planes planes of leading dimension
 // ld, aliasing neither u_in nor u_out) as above; without it they are not read.
 // KEEP0: the right-hand side leaves the number plane of every mode alone (condensation without coalescence: dM0/dt is zero
 // identically), so u_out and every snapshot get that plane's value as loaded, not its round trip through the normalised units.
@@ -140,16 +198,17 @@ __device__ __forceinline__ void counted(const int (&np)[N], F f, S &...s) {
 // is rhs(live, x, state, dx, deriv); the scalars are planes 0 .. X - 1 of u_in / u_out / every snapshot and the plan's planes follow
 // them; they are never normalised (abstol_i = abstol in their own units), count in the norms (n_moms), and are advanced, interpolated
 // and stored like the rest.
-template <int N, int P, typename TIO, bool RANKED, int BS, bool SAVE, bool KEEP0 = false, int X = 0, typename RHS>
-__device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t n, size_t ld, const TIO *u_in, TIO *u_out,
+template <int N, int P, typename TIO, bool RANKED, int BS, bool SAVE, bool KEEP0 = false, int X = 0, typename G, typename RHS>
+__device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, const G g, size_t ld, const TIO *u_in, TIO *u_out,
                                                     double t_span, AdaptiveOpts o, double *dt_dev, double *t_dev, int *info_dev,
                                                     size_t n_save, const double *__restrict__ t_save, TIO *__restrict__ u_save,
                                                     RHS rhs_of) {
     using namespace tsit5;
     using St = adaptive::State<N, X>;
     static_assert(X == 0 || !RANKED, "extra state belongs to the per-lane loop");
-    const size_t i = (size_t)blockIdx.x * BS + threadIdx.x;
-    const bool valid = i < n;
+    static_assert(RANKED || !G::kBarriers, "a sum with barriers belongs to the loop every lane sits through");
+    const size_t i = g.i;
+    const bool valid = g.valid;
     constexpr bool kRanked = RANKED;
     constexpr bool kNormalisedState = !kRanked;  // see rhs_normalised
     // SAVE: snapshot js of this lane's parcel from v (the units of the state) as the final store writes u -- physical units, the
@@ -188,8 +247,10 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
 #pragma unroll
             for (int q = 0; q < 3; ++q)
                 if (q < 2 || A.np[m] == 3) copy((size_t)(X + A.off[m] + q));
-        if (t_dev) t_dev[i] = 0.0;
-        if (info_dev) info_dev[i] = 0, info_dev[ld + i] = 0, info_dev[2 * ld + i] = ADAPT_DONE;
+        if (g.leader) {
+            if (t_dev) t_dev[g.ctl] = 0.0;
+            if (info_dev) info_dev[g.ctl] = 0, info_dev[g.ctl_ld + g.ctl] = 0, info_dev[2 * g.ctl_ld + g.ctl] = ADAPT_DONE;
+        }
         return;
     }
     if (!kRanked && !valid) return;
@@ -218,13 +279,17 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
                 for (int q = 0; q < 3; ++q)
                     if (q < 2 || A.np[m] == 3) u_save[(size_t)(off + q) * ld + i] = (TIO)u.m[m][q];
             }
+        if constexpr (G::kClamp) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) u.m[m][q] = u.m[m][q] < 0.0 ? 0.0 : u.m[m][q];
+        }
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             if (kNormalisedState) u.m[m][q] = div_by_const(u.m[m][q], A.norm[3 * m + q], A.inv_norm[3 * m + q]);
             atol.m[m][q] = kNormalisedState ? o.abstol : o.abstol * A.norm[3 * m + q];
         }
     }
-    const double n_moms = (double)count;
+    const double n_moms = (double)count * (double)g.count;   // components of a group
     // live: the lane's result is wanted (ranked: every lane calls, idle ones sit through the ranking's barriers)
     bool active = valid;
     auto rhs = [&](const St &state, St &deriv) {
@@ -233,14 +298,17 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
     };
     St k1, k2, k3, k4, k5, k6, w;
     // where the error combination and k7 go: k2 and k3, which are dead by then -- SAVE keeps k1 .. k7 for the interpolant and
-    // gives both an array of its own (not touched, and so not there, without it)
+    // gives both an array of its own (not touched, and so not there, without it), or the first none: then k2 stays k2 and the
+    // norm forms the combination (kErrInNorm)
+    constexpr bool kErrInNorm = SAVE && !G::kOwnErr;
     St ke_own, k7_own;
-    St &ke = *[&]() -> St * { if constexpr (SAVE) return &ke_own; else return &k2; }();
+    St &ke = *[&]() -> St * { if constexpr (SAVE && G::kOwnErr) return &ke_own; else return &k2; }();
     St &k7 = *[&]() -> St * { if constexpr (SAVE) return &k7_own; else return &k3; }();
     rhs(u, k1);
     // ---- the first step
-    double dt = dt_dev && valid ? dt_dev[i] : o.dt_init;
-    if (!(dt > 0.0 && adaptive::is_finite(dt))) {
+    double dt = dt_dev && valid ? dt_dev[g.ctl] : o.dt_init;
+    const bool guess = !(dt > 0.0 && adaptive::is_finite(dt));
+    if (G::kBarriers || guess) {   // (a sum with barriers: every lane attends it, whoever uses the result)
         double s0 = 0.0, s1 = 0.0;
         adaptive::counted<N, X>(A.np, [&](double uu, double kk, double at) {
             const double sc = fma(o.reltol, fabs(uu), at);
@@ -248,8 +316,12 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
             s0 = fma(r0, r0, s0);
             s1 = fma(r1, r1, s1);
         }, u, k1, atol);
-        const double d0 = sqrt(s0 / n_moms), d1 = sqrt(s1 / n_moms);
-        dt = d1 == 0.0 ? t_span : 0.01 * d0 / d1;
+        s0 = g.sum(s0);
+        s1 = g.sum(s1);
+        if (guess) {
+            const double d0 = sqrt(s0 / n_moms), d1 = sqrt(s1 / n_moms);
+            dt = d1 == 0.0 ? t_span : 0.01 * d0 / d1;
+        }
     }
     dt = dt > t_span ? t_span : dt;   // (keeps a NaN: status 2 below)
     double t = 0.0, qold = adaptive::kQold0;
@@ -288,17 +360,20 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
         // (ke may be k2: the lambda takes its k2 by value)
         adaptive::each<N, X>([&](double &ww, double &ee, double c1, double c2, double c3, double c4, double c5, double c6, double uu) {
             ww = fma(h, fma(a71, c1, fma(a72, c2, fma(a73, c3, fma(a74, c4, fma(a75, c5, a76 * c6))))), uu);
-            ee = fma(bt1, c1, fma(bt2, c2, fma(bt3, c3, fma(bt4, c4, fma(bt5, c5, bt6 * c6)))));
+            if constexpr (G::kClamp) ww = ww < 0.0 ? 0.0 : ww;
+            if constexpr (!kErrInNorm) ee = err_k1_k6(c1, c2, c3, c4, c5, c6);
         }, w, ke, k1, k2, k3, k4, k5, k6, u);
         rhs(w, k7);
         double s = 0.0;
-        adaptive::counted<N, X>(A.np, [&](double c7, double ee, double uu, double ww, double at) {
+        adaptive::counted<N, X>(A.np, [&](double c7, double ee, double c1, double c2, double c3, double c4, double c5, double c6, double uu,
+                                          double ww, double at) {
+            if constexpr (kErrInNorm) ee = err_k1_k6(c1, c2, c3, c4, c5, c6);
             const double err = h * fma(bt7, c7, ee);
             const double sc = fma(o.reltol, fmax(fabs(uu), fabs(ww)), at);
             const double r = err / sc;
             s = fma(r, r, s);
-        }, k7, ke, u, w, atol);
-        const double eest = sqrt(s / n_moms);
+        }, k7, ke, k1, k2, k3, k4, k5, k6, u, w, atol);
+        const double eest = sqrt(g.sum(s) / n_moms);
         if (!active) continue;   // (an idle lane of a thresholded plan: it only sat through the barriers)
         if (!adaptive::is_finite(eest)) {
             ++n_rej;
@@ -325,6 +400,7 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
                                                  double uu) {
                             vv = fma(h, fma(b[0], c1, fma(b[1], c2, fma(b[2], c3, fma(b[3], c4, fma(b[4], c5, fma(b[5], c6, b[6] * c7)))))),
                                      uu);
+                            if constexpr (G::kClamp) vv = vv < 0.0 ? 0.0 : vv;
                         }, v, k1, k2, k3, k4, k5, k6, k7, u);
                         snapshot(j, v);
                     }
@@ -368,9 +444,11 @@ __device__ __forceinline__ void tsit5_adaptive_loop(const KArgs<N, P> &A, size_t
         u_out[(size_t)(off + 1) * ld + i] = (TIO)u.m[m][1];
         if (A.np[m] == 3) u_out[(size_t)(off + 2) * ld + i] = (TIO)u.m[m][2];
     }
-    if (dt_dev) dt_dev[i] = dt;
-    if (t_dev) t_dev[i] = t;
-    if (info_dev) info_dev[i] = n_acc, info_dev[ld + i] = n_rej, info_dev[2 * ld + i] = status;
+    if (g.leader) {
+        if (dt_dev) dt_dev[g.ctl] = dt;
+        if (t_dev) t_dev[g.ctl] = t;
+        if (info_dev) info_dev[g.ctl] = n_acc, info_dev[g.ctl_ld + g.ctl] = n_rej, info_dev[2 * g.ctl_ld + g.ctl] = status;
+    }
 }
 
 // cloudy_tsit5_adaptive / cloudy_tsit5_adaptive_saveat: the loop on the coalescence right-hand side of the plan -- rhs_normalised
@@ -383,7 +461,7 @@ __device__ __forceinline__ void tsit5_adaptive_body(const KArgs<N, P> *__restric
     constexpr bool kRanked = MODE != MODE_ALLINF;
     // the plan constants through an opaque zero offset per RHS evaluation (see ssprk33_body); none when compiled for the plan
     tsit5_adaptive_loop<N, P, TIO, kRanked, BS, SAVE>(
-        *Ag, n, ld, u_in, u_out, t_span, o, dt_dev, t_dev, info_dev, n_save, t_save, u_save,
+        *Ag, adaptive::LaneGroup<BS>(n, ld), ld, u_in, u_out, t_span, o, dt_dev, t_dev, info_dev, n_save, t_save, u_save,
         [&](bool live, const double (&state)[N][3], double (&deriv)[N][3]) {
             size_t oz = 0;
             if (!SPEC) asm volatile("" : "+s"(oz));

@@ -34,7 +34,7 @@ __device__ __forceinline__ void box_tsit5_adaptive_body(const KArgs<N, P> *__res
     // the plan constants through an opaque zero offset per evaluation (see ssprk33_body); none when compiled for the plan
     // (condensation alone: the number planes come out as they went in)
     tsit5_adaptive_loop<N, P, TIO, kRanked, BS, SAVE, (SRC & SRC_COAL) == 0>(
-        *Ag, n, ld, u_in, u_out, t_span, o, dt_dev, t_dev, info_dev, n_save, t_save, u_save,
+        *Ag, adaptive::LaneGroup<BS>(n, ld), ld, u_in, u_out, t_span, o, dt_dev, t_dev, info_dev, n_save, t_save, u_save,
         [&](bool live, const double (&state)[N][3], double (&deriv)[N][3]) {
             size_t oz = 0;
             if (!SPEC) asm volatile("" : "+s"(oz));

@@ -37,7 +37,7 @@ __device__ __forceinline__ void parcel_tsit5_adaptive_body(const KArgs<N, P> *__
     // the plan constants through an opaque zero offset per evaluation (see ssprk33_body); none when compiled for the plan
     // (condensation alone: the number planes come out as they went in)
     tsit5_adaptive_loop<N, P, TIO, false, BS, SAVE, (SRC & SRC_COAL) == 0, 4>(
-        *Ag, n, ld, y_in, y_out, t_span, o, dt_dev, t_dev, info_dev, n_save, t_save, y_save,
+        *Ag, adaptive::LaneGroup<BS>(n, ld), ld, y_in, y_out, t_span, o, dt_dev, t_dev, info_dev, n_save, t_save, y_save,
         [&](bool /*live*/, const double (&t)[4], const double (&u)[N][3], double (&ft)[4], double (&f)[N][3]) {
             size_t oz = 0;
             if (!SPEC) asm volatile("" : "+s"(oz));
