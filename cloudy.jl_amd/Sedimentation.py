@@ -1,8 +1,7 @@
 """Batched sedimentation flux (src/Sources/Sedimentation.jl:22-37) and the rainshaft per-cell sources
 (test/examples/utils/rainshaft_helpers.jl:52-78, without the inter-cell flux divergence)."""
-import numpy as np
-
 from . import _lib
+from ._adaptive import Controller, save_args, save_times, scalar_or_plane, snapshot_planes, state_pair
 from .device import DeviceArray, as_device, plane_dtype
 
 
@@ -81,16 +80,7 @@ def solve_rainshaft_ssprk33(par, u, n_steps, out=None, stream=None):
     return out if out is not None else u
 
 
-def _cell_supersaturation(s, n):
-    """-> (pointer or None, scalar): `s` a float, or an (1, n) fp64 device array with one supersaturation per cell"""
-    if hasattr(s, "data_ptr") or isinstance(s, DeviceArray):
-        from .device import dtype_code
-
-        sptr, splanes, sn, _ = as_device(s)
-        if splanes != 1 or sn != n or dtype_code(s) != 0:   # (the kernels read n doubles, whatever the plan's plane type)
-            raise ValueError("s must be a float or an (1, n) fp64 device array with one value per cell")
-        return sptr, 0.0
-    return None, float(s)
+_PER_CELL = " with one value per cell"   # (the supersaturation of a column call: scalar_or_plane(s, n, "s", _PER_CELL))
 
 
 def make_rainshaft_cond_rhs(coal_type=None):
@@ -110,7 +100,7 @@ def make_rainshaft_cond_rhs(coal_type=None):
         dt = plane_dtype(plan)
         o = out if out is not None else DeviceArray(plan.nmom, n, dt)
         w = work if work is not None else DeviceArray(plan.nmom, n, dt)
-        sptr, sval = _cell_supersaturation(s, n)
+        sptr, sval = scalar_or_plane(s, n, "s", _PER_CELL)
         _lib.check(_lib.lib().cloudy_rainshaft_cond_rhs(plan.handle, nz, n // nz, ld, ptr, sptr, sval, float(xi), float(p.dz),
                                                        as_device(w)[0], as_device(o)[0], None))
         return o
@@ -133,10 +123,29 @@ def solve_rainshaft_cond_ssprk33(par, u, n_steps, xi, s, out=None, stream=None):
     if n % nz:
         raise ValueError("number of cells must be a multiple of par.nz")
     optr = as_device(out)[0] if out is not None else ptr
-    sptr, sval = _cell_supersaturation(s, n)
+    sptr, sval = scalar_or_plane(s, n, "s", _PER_CELL)
     _lib.check(_lib.lib().cloudy_rainshaft_cond_ssprk33_steps(plan.handle, nz, n // nz, ld, ptr, optr, sptr, sval, float(xi),
                                                               float(par.dz), float(par.dt), int(n_steps), stream))
     return out if out is not None else u
+
+
+def _adaptive_columns(par, u, out, s, controller):
+    """what the two adaptive column wrappers take alike -> (plan, o, n, ld, the C call's arguments up to s, the Controller of
+    `controller` = (reltol, abstol, dt, max_steps, dt_dev, info) with one entry per column)"""
+    from .box_model import _plan_for
+    from .device import dtype_code
+
+    plan = _plan_for(par, dtype_code(u))
+    n = as_device(u)[2]
+    nz = int(getattr(par, "nz", n))
+    if n % nz:
+        raise ValueError("number of cells must be a multiple of par.nz")
+    ncol = n // nz
+    o, uptr, optr, n, ld = state_pair(u, out, plan.nmom)
+    sources = _lib.SRC_COAL | (0 if s is None else _lib.SRC_COND)
+    sptr, sval = (None, 0.0) if s is None else scalar_or_plane(s, n, "s", _PER_CELL)
+    ctl = Controller(*controller, ncol, max(ncol, 1), what="column")
+    return plan, o, n, ld, (plan.handle, nz, ncol, ld, uptr, optr, sources, sptr, sval), ctl
 
 
 def solve_rainshaft_tsit5_adaptive(par, u, t_span, xi=0.0, s=None, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000, out=None,
@@ -149,47 +158,9 @@ def solve_rainshaft_tsit5_adaptive(par, u, t_span, xi=0.0, s=None, reltol=1e-6, 
     (1, n_columns) fp64 device array, the proposed step of every column (in/out).  Returns the state -- `u` advanced in place
     unless `out` is given -- or with info=True (accepted, rejected, status, t_reached), one entry per column; then a column that
     did not reach t_span raises a RuntimeError, after the call."""
-    import ctypes as C
-
-    from .box_model import ADAPTIVE_STATUS, _plan_for
-    from .device import dtype_code
-
-    plan = _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    nz = int(getattr(par, "nz", n))
-    if n % nz:
-        raise ValueError("number of cells must be a multiple of par.nz")
-    ncol = n // nz
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
-    sources = _lib.SRC_COAL | (0 if s is None else _lib.SRC_COND)
-    sptr, sval = (None, 0.0) if s is None else _cell_supersaturation(s, n)
-    dptr = None
-    if dt_dev is not None:
-        dptr, dplanes, dn, _ = as_device(dt_dev)
-        if dplanes != 1 or dn != ncol or dtype_code(dt_dev) != 0:
-            raise ValueError("dt_dev must be an (1, n_columns) fp64 device array")
-    L = _lib.lib()
-    opts = _lib.AdaptiveOptsC()
-    L.cloudy_adaptive_opts_init(C.byref(opts))
-    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
-    t_arr = DeviceArray.zeros(1, max(ncol, 1)) if info else None
-    i_arr = DeviceArray.zeros(3, max(ncol, 1), dtype=np.int32) if info else None
-    _lib.check(L.cloudy_rainshaft_tsit5_adaptive(plan.handle, nz, ncol, ld, uptr, optr, sources, sptr, sval, float(xi), float(par.dz),
-                                                 float(t_span), C.byref(opts), dptr, t_arr.ptr if info else None,
-                                                 i_arr.ptr if info else None, stream))
-    if not info:
-        return o
-    _lib.check(L.cloudy_stream_synchronize(stream))
-    counts = i_arr.to_numpy()[:, :ncol]
-    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
-    bad = np.flatnonzero(status)
-    if bad.size:
-        raise RuntimeError(f"solve_rainshaft_tsit5_adaptive: {bad.size} of {ncol} columns did not reach t_span; the first is column "
-                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
-    return accepted, rejected, status, t_arr.to_numpy()[0, :ncol]
+    plan, o, n, ld, head, ctl = _adaptive_columns(par, u, out, s, (reltol, abstol, dt, max_steps, dt_dev, info))
+    _lib.check(_lib.lib().cloudy_rainshaft_tsit5_adaptive(*head, float(xi), float(par.dz), float(t_span), *ctl.args, stream))
+    return ctl.result("solve_rainshaft_tsit5_adaptive", stream) if info else o
 
 
 def solve_rainshaft_tsit5_adaptive_saveat(par, u, t_span, t_save, xi=0.0, s=None, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000,
@@ -204,57 +175,18 @@ def solve_rainshaft_tsit5_adaptive_saveat(par, u, t_span, t_save, xi=0.0, s=None
     With info=True returns (state, saved, accepted, rejected, status, t_reached), one entry per column, and raises as
     solve_rainshaft_tsit5_adaptive does -- keep the snapshots of a run that may stop early with info=False.  Everything else as
     solve_rainshaft_tsit5_adaptive."""
-    import ctypes as C
-
-    from .box_model import ADAPTIVE_STATUS, _plan_for
     from .device import dtype_code
 
-    plan = _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    nz = int(getattr(par, "nz", n))
-    if n % nz:
-        raise ValueError("number of cells must be a multiple of par.nz")
-    ncol = n // nz
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
-    sources = _lib.SRC_COAL | (0 if s is None else _lib.SRC_COND)
-    sptr, sval = (None, 0.0) if s is None else _cell_supersaturation(s, n)
-    dptr = None
-    if dt_dev is not None:
-        dptr, dplanes, dn, _ = as_device(dt_dev)
-        if dplanes != 1 or dn != ncol or dtype_code(dt_dev) != 0:
-            raise ValueError("dt_dev must be an (1, n_columns) fp64 device array")
-    times = np.ascontiguousarray(np.atleast_1d(np.asarray(t_save, dtype=np.float64)))
-    if times.ndim != 1:
-        raise ValueError("t_save must be a sequence of times")
-    n_save = int(times.size)
+    plan, o, n, ld, head, ctl = _adaptive_columns(par, u, out, s, (reltol, abstol, dt, max_steps, dt_dev, info))
+    times = save_times(t_save, "t_save")
+    rows = times.size * plan.nmom
     if save_out is None:
-        saved = DeviceArray(n_save * planes, ld, dtype=np.float32 if dtype_code(u) else np.float64)
+        saved = snapshot_planes(u, times.size, plan.nmom, ld)
     else:
         saved = save_out
         vptr, vplanes, vn, vld = as_device(saved)
-        if vplanes != n_save * planes or vn != n or vld != ld or dtype_code(saved) != dtype_code(u):
-            raise ValueError(f"save_out must be ({n_save * planes}, n) with the leading dimension and plane type of u")
-    L = _lib.lib()
-    opts = _lib.AdaptiveOptsC()
-    L.cloudy_adaptive_opts_init(C.byref(opts))
-    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
-    t_arr = DeviceArray.zeros(1, max(ncol, 1)) if info else None
-    i_arr = DeviceArray.zeros(3, max(ncol, 1), dtype=np.int32) if info else None
-    _lib.check(L.cloudy_rainshaft_tsit5_adaptive_saveat(plan.handle, nz, ncol, ld, uptr, optr, sources, sptr, sval, float(xi), float(par.dz),
-                                                        float(t_span), C.byref(opts), dptr, t_arr.ptr if info else None,
-                                                        i_arr.ptr if info else None, stream, n_save,
-                                                        times.ctypes.data_as(C.POINTER(C.c_double)),
-                                                        as_device(saved)[0] if n_save else None))
-    if not info:
-        return o, saved
-    _lib.check(L.cloudy_stream_synchronize(stream))
-    counts = i_arr.to_numpy()[:, :ncol]
-    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
-    bad = np.flatnonzero(status)
-    if bad.size:
-        raise RuntimeError(f"solve_rainshaft_tsit5_adaptive_saveat: {bad.size} of {ncol} columns did not reach t_span; the first is column "
-                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
-    return o, saved, accepted, rejected, status, t_arr.to_numpy()[0, :ncol]
+        if vplanes != rows or vn != n or vld != ld or dtype_code(saved) != dtype_code(u):
+            raise ValueError(f"save_out must be ({rows}, n) with the leading dimension and plane type of u")
+    _lib.check(_lib.lib().cloudy_rainshaft_tsit5_adaptive_saveat(*head, float(xi), float(par.dz), float(t_span), *ctl.args, stream,
+                                                                *save_args(times, as_device(saved)[0])))
+    return (o, saved) + ctl.result("solve_rainshaft_tsit5_adaptive_saveat", stream) if info else (o, saved)

@@ -11,7 +11,8 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, as_device, dtype_code
+from ._adaptive import Controller, save_args, save_times, scalar_or_plane, snapshot_planes, state_pair
+from .device import as_device, dtype_code
 from .EquationTypes import AnalyticalCoalStyle, CoalescenceStyle, FixedThreshold, MovingThreshold, NumericalCoalStyle
 from .ParticleDistributions import nparams
 
@@ -80,19 +81,20 @@ def make_box_model_rhs(coal_type, threshold_style=None):
     return rhs
 
 
+def _solver_plan(par, u, coal_type):
+    """the plan of a solve_* call: `coal_type` None or AnalyticalCoalStyle: the tensor plan of `par`, NumericalCoalStyle: its quadrature plan"""
+    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
+        raise ValueError("Invalid coal style!")
+    return _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
+
+
 def solve_ssprk33(par, u, dt, n_steps, out=None, stream=None, coal_type=None):
     """solve(ODEProblem(rhs, u, tspan, par), SSPRK33(), dt = dt) for n_steps fixed steps, on the device
     (cloudy_ssprk33_steps): the final state only (the examples' `sol.u[end]`).  `u` is advanced in place unless
     `out` is given.  `coal_type`: the style the RHS was made with (make_box_model_rhs(coal_type)); default
     AnalyticalCoalStyle, NumericalCoalStyle() integrates get_coal_ints(::NumericalCoalStyle, p.pdists, p.kernel_func)."""
-    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
-        raise ValueError("Invalid coal style!")
-    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    plan = _solver_plan(par, u, coal_type)
+    o, uptr, optr, n, ld = state_pair(u, out, plan.nmom)
     _lib.check(_lib.lib().cloudy_ssprk33_steps(plan.handle, n, ld, uptr, optr, float(dt), int(n_steps), stream))
     return o
 
@@ -102,19 +104,10 @@ def solve_tsit5(par, u, dt, n_steps, out=None, stream=None, coal_type=None):
     (cloudy_tsit5_steps): BASELINE configs[0] names Tsit5; no reference driver uses it (they call SSPRK33).  Every plan
     solve_ssprk33 serves (thresholds Inf / fixed / moving, NumericalCoalStyle through `coal_type`), fp64 or float planes.
     `u` is advanced in place unless `out` is given."""
-    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
-        raise ValueError("Invalid coal style!")
-    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
+    plan = _solver_plan(par, u, coal_type)
+    o, uptr, optr, n, ld = state_pair(u, out, plan.nmom)
     _lib.check(_lib.lib().cloudy_tsit5_steps(plan.handle, n, ld, uptr, optr, float(dt), int(n_steps), stream))
     return o
-
-
-ADAPTIVE_STATUS = ("reached t_span", "max_steps attempts", "dt below 1e-14 t_span or not finite")
 
 
 def solve_tsit5_adaptive(par, u, t_span, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000, out=None, dt_dev=None, info=False,
@@ -129,39 +122,11 @@ def solve_tsit5_adaptive(par, u, t_span, reltol=1e-6, abstol=1e-9, dt=None, max_
     (or `out`) and `dt_dev` already hold what every parcel reached, the stopped ones their state at the time they stopped.
     AnalyticalCoalStyle
     plans, fp64 or float planes; NumericalCoalStyle plans are refused (solve_tsit5 steps them with a fixed dt)."""
-    import ctypes as C
-
-    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
-        raise ValueError("Invalid coal style!")
-    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
-    dptr = None
-    if dt_dev is not None:
-        dptr, dplanes, dn, _ = as_device(dt_dev)
-        if dplanes != 1 or dn != n or dtype_code(dt_dev) != 0:
-            raise ValueError("dt_dev must be an (1, n) fp64 device array")
-    L = _lib.lib()
-    opts = _lib.AdaptiveOptsC()
-    L.cloudy_adaptive_opts_init(C.byref(opts))
-    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
-    t_arr = DeviceArray.zeros(1, n) if info else None
-    i_arr = DeviceArray.zeros(3, ld, dtype=np.int32) if info else None
-    _lib.check(L.cloudy_tsit5_adaptive(plan.handle, n, ld, uptr, optr, float(t_span), C.byref(opts), dptr,
-                                       t_arr.ptr if info else None, i_arr.ptr if info else None, stream))
-    if not info:
-        return o
-    _lib.check(L.cloudy_stream_synchronize(stream))
-    counts = i_arr.to_numpy()[:, :n]
-    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
-    bad = np.flatnonzero(status)
-    if bad.size:
-        raise RuntimeError(f"solve_tsit5_adaptive: {bad.size} of {n} parcels did not reach t_span; the first is parcel {int(bad[0])} "
-                           f"(status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
-    return accepted, rejected, status, t_arr.to_numpy()[0]
+    plan = _solver_plan(par, u, coal_type)
+    o, uptr, optr, n, ld = state_pair(u, out, plan.nmom)
+    ctl = Controller(reltol, abstol, dt, max_steps, dt_dev, info, n, ld)
+    _lib.check(_lib.lib().cloudy_tsit5_adaptive(plan.handle, n, ld, uptr, optr, float(t_span), *ctl.args, stream))
+    return ctl.result("solve_tsit5_adaptive", stream) if info else o
 
 
 def solve_tsit5_adaptive_saveat(par, u, t_span, saveat, reltol=1e-6, abstol=1e-9, dt=None, max_steps=10000, out=None, dt_dev=None,
@@ -174,45 +139,14 @@ def solve_tsit5_adaptive_saveat(par, u, t_span, saveat, reltol=1e-6, abstol=1e-9
     stopped early has NaN in the snapshots it did not reach.  With info=True returns (snapshots, accepted, rejected, status,
     t_reached) and raises as solve_tsit5_adaptive does -- keep the snapshots of a run that may stop early with info=False and
     read the status planes through the C call.  Everything else as solve_tsit5_adaptive."""
-    import ctypes as C
-
-    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
-        raise ValueError("Invalid coal style!")
-    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
-    dptr = None
-    if dt_dev is not None:
-        dptr, dplanes, dn, _ = as_device(dt_dev)
-        if dplanes != 1 or dn != n or dtype_code(dt_dev) != 0:
-            raise ValueError("dt_dev must be an (1, n) fp64 device array")
-    times = np.ascontiguousarray(np.atleast_1d(np.asarray(saveat, dtype=np.float64)))
-    if times.ndim != 1:
-        raise ValueError("saveat must be a sequence of times")
-    n_save = int(times.size)
-    saved = DeviceArray(n_save * planes, ld, dtype=np.float32 if dtype_code(u) else np.float64)
-    L = _lib.lib()
-    opts = _lib.AdaptiveOptsC()
-    L.cloudy_adaptive_opts_init(C.byref(opts))
-    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
-    t_arr = DeviceArray.zeros(1, n) if info else None
-    i_arr = DeviceArray.zeros(3, ld, dtype=np.int32) if info else None
-    _lib.check(L.cloudy_tsit5_adaptive_saveat(plan.handle, n, ld, uptr, optr, float(t_span), C.byref(opts), dptr,
-                                              t_arr.ptr if info else None, i_arr.ptr if info else None, stream, n_save,
-                                              times.ctypes.data_as(C.POINTER(C.c_double)), saved.ptr if n_save else None))
-    if not info:
-        return saved
-    _lib.check(L.cloudy_stream_synchronize(stream))
-    counts = i_arr.to_numpy()[:, :n]
-    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
-    bad = np.flatnonzero(status)
-    if bad.size:
-        raise RuntimeError(f"solve_tsit5_adaptive_saveat: {bad.size} of {n} parcels did not reach t_span; the first is parcel "
-                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
-    return saved, accepted, rejected, status, t_arr.to_numpy()[0]
+    plan = _solver_plan(par, u, coal_type)
+    o, uptr, optr, n, ld = state_pair(u, out, plan.nmom)
+    ctl = Controller(reltol, abstol, dt, max_steps, dt_dev, info, n, ld)
+    times = save_times(saveat, "saveat")
+    saved = snapshot_planes(u, times.size, plan.nmom, ld)
+    _lib.check(_lib.lib().cloudy_tsit5_adaptive_saveat(plan.handle, n, ld, uptr, optr, float(t_span), *ctl.args, stream,
+                                                      *save_args(times, saved.ptr)))
+    return (saved,) + ctl.result("solve_tsit5_adaptive_saveat", stream) if info else saved
 
 
 def solve_box_ssprk33(par, u, dt, n_steps, xi, s, coal=True, cond=True, out=None, stream=None, coal_type=None):
@@ -222,22 +156,10 @@ def solve_box_ssprk33(par, u, dt, n_steps, xi, s, coal=True, cond=True, out=None
     (cloudy_box_ssprk33_steps).  `xi` = p.xi; `s`: the supersaturation, a float or an (1, n) fp64 device array (one value per
     parcel), as rhs_condensation takes it.  `u` is advanced in place unless `out` is given.  `coal_type`: as solve_ssprk33; a
     NumericalCoalStyle plan serves cond alone."""
-    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
-        raise ValueError("Invalid coal style!")
+    plan = _solver_plan(par, u, coal_type)
     sources = (_lib.SRC_COAL if coal else 0) | (_lib.SRC_COND if cond else 0)
-    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
-    if hasattr(s, "data_ptr") or isinstance(s, DeviceArray):
-        sptr, splanes, sn, _ = as_device(s)
-        if splanes != 1 or sn != n or dtype_code(s) != 0:   # (the kernel reads n doubles, whatever the plan's plane type)
-            raise ValueError("s must be a float or an (1, n) fp64 device array")
-        sval = 0.0
-    else:
-        sptr, sval = None, float(s)
+    o, uptr, optr, n, ld = state_pair(u, out, plan.nmom)
+    sptr, sval = scalar_or_plane(s, n, "s")
     _lib.check(_lib.lib().cloudy_box_ssprk33_steps(plan.handle, n, ld, uptr, optr, sources, sptr, sval, float(xi), float(dt),
                                                   int(n_steps), stream))
     return o
@@ -255,54 +177,16 @@ def solve_box_tsit5_adaptive(par, u, t_span, xi, s, coal=True, cond=True, saveat
     or (snapshots, accepted, rejected, status, t_reached).  With info=True a parcel that did not reach t_span raises the
     RuntimeError of solve_tsit5_adaptive, after the call.  `coal_type`: as solve_ssprk33; a NumericalCoalStyle plan serves cond
     alone."""
-    import ctypes as C
-
-    if coal_type is not None and not isinstance(coal_type, (AnalyticalCoalStyle, NumericalCoalStyle)):
-        raise ValueError("Invalid coal style!")
+    plan = _solver_plan(par, u, coal_type)
     sources = (_lib.SRC_COAL if coal else 0) | (_lib.SRC_COND if cond else 0)
-    plan = _numerical_plan_for(par, dtype_code(u)) if isinstance(coal_type, NumericalCoalStyle) else _plan_for(par, dtype_code(u))
-    uptr, planes, n, ld = as_device(u)
-    o = out if out is not None else u
-    optr, oplanes, on, old = as_device(o)
-    if planes != plan.nmom or oplanes != plan.nmom or on != n or old != ld:
-        raise ValueError(f"u and out must both be ({plan.nmom}, n) with equal leading dimension")
-    if hasattr(s, "data_ptr") or isinstance(s, DeviceArray):
-        sptr, splanes, sn, _ = as_device(s)
-        if splanes != 1 or sn != n or dtype_code(s) != 0:   # (the kernel reads n doubles, whatever the plan's plane type)
-            raise ValueError("s must be a float or an (1, n) fp64 device array")
-        sval = 0.0
-    else:
-        sptr, sval = None, float(s)
-    dptr = None
-    if dt_dev is not None:
-        dptr, dplanes, dn, _ = as_device(dt_dev)
-        if dplanes != 1 or dn != n or dtype_code(dt_dev) != 0:
-            raise ValueError("dt_dev must be an (1, n) fp64 device array")
-    n_save, times, saved = 0, None, None
-    if saveat is not None:
-        times = np.ascontiguousarray(np.atleast_1d(np.asarray(saveat, dtype=np.float64)))
-        if times.ndim != 1:
-            raise ValueError("saveat must be a sequence of times")
-        n_save = int(times.size)
-        saved = DeviceArray(n_save * planes, ld, dtype=np.float32 if dtype_code(u) else np.float64)
-    L = _lib.lib()
-    opts = _lib.AdaptiveOptsC()
-    L.cloudy_adaptive_opts_init(C.byref(opts))
-    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
-    t_arr = DeviceArray.zeros(1, n) if info else None
-    i_arr = DeviceArray.zeros(3, ld, dtype=np.int32) if info else None
-    _lib.check(L.cloudy_box_tsit5_adaptive(plan.handle, n, ld, uptr, optr, sources, sptr, sval, float(xi), float(t_span), C.byref(opts),
-                                           dptr, t_arr.ptr if info else None, i_arr.ptr if info else None, stream, n_save,
-                                           times.ctypes.data_as(C.POINTER(C.c_double)) if n_save else None,
-                                           saved.ptr if n_save else None))
+    o, uptr, optr, n, ld = state_pair(u, out, plan.nmom)
+    sptr, sval = scalar_or_plane(s, n, "s")
+    ctl = Controller(reltol, abstol, dt, max_steps, dt_dev, info, n, ld)
+    times = save_times(() if saveat is None else saveat, "saveat")
+    saved = None if saveat is None else snapshot_planes(u, times.size, plan.nmom, ld)
+    _lib.check(_lib.lib().cloudy_box_tsit5_adaptive(plan.handle, n, ld, uptr, optr, sources, sptr, sval, float(xi), float(t_span),
+                                                   *ctl.args, stream, *save_args(times, saved.ptr if times.size else None)))
     if not info:
         return o if saveat is None else saved
-    _lib.check(L.cloudy_stream_synchronize(stream))
-    counts = i_arr.to_numpy()[:, :n]
-    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
-    bad = np.flatnonzero(status)
-    if bad.size:
-        raise RuntimeError(f"solve_box_tsit5_adaptive: {bad.size} of {n} parcels did not reach t_span; the first is parcel "
-                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
-    res = (accepted, rejected, status, t_arr.to_numpy()[0])
+    res = ctl.result("solve_box_tsit5_adaptive", stream)
     return res if saveat is None else (saved,) + res

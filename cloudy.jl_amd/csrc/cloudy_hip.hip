@@ -253,6 +253,26 @@ double cond_coef(const cloudy_plan *plan, double xi) {
     const double xi_n = xi / std::pow(plan->h.norms[1], 2.0 / 3.0);
     return 3 * xi_n * std::pow(4 * M_PI / 3, 2.0 / 3.0) / std::pow(1000.0, 1.0 / 3.0);
 }
+// the condensation fields of a request: the sources of its right-hand side, the folded coefficient, the supersaturation
+void set_condensation(LaunchReq &r, const cloudy_plan *plan, int sources, double xi, double s, const double *s_dev) {
+    r.sources = sources;
+    r.coef = cond_coef(plan, xi);
+    r.s_scalar = s;
+    r.s_dev = s_dev;
+}
+// the adaptive fields of a request: t_span where the fixed-step requests carry dt, the controller's options and optional planes,
+// and -- n_save > 0, which selects the kernel that saves -- the save times (host) and the snapshot planes
+void set_adaptive(LaunchReq &r, double t_span, const AdaptiveOpts &c, double *dt_dev, double *t_dev, int32_t *info_dev, size_t n_save,
+                  const double *t_save, void *save_dev) {
+    r.dt = t_span;
+    r.adaptive = &c;
+    r.dt_dev = dt_dev;
+    r.t_dev = t_dev;
+    r.info_dev = info_dev;
+    r.n_save = n_save;
+    r.t_save = t_save;
+    if (n_save > 0) r.out2 = save_dev;
+}
 
 // Unit u of the plan, compiled and loaded on first use (the main unit at plan creation); never ok when plan-time compilation is off.
 const JitSlot &jit_unit(const cloudy_plan *plan, JitUnit u) {
@@ -261,37 +281,34 @@ const JitSlot &jit_unit(const cloudy_plan *plan, JitUnit u) {
     return s;
 }
 
-// The column unit that serves columns of nz cells: the one of the workgroup size jit_rainshaft_part prefers, then every
-// smaller one that still holds a column and fits the LDS -- a unit that does not compile or load is not the end of the call while
-// another can serve it.  Loads on first use.  JIT_UNITS: none (the caller steps stage by stage, or runs the ahead-of-time integrator).
-// rhs_only: a unit with the one-evaluation kernel (cloudy_rainshaft_rhs).  cond: the same pick among the units with the
-// condensation source (cloudy_rainshaft_cond_*: the same workgroup sizes, the same LDS).
-JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, bool rhs_only, bool cond = false) {
+// The unit of a column family that serves columns of nz cells with its kernel at `pos`: the one of the workgroup size the family's
+// rule prefers (part), then every smaller one that still holds a column and fits the LDS (fits) -- a unit that does not
+// compile or load is not the end of the call while another can serve it.  Loads on first use.  JIT_UNITS: none.
+JitUnit pick_column(const cloudy_plan *plan, JitColumnFamily family, size_t nz, size_t n_columns, int pos,
+                    int (*part)(const HostPlan &, size_t, size_t), bool (*fits)(const HostPlan &, int, size_t)) {
     if (!plan->jit_on || nz < 1 || nz > 1024) return JIT_UNITS;
-    const int pref = jit_rainshaft_part(plan->h, nz, n_columns);
+    const int pref = part(plan->h, nz, n_columns);
     bool reached = false;
     for (int bs : {1024, 512, 256}) {
         reached = reached || bs == pref;
-        const JitUnit u = jit_column_unit(bs, cond);
-        if (reached && jit_rainshaft_fits(plan->h, bs, nz) && jit_unit(plan, u).k[rhs_only ? COL_RHS : COL_STEPS].fn != nullptr) return u;
+        const JitUnit u = jit_column_unit(family, bs);
+        if (reached && fits(plan->h, bs, nz) && jit_unit(plan, u).k[pos].fn != nullptr) return u;
     }
     return JIT_UNITS;
 }
-
-// The adaptive column unit that serves columns of nz cells, picked as pick_rainshaft picks among its own sizes (jit_column_adaptive_part,
-// then every smaller size that still holds a column and fits the LDS).  cond: the kernel with the condensation source.  dense: among
-// the units with the saving kernels (cloudy_rainshaft_tsit5_adaptive_saveat) -- the same sizes, the same LDS, the same rule, so a call
-// with and a call without save times run the same geometry.
-JitUnit pick_column_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, bool cond, bool dense = false) {
-    if (!plan->jit_on || nz < 1 || nz > 1024) return JIT_UNITS;
-    const int pref = jit_column_adaptive_part(plan->h, nz, n_columns);
-    bool reached = false;
-    for (int bs : {1024, 512, 256}) {
-        reached = reached || bs == pref;
-        const JitUnit u = dense ? jit_column_dense_unit(bs) : jit_column_adaptive_unit(bs);
-        if (reached && jit_column_adaptive_fits(plan->h, bs, nz) && jit_unit(plan, u).k[cond ? COLAD_COALCOND : COLAD_COAL].fn != nullptr) return u;
-    }
-    return JIT_UNITS;
+// The fused column integrator's (none: the caller steps stage by stage, or runs the ahead-of-time integrator).  rhs_only: a unit
+// with the one-evaluation kernel (cloudy_rainshaft_rhs).  cond: the same pick among the units with the condensation source
+// (cloudy_rainshaft_cond_*: the same workgroup sizes, the same LDS).
+JitUnit pick_rainshaft(const cloudy_plan *plan, size_t nz, size_t n_columns, bool rhs_only, bool cond = false) {
+    return pick_column(plan, cond ? COLF_COND : COLF_PLAIN, nz, n_columns, rhs_only ? COL_RHS : COL_STEPS, jit_rainshaft_part,
+                       jit_rainshaft_fits);
+}
+// The adaptive column's.  cond: the kernel with the condensation source.  dense: among the units with the saving kernels
+// (cloudy_rainshaft_tsit5_adaptive_saveat) -- the same sizes, the same LDS, the same rule, so a call with and a call without save
+// times run the same geometry.
+JitUnit pick_column_adaptive(const cloudy_plan *plan, size_t nz, size_t n_columns, bool cond, bool dense) {
+    return pick_column(plan, dense ? COLF_DENSE : COLF_ADAPTIVE, nz, n_columns, cond ? COLAD_COALCOND : COLAD_COAL,
+                       jit_column_adaptive_part, jit_column_adaptive_fits);
 }
 
 // Whether the calls with the condensation source take the stage-by-stage form because NO column unit could hold the columns
@@ -333,15 +350,11 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_BOX_SSPRK33: return JIT_BOX;
     case OP_PARCEL_SSPRK33:
     case OP_PARCEL_RHS: return JIT_PARCEL;
-    case OP_TSIT5_ADAPTIVE:
-    case OP_TSIT5_SAVEAT: return JIT_ADAPTIVE;
-    case OP_BOX_TSIT5_ADAPTIVE:
-    case OP_BOX_TSIT5_SAVEAT: return JIT_BOX_ADAPTIVE;
-    case OP_PARCEL_TSIT5_ADAPTIVE:
-    case OP_PARCEL_TSIT5_SAVEAT: return JIT_PARCEL_ADAPTIVE;
+    case OP_TSIT5_ADAPTIVE: return JIT_ADAPTIVE;
+    case OP_BOX_TSIT5_ADAPTIVE: return JIT_BOX_ADAPTIVE;
+    case OP_PARCEL_TSIT5_ADAPTIVE: return JIT_PARCEL_ADAPTIVE;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
-    case OP_RAINSHAFT_TSIT5_ADAPTIVE: return pick_column_adaptive(plan, r.nz, r.n / r.nz, (r.sources & SRC_COND) != 0);
-    case OP_RAINSHAFT_TSIT5_SAVEAT: return pick_column_adaptive(plan, r.nz, r.n / r.nz, (r.sources & SRC_COND) != 0, true);
+    case OP_RAINSHAFT_TSIT5_ADAPTIVE: return pick_column_adaptive(plan, r.nz, r.n / r.nz, (r.sources & SRC_COND) != 0, r.n_save > 0);
     case OP_RAINSHAFT_COND_SSPRK33:
     case OP_RAINSHAFT_COND_RHS:
         return rainshaft_cond_staged(h, r.nz) ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, r.op == OP_RAINSHAFT_COND_RHS, true);
@@ -357,6 +370,7 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
 // one kernel.
 int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
     const bool coal = (r.sources & SRC_COAL) != 0;
+    const int saveat = r.n_save > 0 ? 1 : 0;   // (an adaptive unit's saving kernel follows its twin)
     switch (u) {
     case JIT_MAIN: {
         if (h.coal_style == CLOUDY_NUMERICAL_COAL || h.mode != MODE_ALLINF) return 0;
@@ -365,16 +379,18 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
         return ppl == 4 ? MAIN_ALLINF4 : ppl == 2 ? MAIN_ALLINF2 : MAIN_PPL1;
     }
     case JIT_BOX: return coal ? BOX_COALCOND : BOX_COND;
-    case JIT_ADAPTIVE: return r.op == OP_TSIT5_SAVEAT ? ADAPTIVE_SAVEAT : ADAPTIVE_PLAIN;
-    case JIT_BOX_ADAPTIVE: return (coal ? BOXAD_COALCOND : BOXAD_COND) + (r.op == OP_BOX_TSIT5_SAVEAT ? 1 : 0);
-    case JIT_PARCEL_ADAPTIVE: return (coal ? PARAD_COALCOND : PARAD_COND) + (r.op == OP_PARCEL_TSIT5_SAVEAT ? 1 : 0);
+    case JIT_ADAPTIVE: return saveat ? ADAPTIVE_SAVEAT : ADAPTIVE_PLAIN;
+    case JIT_BOX_ADAPTIVE: return (coal ? BOXAD_COALCOND : BOXAD_COND) + saveat;
+    case JIT_PARCEL_ADAPTIVE: return (coal ? PARAD_COALCOND : PARAD_COND) + saveat;
     case JIT_PARCEL: return r.op == OP_PARCEL_RHS ? (coal ? PARCEL_RHS_COAL : PARCEL_RHS) : (coal ? PARCEL_COALCOND : PARCEL_COND);
     case JIT_DIAG:
         return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
                : r.op == OP_COND      ? DIAG_COND_EVAP   : r.op == OP_NQ        ? DIAG_STANDARD_NQ : DIAG_COAL_INTS;
-    default:
-        if (jit_is_column_adaptive(u) || jit_is_column_dense(u)) return (r.sources & SRC_COND) ? COLAD_COALCOND : COLAD_COAL;
-        return jit_is_column(u) && (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) ? COL_RHS : 0;
+    default: {
+        const JitColumnFamily f = jit_column_family(u);
+        if (f >= COLF_ADAPTIVE) return (r.sources & SRC_COND) ? COLAD_COALCOND : COLAD_COAL;
+        return f != COLF_NONE && (r.op == OP_RAINSHAFT_RHS || r.op == OP_RAINSHAFT_COND_RHS) ? COL_RHS : 0;
+    }
     }
 }
 
@@ -593,27 +609,27 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
                                                   "the plan (hiprtc)");
     if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS)
         return refuse_without_unit(plan, JIT_PARCEL, "the parcel kernels are compiled for the plan (hiprtc)");
-    if (r.op == OP_TSIT5_ADAPTIVE || r.op == OP_TSIT5_SAVEAT)
+    if (r.op == OP_TSIT5_ADAPTIVE)
         return refuse_without_unit(plan, JIT_ADAPTIVE, "cloudy_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and has no "
                                                        "ahead-of-time instance: cloudy_tsit5_steps steps such a plan with a fixed dt");
-    if (r.op == OP_BOX_TSIT5_ADAPTIVE || r.op == OP_BOX_TSIT5_SAVEAT)
+    if (r.op == OP_BOX_TSIT5_ADAPTIVE)
         return refuse_without_unit(plan, JIT_BOX_ADAPTIVE, "cloudy_box_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and "
                                                            "has no ahead-of-time instance: step such a plan stage by stage with "
                                                            "cloudy_coal_rhs and cloudy_cond_evap");
-    if (r.op == OP_PARCEL_TSIT5_ADAPTIVE || r.op == OP_PARCEL_TSIT5_SAVEAT)
+    if (r.op == OP_PARCEL_TSIT5_ADAPTIVE)
         return refuse_without_unit(plan, JIT_PARCEL_ADAPTIVE, "cloudy_parcel_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) "
                                                               "and has no ahead-of-time instance: step such a parcel stage by stage with "
                                                               "cloudy_cond_evap (and cloudy_coal_rhs) and cloudy_parcel_thermo_host");
-    if (r.op == OP_RAINSHAFT_TSIT5_ADAPTIVE || r.op == OP_RAINSHAFT_TSIT5_SAVEAT) {
+    if (r.op == OP_RAINSHAFT_TSIT5_ADAPTIVE) {
         const int bs = jit_column_adaptive_part(plan->h, r.nz, r.n / r.nz);
-        return refuse_without_unit(plan, r.op == OP_RAINSHAFT_TSIT5_SAVEAT ? jit_column_dense_unit(bs) : jit_column_adaptive_unit(bs),
+        return refuse_without_unit(plan, jit_column_unit(r.n_save > 0 ? COLF_DENSE : COLF_ADAPTIVE, bs),
                                    "cloudy_rainshaft_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) and has no ahead-of-time "
                                    "instance: cloudy_rainshaft_cond_ssprk33_steps steps such columns with a fixed dt");
     }
     if (r.op == OP_RAINSHAFT_COND_SSPRK33 || r.op == OP_RAINSHAFT_COND_RHS) {
         if (rainshaft_cond_staged(plan->h, r.nz))
             return r.op == OP_RAINSHAFT_COND_RHS ? rainshaft_cond_rhs_unfused(plan, r) : rainshaft_staged_steps(plan, r);
-        return refuse_without_unit(plan, jit_column_unit(jit_rainshaft_part(plan->h, r.nz, r.n / r.nz), true),
+        return refuse_without_unit(plan, jit_column_unit(COLF_COND, jit_rainshaft_part(plan->h, r.nz, r.n / r.nz)),
                                    "the column kernels with the condensation source are compiled for the plan (hiprtc)");
     }
     if (r.op == OP_RAINSHAFT_RHS) return rainshaft_rhs_unfused(plan, r);
@@ -673,7 +689,7 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
             return run(plan, coal);
         }
     }
-    if (r.op == OP_BOX_TSIT5_ADAPTIVE || r.op == OP_BOX_TSIT5_SAVEAT) {   // (sources: COND or COAL | COND; the entry point forwards COAL)
+    if (r.op == OP_BOX_TSIT5_ADAPTIVE) {   // (sources: COND or COAL | COND; the entry point forwards COAL)
         static const char kStaged[] = "step such a plan stage by stage with cloudy_coal_rhs and cloudy_cond_evap";
         if (plan->h.dtype == CLOUDY_F32_FAST)
             return fail(CLOUDY_EUNSUPPORTED, "cloudy_box_tsit5_adaptive serves CLOUDY_F64, CLOUDY_F64_RELAXED and CLOUDY_F32 plans (state and "
@@ -683,7 +699,7 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
             return fail(CLOUDY_EUNSUPPORTED, "the combined coalescence + condensation kernel is not built for quadrature "
                                              "(NumericalCoalStyle) plans: %s, or pass CLOUDY_SRC_COND alone", kStaged);
     }
-    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS || r.op == OP_PARCEL_TSIT5_ADAPTIVE || r.op == OP_PARCEL_TSIT5_SAVEAT) {
+    if (r.op == OP_PARCEL_SSPRK33 || r.op == OP_PARCEL_RHS || r.op == OP_PARCEL_TSIT5_ADAPTIVE) {
         static const char kStaged[] = "step such a parcel stage by stage: cloudy_cond_evap (and cloudy_coal_rhs) per stage with the "
                                       "thermodynamics of cloudy_parcel_thermo_host on the host's side";
         if (plan->h.dtype != CLOUDY_F64)
@@ -696,7 +712,7 @@ int run(const cloudy_plan *plan, const LaunchReq &r) {
             return fail(CLOUDY_EUNSUPPORTED, "the parcel kernel with coalescence is built for plans whose thresholds are all Inf (the "
                                              "ranked variant is not): pass CLOUDY_SRC_COND alone, or %s", kStaged);
     }
-    if (r.op == OP_TSIT5_ADAPTIVE || r.op == OP_TSIT5_SAVEAT) {   // (one kernel body: the same limits, the same words)
+    if (r.op == OP_TSIT5_ADAPTIVE) {   // (with or without snapshots: one kernel body, the same limits, the same words)
         if (plan->h.coal_style == CLOUDY_NUMERICAL_COAL)
             return fail(CLOUDY_EUNSUPPORTED, "cloudy_tsit5_adaptive is not built for quadrature (NumericalCoalStyle) plans: "
                                              "cloudy_tsit5_steps steps them with a fixed dt");
@@ -1238,20 +1254,6 @@ static int adaptive_request(const cloudy_plan *plan, size_t n, size_t ld, const 
     return adaptive_request(plan, n, ld, in, out, t_span, o, c, [] { return (int)CLOUDY_OK; });
 }
 
-int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, double t_span,
-                          const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream) {
-    AdaptiveOpts c;
-    int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c);
-    if (rc) return rc;
-    LaunchReq r(OP_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
-    r.dt = t_span;
-    r.adaptive = &c;
-    r.dt_dev = dt_dev;
-    r.t_dev = t_dev;
-    r.info_dev = info_dev;
-    return run(plan, r);
-}
-
 // the checks of the save times of a call with dense output: they need no device either and precede the plan's (t_span is
 // checked after them; a save time compared with a t_span that is not finite or negative fails here or there, with an EINVAL
 // either way)
@@ -1276,21 +1278,17 @@ int cloudy_tsit5_adaptive_saveat(const cloudy_plan *plan, size_t n, size_t ld, c
                                  const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream,
                                  size_t n_save, const double *t_save, void *u_save_dev) {
     if (int rc = check_save_times(n_save, t_save, u_save_dev, t_span)) return rc;
-    if (n_save == 0)   // nothing to save: cloudy_tsit5_adaptive, its kernel
-        return cloudy_tsit5_adaptive(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, dt_dev, t_dev, info_dev, stream);
     AdaptiveOpts c;
     int rc = adaptive_request(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, c);
     if (rc) return rc;
-    LaunchReq r(OP_TSIT5_SAVEAT, n, ld, u_in_dev, u_out_dev, stream);
-    r.dt = t_span;
-    r.adaptive = &c;
-    r.dt_dev = dt_dev;
-    r.t_dev = t_dev;
-    r.info_dev = info_dev;
-    r.n_save = n_save;
-    r.t_save = t_save;
-    r.out2 = u_save_dev;
+    LaunchReq r(OP_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
+    set_adaptive(r, t_span, c, dt_dev, t_dev, info_dev, n_save, t_save, u_save_dev);   // (nothing to save: the plain kernel)
     return run(plan, r);
+}
+
+int cloudy_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, double t_span,
+                          const cloudy_adaptive_opts *opts, double *dt_dev, double *t_dev, int32_t *info_dev, void *stream) {
+    return cloudy_tsit5_adaptive_saveat(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, dt_dev, t_dev, info_dev, stream, 0, nullptr, nullptr);
 }
 
 int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const void *u_in_dev, void *u_out_dev, int sources,
@@ -1298,10 +1296,7 @@ int cloudy_box_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, const
     int rc = check_batch(plan, n, ld, u_in_dev, u_out_dev);
     if (rc) return rc;
     LaunchReq r(OP_BOX_SSPRK33, n, ld, u_in_dev, u_out_dev, stream);
-    r.sources = sources;
-    r.coef = cond_coef(plan, xi);
-    r.s_scalar = s;
-    r.s_dev = s_dev;
+    set_condensation(r, plan, sources, xi, s, s_dev);
     r.dt = dt;
     r.n_steps = n_steps;
     return run(plan, r);
@@ -1319,19 +1314,9 @@ int cloudy_box_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, cons
     if (sources == SRC_COAL)   // coalescence alone is cloudy_tsit5_adaptive[_saveat]: the same request, the same kernel
         return cloudy_tsit5_adaptive_saveat(plan, n, ld, u_in_dev, u_out_dev, t_span, opts, dt_dev, t_dev, info_dev, stream, n_save,
                                             t_save, u_save_dev);
-    LaunchReq r(n_save > 0 ? OP_BOX_TSIT5_SAVEAT : OP_BOX_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
-    r.sources = sources;
-    r.coef = cond_coef(plan, xi);
-    r.s_scalar = s;
-    r.s_dev = s_dev;
-    r.dt = t_span;
-    r.adaptive = &c;
-    r.dt_dev = dt_dev;
-    r.t_dev = t_dev;
-    r.info_dev = info_dev;
-    r.n_save = n_save;
-    r.t_save = t_save;
-    r.out2 = u_save_dev;
+    LaunchReq r(OP_BOX_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
+    set_condensation(r, plan, sources, xi, s, s_dev);
+    set_adaptive(r, t_span, c, dt_dev, t_dev, info_dev, n_save, t_save, u_save_dev);
     return run(plan, r);
 }
 
@@ -1371,15 +1356,20 @@ static int parcel_params(const cloudy_parcel_params *p, ParcelParams &c) {
 }
 static_assert(sizeof(ParcelParams) == 13 * sizeof(double), "ParcelParams is 13 doubles");
 
-// what the two parcel entry points share: the checks that need no device.  The plan comes last, so that every other check is
-// reachable -- and tested -- without one.
-static int parcel_request(const cloudy_plan *plan, size_t n, size_t ld, const void *in, void *out, const cloudy_parcel_params *p,
-                          int sources, bool steps, double dt, int n_steps, ParcelParams &c) {
-    int rc = parcel_params(p, c);
-    if (rc) return rc;
+// the descriptor's checks, then the sources of a parcel call (alternative: the entry point that serves coalescence alone)
+static int check_parcel(const cloudy_parcel_params *p, ParcelParams &c, int sources, const char *alternative) {
+    if (int rc = parcel_params(p, c)) return rc;
     if (sources != SRC_COND && sources != (SRC_COAL | SRC_COND))
         return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COND or CLOUDY_SRC_COAL | CLOUDY_SRC_COND (coalescence alone is "
-                                   "not a parcel: cloudy_ssprk33_steps)", sources);
+                                   "not a parcel: %s)", sources, alternative);
+    return CLOUDY_OK;
+}
+// what the two fixed-step parcel entry points share: the checks that need no device.  The plan comes last, so that every other
+// check is reachable -- and tested -- without one.
+static int parcel_request(const cloudy_plan *plan, size_t n, size_t ld, const void *in, void *out, const cloudy_parcel_params *p,
+                          int sources, bool steps, double dt, int n_steps, ParcelParams &c) {
+    int rc = check_parcel(p, c, sources, "cloudy_ssprk33_steps");
+    if (rc) return rc;
     if (steps && (rc = check_steps(n_steps, dt))) return rc;
     if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
     return check_batch(plan, n, ld, in, out);
@@ -1388,6 +1378,14 @@ static int parcel_request(const cloudy_plan *plan, size_t n, size_t ld, const vo
 static double parcel_coef0(const cloudy_plan *plan, const ParcelParams &c) {
     return 3 * std::pow(4 * M_PI / 3, 2.0 / 3.0) / (std::cbrt(c.rho_l) * std::pow(plan->h.norms[1], 2.0 / 3.0));
 }
+// the parcel fields of a request: the sources, the constants (read at the launch: `c` outlives it), coef0 and the updraft
+static void set_parcel(LaunchReq &r, const cloudy_plan *plan, int sources, const ParcelParams &c, double w, const double *w_dev) {
+    r.sources = sources;
+    r.parcel = &c;
+    r.coef = parcel_coef0(plan, c);
+    r.s_scalar = w;
+    r.s_dev = w_dev;
+}
 
 int cloudy_parcel_rhs(const cloudy_plan *plan, size_t n, size_t ld, const void *y_dev, const double *w_dev, double w,
                       const cloudy_parcel_params *params, int sources, void *dy_dev, void *stream) {
@@ -1395,11 +1393,7 @@ int cloudy_parcel_rhs(const cloudy_plan *plan, size_t n, size_t ld, const void *
     int rc = parcel_request(plan, n, ld, y_dev, dy_dev, params, sources, false, 0.0, 0, c);
     if (rc) return rc;
     LaunchReq r(OP_PARCEL_RHS, n, ld, y_dev, dy_dev, stream);
-    r.sources = sources;
-    r.parcel = &c;
-    r.coef = parcel_coef0(plan, c);
-    r.s_scalar = w;
-    r.s_dev = w_dev;
+    set_parcel(r, plan, sources, c, w, w_dev);
     return run(plan, r);
 }
 
@@ -1410,11 +1404,7 @@ int cloudy_parcel_ssprk33_steps(const cloudy_plan *plan, size_t n, size_t ld, co
     int rc = parcel_request(plan, n, ld, y_in_dev, y_out_dev, params, sources, true, dt, n_steps, c);
     if (rc) return rc;
     LaunchReq r(OP_PARCEL_SSPRK33, n, ld, y_in_dev, y_out_dev, stream);
-    r.sources = sources;
-    r.parcel = &c;
-    r.coef = parcel_coef0(plan, c);
-    r.s_scalar = w;
-    r.s_dev = w_dev;
+    set_parcel(r, plan, sources, c, w, w_dev);
     r.dt = dt;
     r.n_steps = n_steps;
     return run(plan, r);
@@ -1428,28 +1418,12 @@ int cloudy_parcel_tsit5_adaptive(const cloudy_plan *plan, size_t n, size_t ld, c
     if (int rc = check_save_times(n_save, t_save, y_save_dev, t_span, "y_save_dev")) return rc;
     AdaptiveOpts c;
     ParcelParams pc;
-    const auto parcel_checks = [&] {
-        if (int rc = parcel_params(params, pc)) return rc;
-        if (sources != SRC_COND && sources != (SRC_COAL | SRC_COND))
-            return fail(CLOUDY_EINVAL, "sources (%d) must be CLOUDY_SRC_COND or CLOUDY_SRC_COAL | CLOUDY_SRC_COND (coalescence alone is "
-                                       "not a parcel: cloudy_tsit5_adaptive)", sources);
-        return (int)CLOUDY_OK;
-    };
-    if (int rc = adaptive_request(plan, n, ld, y_in_dev, y_out_dev, t_span, opts, c, parcel_checks)) return rc;
-    LaunchReq r(n_save > 0 ? OP_PARCEL_TSIT5_SAVEAT : OP_PARCEL_TSIT5_ADAPTIVE, n, ld, y_in_dev, y_out_dev, stream);
-    r.sources = sources;
-    r.parcel = &pc;
-    r.coef = parcel_coef0(plan, pc);
-    r.s_scalar = w;
-    r.s_dev = w_dev;
-    r.dt = t_span;
-    r.adaptive = &c;
-    r.dt_dev = dt_dev;
-    r.t_dev = t_dev;
-    r.info_dev = info_dev;
-    r.n_save = n_save;
-    r.t_save = t_save;
-    r.out2 = y_save_dev;
+    if (int rc = adaptive_request(plan, n, ld, y_in_dev, y_out_dev, t_span, opts, c,
+                                  [&] { return check_parcel(params, pc, sources, "cloudy_tsit5_adaptive"); }))
+        return rc;
+    LaunchReq r(OP_PARCEL_TSIT5_ADAPTIVE, n, ld, y_in_dev, y_out_dev, stream);
+    set_parcel(r, plan, sources, pc, w, w_dev);
+    set_adaptive(r, t_span, c, dt_dev, t_dev, info_dev, n_save, t_save, y_save_dev);
     return run(plan, r);
 }
 
@@ -1640,9 +1614,7 @@ int cloudy_rainshaft_cond_rhs(const cloudy_plan *plan, size_t nz, size_t n_colum
     r.out2 = flux_work_dev;
     r.nz = nz;
     r.dz = dz;
-    r.coef = cond_coef(plan, xi);
-    r.s_scalar = s;
-    r.s_dev = s_dev;
+    set_condensation(r, plan, SRC_COAL | SRC_COND, xi, s, s_dev);
     return run(plan, r);
 }
 
@@ -1664,9 +1636,7 @@ int cloudy_rainshaft_cond_ssprk33_steps(const cloudy_plan *plan, size_t nz, size
     r.n_steps = n_steps;
     r.nz = nz;
     r.dz = dz;
-    r.coef = cond_coef(plan, xi);
-    r.s_scalar = s;
-    r.s_dev = s_dev;
+    set_condensation(r, plan, SRC_COAL | SRC_COND, xi, s, s_dev);
     return run(plan, r);
 }
 
@@ -1709,22 +1679,12 @@ static int rainshaft_adaptive_call(const cloudy_plan *plan, size_t nz, size_t n_
                                                        "has no ahead-of-time instance: cloudy_rainshaft_cond_ssprk33_steps steps such "
                                                        "columns with a fixed dt");
     if (n == 0) return CLOUDY_OK;
-    LaunchReq r(n_save > 0 ? OP_RAINSHAFT_TSIT5_SAVEAT : OP_RAINSHAFT_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
+    LaunchReq r(OP_RAINSHAFT_TSIT5_ADAPTIVE, n, ld, u_in_dev, u_out_dev, stream);
     r.rainshaft = 1;
-    r.sources = sources;
     r.nz = nz;
     r.dz = dz;
-    r.coef = cond_coef(plan, xi);
-    r.s_scalar = s;
-    r.s_dev = s_dev;
-    r.dt = t_span;
-    r.adaptive = &c;
-    r.dt_dev = dt_dev;
-    r.t_dev = t_dev;
-    r.info_dev = info_dev;
-    r.n_save = n_save;
-    r.t_save = t_save;
-    r.out2 = n_save > 0 ? u_save_dev : nullptr;
+    set_condensation(r, plan, sources, xi, s, s_dev);
+    set_adaptive(r, t_span, c, dt_dev, t_dev, info_dev, n_save, t_save, u_save_dev);
     return run(plan, r);
 }
 

@@ -55,14 +55,11 @@ enum Op {
     OP_RAINSHAFT_COND_RHS = 13 /* one evaluation of the column right-hand side with it (cloudy_rainshaft_cond_rhs) */,
     OP_PARCEL_SSPRK33 = 14 /* fused SSPRK33 steps of the adiabatic parcel (cloudy_parcel_ssprk33_steps, parcel.hpp) */,
     OP_PARCEL_RHS = 15 /* one evaluation of its right-hand side (cloudy_parcel_rhs) */,
-    OP_TSIT5_ADAPTIVE = 16 /* per-parcel adaptive Tsit5 to t_span (cloudy_tsit5_adaptive, adaptive.hpp) */,
-    OP_TSIT5_SAVEAT = 17 /* the same with snapshots at the caller's save times (cloudy_tsit5_adaptive_saveat) */,
-    OP_BOX_TSIT5_ADAPTIVE = 18 /* per-parcel adaptive Tsit5 with the condensation source (cloudy_box_tsit5_adaptive, adaptive_box.hpp) */,
-    OP_BOX_TSIT5_SAVEAT = 19 /* the same with snapshots at the caller's save times (its n_save > 0) */,
-    OP_PARCEL_TSIT5_ADAPTIVE = 20 /* per-parcel adaptive Tsit5 of the adiabatic parcel (cloudy_parcel_tsit5_adaptive, adaptive_thermo.hpp) */,
-    OP_PARCEL_TSIT5_SAVEAT = 21 /* the same with snapshots at the caller's save times (its n_save > 0) */,
-    OP_RAINSHAFT_TSIT5_ADAPTIVE = 22 /* per-column adaptive Tsit5 of the rainshaft columns (cloudy_rainshaft_tsit5_adaptive, adaptive_column.hpp) */,
-    OP_RAINSHAFT_TSIT5_SAVEAT = 23 /* the same with snapshots at the caller's save times (cloudy_rainshaft_tsit5_adaptive_saveat, n_save > 0) */
+    // the adaptive operations: to t_span, and -- n_save > 0 -- with snapshots at the caller's save times (the kernel that saves)
+    OP_TSIT5_ADAPTIVE = 16 /* per-parcel adaptive Tsit5 (cloudy_tsit5_adaptive, cloudy_tsit5_adaptive_saveat, adaptive.hpp) */,
+    OP_BOX_TSIT5_ADAPTIVE = 17 /* the same with the condensation source (cloudy_box_tsit5_adaptive, adaptive_box.hpp) */,
+    OP_PARCEL_TSIT5_ADAPTIVE = 18 /* the same on the adiabatic parcel (cloudy_parcel_tsit5_adaptive, adaptive_thermo.hpp) */,
+    OP_RAINSHAFT_TSIT5_ADAPTIVE = 19 /* per-column adaptive Tsit5 of the rainshaft columns (cloudy_rainshaft_tsit5_adaptive[_saveat], adaptive_column.hpp) */
 };
 
 struct LaunchReq {
@@ -76,16 +73,16 @@ struct LaunchReq {
     void *out2 = nullptr;  // OP_FINITE_2D: thresholds (may be null); rainshaft OP_COAL: the sedimentation flux (null: not wanted);
                            // OP_RAINSHAFT_RHS: the cell fluxes (work planes)
     hipStream_t stream;
-    double dt = 0.0;  // OP_SSPRK33, OP_TSIT5, OP_RAINSHAFT_SSPRK33, OP_BOX_SSPRK33; OP_*TSIT5_ADAPTIVE, OP_*TSIT5_SAVEAT: t_span
+    double dt = 0.0;  // OP_SSPRK33, OP_TSIT5, OP_RAINSHAFT_SSPRK33, OP_BOX_SSPRK33; OP_*TSIT5_ADAPTIVE: t_span
     int n_steps = 0;  // likewise
     double coef = 0.0, s_scalar = 0.0;  // OP_COND, OP_BOX_*, OP_RAINSHAFT_COND_*
     const double *s_dev = nullptr;      // OP_COND, OP_BOX_*, OP_RAINSHAFT_COND_* (optional per-parcel supersaturation)
     int sources = 0;                    // OP_BOX_*, OP_PARCEL_*: CLOUDY_SRC_* bits
     const void *parcel = nullptr;       // OP_PARCEL_*: the ParcelParams (parcel.hpp); coef = coef0, s_scalar / s_dev = w / w_dev
-    const void *adaptive = nullptr;     // OP_*TSIT5_ADAPTIVE, OP_*TSIT5_SAVEAT: the AdaptiveOpts (adaptive.hpp) ...
+    const void *adaptive = nullptr;     // OP_*TSIT5_ADAPTIVE: the AdaptiveOpts (adaptive.hpp) ...
     double *dt_dev = nullptr, *t_dev = nullptr;   // ... and its optional per-parcel planes: next dt (in/out), time reached,
-    int32_t *info_dev = nullptr;                  // accepted / rejected / status ([3][ld]); OP_RAINSHAFT_TSIT5_ADAPTIVE / _SAVEAT: per column ([3][n_columns])
-    size_t n_save = 0;                  // OP_*TSIT5_SAVEAT: the save times (host; run() uploads them into the plan's scratch) and,
+    int32_t *info_dev = nullptr;                  // accepted / rejected / status ([3][ld]); OP_RAINSHAFT_TSIT5_ADAPTIVE: per column ([3][n_columns])
+    size_t n_save = 0;                  // OP_*TSIT5_ADAPTIVE, > 0: the save times (host; the launch uploads them into the plan's scratch) and,
     const double *t_save = nullptr;     // in `out2`, the snapshot planes
     size_t nz = 0;    // OP_RAINSHAFT_*: cells per column (n = nz * n_columns)
     double dz = 0.0;  // OP_RAINSHAFT_*

@@ -8,10 +8,9 @@ units.  `par` carries what rhs_coal! reads (ODEParameters), or is a Plan."""
 import ctypes as C
 from dataclasses import dataclass, fields
 
-import numpy as np
-
 from . import _lib
-from .device import DeviceArray, as_device, dtype_code
+from ._adaptive import Controller, save_args, save_times, scalar_or_plane, state_pair
+from .device import DeviceArray, dtype_code
 
 _R = 8.3144598
 
@@ -49,30 +48,23 @@ def _plan(par, y):
     return _numerical_plan_for(par, dtype_code(y)) if getattr(par, "coal_data", None) is None else _plan_for(par, dtype_code(y))
 
 
-def _updraft(w, n):
-    """w: a float, or an (1, n) fp64 device array (one value per parcel) -- validated as solve_box_ssprk33 validates s"""
-    if hasattr(w, "data_ptr") or isinstance(w, DeviceArray):
-        wptr, wplanes, wn, _ = as_device(w)
-        if wplanes != 1 or wn != n or dtype_code(w) != 0:
-            raise ValueError("w must be a float or an (1, n) fp64 device array")
-        return wptr, 0.0
-    return None, float(w)
-
-
 def _sources(coal):
     return _lib.SRC_COND | (_lib.SRC_COAL if coal else 0)
+
+
+def _parcel_call(par, y, out, w, params, names="y and out"):
+    """what the three entry points take alike -> (plan, o, yptr, optr, n, ld, wptr, wval, the cloudy_parcel_params); `w`: a float,
+    or an (1, n) fp64 device array (one value per parcel)"""
+    plan = _plan(par, y)
+    o, yptr, optr, n, ld = state_pair(y, out, 4 + plan.nmom, names)
+    wptr, wval = scalar_or_plane(w, n, "w")
+    return plan, o, yptr, optr, n, ld, wptr, wval, (params if params is not None else ParcelParams()).to_c()
 
 
 def parcel_rhs(par, dy, y, w, params=None, coal=False, stream=None):
     """parcel_model_cloudy(dY, Y, p, t) (parcel_example.jl:15-85) for a batch, with the distributions updated from the current
     moments; `coal`: rhs_coal! added to the moments' tendency.  One launch."""
-    plan = _plan(par, y)
-    yptr, planes, n, ld = as_device(y)
-    dptr, dplanes, dn, dld = as_device(dy)
-    if planes != 4 + plan.nmom or dplanes != planes or dn != n or dld != ld:
-        raise ValueError(f"y and dy must both be ({4 + plan.nmom}, n) with equal leading dimension")
-    wptr, wval = _updraft(w, n)
-    c = (params if params is not None else ParcelParams()).to_c()
+    plan, dy, yptr, dptr, n, ld, wptr, wval, c = _parcel_call(par, y, dy, w, params, "y and dy")
     _lib.check(_lib.lib().cloudy_parcel_rhs(plan.handle, n, ld, yptr, wptr, wval, C.byref(c), _sources(coal), dptr, stream))
     return dy
 
@@ -81,14 +73,7 @@ def solve_parcel_ssprk33(par, y, w, dt, n_steps, params=None, coal=False, out=No
     """solve(ODEProblem(parcel_model_cloudy, Yinit, tspan, p), SSPRK33(), dt = dt) for n_steps fixed steps on the device
     (parcel_example.jl:104-111): the final state only, one launch, state in registers.  `y` is advanced in place unless `out`
     is given."""
-    plan = _plan(par, y)
-    yptr, planes, n, ld = as_device(y)
-    o = out if out is not None else y
-    optr, oplanes, on, old = as_device(o)
-    if planes != 4 + plan.nmom or oplanes != planes or on != n or old != ld:
-        raise ValueError(f"y and out must both be ({4 + plan.nmom}, n) with equal leading dimension")
-    wptr, wval = _updraft(w, n)
-    c = (params if params is not None else ParcelParams()).to_c()
+    plan, o, yptr, optr, n, ld, wptr, wval, c = _parcel_call(par, y, out, w, params)
     _lib.check(_lib.lib().cloudy_parcel_ssprk33_steps(plan.handle, n, ld, yptr, optr, _sources(coal), wptr, wval, C.byref(c),
                                                      float(dt), int(n_steps), stream))
     return o
@@ -104,44 +89,13 @@ def solve_parcel_tsit5_adaptive(par, y, w, t_span, params=None, coal=False, relt
     array, snapshot j in planes j (4 + nmom) ...  Returns what solve_box_tsit5_adaptive returns: the state -- with `times` the
     snapshots --, or with info=True (accepted, rejected, status, t_reached), preceded by the snapshots with `times`.  With
     info=True a parcel that did not reach t_span raises RuntimeError, after the call."""
-    from .box_model import ADAPTIVE_STATUS
-
-    plan = _plan(par, y)
-    yptr, planes, n, ld = as_device(y)
-    o = out if out is not None else y
-    optr, oplanes, on, old = as_device(o)
-    if planes != 4 + plan.nmom or oplanes != planes or on != n or old != ld:
-        raise ValueError(f"y and out must both be ({4 + plan.nmom}, n) with equal leading dimension")
-    wptr, wval = _updraft(w, n)
-    c = (params if params is not None else ParcelParams()).to_c()
-    dptr = None
-    if dt_dev is not None:
-        dptr, dplanes, dn, _ = as_device(dt_dev)
-        if dplanes != 1 or dn != n or dtype_code(dt_dev) != 0:
-            raise ValueError("dt_dev must be an (1, n) fp64 device array")
-    ts = np.ascontiguousarray(np.atleast_1d(np.asarray(times, dtype=np.float64)))
-    if ts.ndim != 1:
-        raise ValueError("times must be a sequence of times")
-    n_save = int(ts.size)
-    saved = DeviceArray(n_save * planes, ld) if n_save else None
-    L = _lib.lib()
-    opts = _lib.AdaptiveOptsC()
-    L.cloudy_adaptive_opts_init(C.byref(opts))
-    opts.reltol, opts.abstol, opts.dt_init, opts.max_steps = float(reltol), float(abstol), 0.0 if dt is None else float(dt), int(max_steps)
-    t_arr = DeviceArray.zeros(1, n) if info else None
-    i_arr = DeviceArray.zeros(3, ld, dtype=np.int32) if info else None
-    _lib.check(L.cloudy_parcel_tsit5_adaptive(plan.handle, n, ld, yptr, optr, _sources(coal), wptr, wval, C.byref(c), float(t_span),
-                                              C.byref(opts), dptr, t_arr.ptr if info else None, i_arr.ptr if info else None, stream,
-                                              n_save, ts.ctypes.data_as(C.POINTER(C.c_double)) if n_save else None,
-                                              saved.ptr if n_save else None))
+    plan, o, yptr, optr, n, ld, wptr, wval, c = _parcel_call(par, y, out, w, params)
+    ctl = Controller(reltol, abstol, dt, max_steps, dt_dev, info, n, ld)
+    ts = save_times(times, "times")
+    saved = DeviceArray(ts.size * (4 + plan.nmom), ld) if ts.size else None
+    _lib.check(_lib.lib().cloudy_parcel_tsit5_adaptive(plan.handle, n, ld, yptr, optr, _sources(coal), wptr, wval, C.byref(c),
+                                                      float(t_span), *ctl.args, stream, *save_args(ts, saved.ptr if ts.size else None)))
     if not info:
-        return saved if n_save else o
-    _lib.check(L.cloudy_stream_synchronize(stream))
-    counts = i_arr.to_numpy()[:, :n]
-    accepted, rejected, status = counts[0].copy(), counts[1].copy(), counts[2].copy()
-    bad = np.flatnonzero(status)
-    if bad.size:
-        raise RuntimeError(f"solve_parcel_tsit5_adaptive: {bad.size} of {n} parcels did not reach t_span; the first is parcel "
-                           f"{int(bad[0])} (status {int(status[bad[0]])}: {ADAPTIVE_STATUS[int(status[bad[0]])]})")
-    res = (accepted, rejected, status, t_arr.to_numpy()[0])
-    return (saved,) + res if n_save else res
+        return saved if ts.size else o
+    res = ctl.result("solve_parcel_tsit5_adaptive", stream)
+    return (saved,) + res if ts.size else res

@@ -339,6 +339,22 @@ def test_adaptive_column_units_compile_without_a_gpu(cloudy, case, tmp_path, mon
     assert tails == {"", "_b512", "_b1024"}
 
 
+@pytest.mark.parametrize("case", CASES + ("moving", "numerical"))
+def test_every_declared_kernel_is_defined_with_its_argument_tags(cloudy, case):
+    """cloudy_jit_selfcheck(desc, "source-only") compiles nothing: for every unit of the four plans of this file it checks that each
+    kernel the loader would ask for is defined in the unit's text with as many parameters as the launch has argument tags -- the
+    generators write both from one list, and the adaptive ones append shared lists to it."""
+    L = cloudy.lib()
+    if case == "numerical":
+        d = cloudy.NumericalPlan.make_desc([1, 1], cloudy.LinearKernelFunction(5e-3), bench.NORMS, 10, quad_mode=cloudy.QUAD_FIXED)
+    elif case == "moving":
+        d, keep = cloudy.Plan.make_desc([1, 1], np.array(GOLOVIN), (0.9, 1.0), bench.NORMS, 1, vel=VEL)
+    else:
+        nm = 1 if case == "single_gamma" else 2
+        d, keep = cloudy.Plan.make_desc([1] * nm, np.array(GOLOVIN), (2e-10, INF)[2 - nm:], bench.NORMS, 0, vel=VEL)
+    assert L.cloudy_jit_selfcheck(C.byref(d), b"source-only") == 0, L.cloudy_last_error().decode()
+
+
 @pytest.mark.parametrize("case", ["moving", "numerical"])
 def test_plans_that_are_not_served_have_no_such_unit(cloudy, case, tmp_path, monkeypatch):
     """A MovingThreshold plan (with a velocity term) and a NumericalCoalStyle plan: none of their units defines an adaptive column

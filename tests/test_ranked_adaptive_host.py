@@ -180,7 +180,8 @@ def test_block_sizes_are_those_the_kernel_generator_uses():
 
     plain = re.search(r'"cloudy_jit_adaptive_tsit5"\) \+ jit_suffix\(h\), (\d+), tensor_waves\(h\)', body("JitKernel adaptive_kernel("))
     assert plain and ", true, " + plain.group(1) + ", true" in body("JitKernel adaptive_kernel(")
-    assert "const int bs = coal && h.mode != MODE_ALLINF ? jit_sorted_block_size(h) : kBlock;" in body("JitKernel box_adaptive_kernel(")
+    assert "const int bs = box_bs(h, coal);" in body("JitKernel box_adaptive_kernel(")   # (the choice it shares with box_kernel)
+    assert "int box_bs(const HostPlan &h, bool coal) { return coal && h.mode != MODE_ALLINF ? jit_sorted_block_size(h) : kBlock; }" in jit
     resolve = body("int jit_sorted_block_size_resolve(")
     assert "if (h.mode != MODE_FIXED || h.N > 3) return kBlock;" in resolve
     wide = re.search(r"for \(int i = 0; i < h.N - 1; \+\+i\) passes \+= h.finite\[i\] \? 1 : 0;\s+return passes >= 1 \? (\d+) : kBlock;", resolve)

@@ -290,16 +290,20 @@ def test_singleton_picks(oracle, plan):
 
 # ---- 4. the columns
 def test_column_count():
-    """jit_rainshaft_part (csrc/jit.hpp) restated for the column test's plan -- cfg3b: two modes, a threshold -- and nz = 20: more
-    columns than a 256-thread workgroup holds, so the pick is the size with the smallest time per cell among those whose LDS fits,
-    full[i] * bs / ((bs / nz) * nz).  NCOL fills two workgroups of that size and part of a third."""
+    """jit_rainshaft_part (csrc/jit.hpp: the shared rule jit_column_part on jit_rainshaft_fits) restated for the column test's plan
+    -- cfg3b: two modes, a threshold -- and nz = 20: more columns than a 256-thread workgroup holds, so the pick is the size with
+    the smallest time per cell among those whose LDS fits, full[i] * bs / ((bs / nz) * nz).  NCOL fills two workgroups of that size
+    and part of a third."""
     jit = open(os.path.join(CSRC, "jit.hpp")).read()
-    start = jit.index("inline int jit_rainshaft_part(")
+    start = jit.index("inline int jit_column_part(")
     body = jit[start:jit.index("\n}\n", start)]
     sizes = [int(v) for v in re.search(r"static const int sizes\[3\] = \{(\d+), (\d+), (\d+)\};", body).groups()]
     full = [float(v) for v in re.search(r"const double full\[3\] = \{([\d.]+), ([\d.]+), ([\d.]+)\};", body).groups()]
-    assert "if (nz <= 256 && n_columns <= 256 / nz && jit_rainshaft_fits(h, 256, nz)) {" in body
+    assert "if (nz <= 256 && n_columns <= 256 / nz && fits(256)) {" in body
     assert "const double t = full[i] * double(bs) / double((bs / nz) * nz);" in body
+    caller = jit[jit.index("inline int jit_rainshaft_part("):]
+    assert "return jit_column_part(nz, n_columns, [&](int bs) { return jit_rainshaft_fits(h, bs, nz); });" in caller[:caller.index("\n}\n")]
+    assert "return (size_t)bs >= nz && jit_rainshaft_lds_bytes(h, bs) <= kLdsPerWorkgroup;" in jit
     limit = int(re.search(r"constexpr size_t kLdsPerWorkgroup = (\d+);", jit).group(1))
 
     def lds_bytes(n_modes, bs):   # jit_rainshaft_lds_bytes of a thresholded plan
