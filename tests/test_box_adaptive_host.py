@@ -1,6 +1,6 @@
 """CPU-only checks of cloudy_box_tsit5_adaptive (csrc/adaptive_box.hpp): per-parcel adaptive Tsit5 of du/dt = [coal](u) + [cond](u; s, xi).
-The reference is the NumPy restatement of the controller (test_tsit5_adaptive_host.adaptive_tsit5_host, with snapshots
-test_tsit5_saveat_host.saveat_tsit5_host) on the unchanged oracle's rhs_coal_batch + rhs_condensation_batch: the restatement against
+The reference is the NumPy restatement of the controller (tsit5_restated.adaptive_tsit5, with snapshots: its t_save) on the
+unchanged oracle's rhs_coal_batch + rhs_condensation_batch: the restatement against
 the closed form of a Monodisperse mode under condensation, the sensitivity of its decisions to the last bit of the combined
 right-hand side on the batches the GPU tests use, the ABI, every argument check of the C entry point, and the plan-time unit
 compiling for gfx950 without a device.
@@ -17,8 +17,9 @@ import pytest
 
 import bench
 import test_tsit5_adaptive_host as H
-import test_tsit5_saveat_host as S
-from test_host_abi import INF, ROOT, _c_prototypes, _julia_ccalls
+from test_host_abi import INF, ROOT, _c_prototypes
+from tsit5_restated import (DONE, adaptive_tsit5, assert_adaptive_opts_refusals, assert_symbol_agrees, default_opts, last_bit_noise, plane_norms,
+                            save_times)
 
 NAME = "cloudy_box_tsit5_adaptive"
 XI_COND = 1e-8      # the closed-form batch
@@ -54,15 +55,15 @@ def cond_params(oracle):
 
 @functools.lru_cache(maxsize=None)
 def cond_case(n, reltol, saveat=False, max_steps=10000):
-    """-> (u0, s, exact at t_span, the restatement's result (with snapshots: at S.save_times(COND_T)), its per-plane errors);
+    """-> (u0, s, exact at t_span, the restatement's result (with snapshots: at save_times(COND_T)), its per-plane errors);
     computed once per session and shared (treat the arrays as read-only)"""
     from oracle import cloudy_oracle as oracle
 
     op = cond_params(oracle)
     u0, s = cond_batch(n)
     rhs = lambda u: oracle.rhs_condensation_batch(op, XI_COND, s, u)  # noqa: E731
-    opts = dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, plane_norms=H.plane_norms((2,)))
-    res = S.saveat_tsit5_host(rhs, u0, COND_T, S.save_times(COND_T), opts) if saveat else H.adaptive_tsit5_host(rhs, u0, COND_T, opts)
+    opts = dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, plane_norms=plane_norms((2,)))
+    res = adaptive_tsit5(rhs, u0, COND_T, opts, t_save=save_times(COND_T) if saveat else None)
     exact = cond_exact(u0, s, COND_T)
     return u0, s, exact, res, H.plane_errors(res["u"], exact, u0)
 
@@ -81,10 +82,10 @@ def box_rhs(oracle, kind, n, perturb=None):
 
 def box_reference(oracle, kind, n, max_steps=10000, perturb=None, saveat=False):
     u0 = H.two_gamma_batch(n, kind=kind)
-    opts = dict(reltol=1e-6, abstol=1e-9, max_steps=max_steps, plane_norms=H.plane_norms((3, 3)), normalised=kind == "allinf")
+    opts = dict(reltol=1e-6, abstol=1e-9, max_steps=max_steps, plane_norms=plane_norms((3, 3)), normalised=kind == "allinf")
     t_span = H.TWO_GAMMA_T[kind]
     rhs = box_rhs(oracle, kind, n, perturb)
-    return u0, (S.saveat_tsit5_host(rhs, u0, t_span, S.save_times(t_span), opts) if saveat else H.adaptive_tsit5_host(rhs, u0, t_span, opts))
+    return u0, adaptive_tsit5(rhs, u0, t_span, opts, t_save=save_times(t_span) if saveat else None)
 
 
 @functools.lru_cache(maxsize=None)
@@ -99,13 +100,9 @@ def box_reference_cached(kind, n, max_steps=10000, saveat=False):
 def test_symbol_in_header_ctypes_table_julia_shim_and_python(cloudy):
     protos = _c_prototypes()
     plain, box = protos["cloudy_tsit5_adaptive_saveat"][1], protos["cloudy_box_ssprk33_steps"][1]
-    assert protos[NAME] == ("int", plain[:5] + box[5:9] + plain[5:])
     assert len(protos[NAME][1]) == 18
-    res, argtypes = cloudy._lib.SYMBOLS[NAME]
-    assert res is C.c_int and len(argtypes) == 18 and hasattr(cloudy.lib(), NAME)
+    assert_symbol_agrees(cloudy, NAME, plain[:5] + box[5:9] + plain[5:])
     src = open(os.path.join(ROOT, "julia", "CloudyHIP.jl")).read()
-    mine = [c for c in _julia_ccalls(src) if c[0] == NAME]
-    assert len(mine) == 1 and mine[0][1] == "Cint" and len(mine[0][2]) == 18
     assert re.search(r"function solve_box_tsit5_adaptive!\(u, plan::Plan, t_span, xi, s; coal::Bool = true, cond::Bool = true", src)
     assert "solve_box_tsit5_adaptive" in cloudy.__all__
     sig = inspect.signature(cloudy.solve_box_tsit5_adaptive).parameters
@@ -129,7 +126,7 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
 
     def call(times=(0.0, 0.25, 1.0), t_save="times", u_save=dummy, n=4, ld=4, t_span=1.0, u_in=dummy, u_out=dummy, sources=3, s=0.05,
              xi=1e-8, opts="default", **kw):
-        o = H.default_opts(cloudy, **kw) if opts == "default" else opts
+        o = default_opts(cloudy, **kw) if opts == "default" else opts
         arr = (C.c_double * max(len(times), 1))(*times)
         return L.cloudy_box_tsit5_adaptive(None, n, ld, u_in, u_out, sources, None, s, xi, t_span, None if o is None else C.byref(o), None,
                                            None, None, None, len(times), arr if t_save == "times" else t_save, u_save)
@@ -151,22 +148,8 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
     cap = int(re.search(r"#define CLOUDY_MAX_SAVE_TIMES (\d+)", open(os.path.join(ROOT, "include", "cloudy_hip.h")).read()).group(1))
     assert call(times=tuple(np.linspace(0.0, 1.0, cap + 1))) == E.EINVAL and "n_save" in msg()
     # then those of cloudy_tsit5_adaptive
-    assert call(opts=None) == E.EINVAL and msg() == "opts is NULL"
-    short = H.default_opts(cloudy)
-    short.struct_size -= 8
-    assert call(opts=short) == E.EINVAL and "struct_size" in msg()
-    for bad in (0.0, -1e-6, nan, inf):
-        assert call(reltol=bad, sources=0) == E.EINVAL and "reltol" in msg(), bad
-    for bad in (-1e-9, nan, inf):
-        assert call(abstol=bad) == E.EINVAL and "abstol" in msg(), bad
-    for bad in (-1.0, nan, inf):
-        assert call(dt_init=bad) == E.EINVAL and "dt_init" in msg(), bad
-    for bad in (-1.0, nan, inf):
-        assert call(times=(), t_save=None, u_save=None, t_span=bad) == E.EINVAL and "t_span" in msg(), bad
-    for bad in (0, -1, 1000001):
-        assert call(max_steps=bad) == E.EINVAL and "max_steps" in msg(), bad
-    assert call(n=4, ld=3, xi=nan) == E.EINVAL and "ld (3) must be >= n_parcels (4)" in msg()
-    assert call(u_in=None, sources=7) == E.EINVAL and msg() == "device buffer is NULL"
+    assert_adaptive_opts_refusals(cloudy, call, msg, no_times=dict(times=(), t_save=None, u_save=None),
+                                  later=(dict(sources=0), dict(sources=7), dict(xi=nan)))
     # then the box's: sources, xi
     for bad in (0, -1, 4, 7):
         assert call(sources=bad, xi=nan) == E.EINVAL and "sources" in msg() and str(bad) in msg(), bad
@@ -228,7 +211,7 @@ def test_restatement_against_the_condensation_closed_form(oracle, reltol):
     attempts = res["accepted"] + res["rejected"]
     print(f"reltol={reltol:g}: attempts {attempts.min()} .. {attempts.max()}, error per plane {err}, "
           f"M1 moves by {(exact[1] / u0[1]).min():.3g} .. {(exact[1] / u0[1]).max():.3g}")
-    assert np.all(res["status"] == H.DONE) and np.all(res["t"] == COND_T)
+    assert np.all(res["status"] == DONE) and np.all(res["t"] == COND_T)
     assert attempts.min() == 1 and attempts.max() == (8 if reltol == 1e-6 else 16)
     assert (exact[1] / u0[1]).min() < 0.6 and (exact[1] / u0[1]).max() > 2.7 and np.all(exact[1] > 0)
     assert np.all(err <= 1e-7), err
@@ -246,7 +229,7 @@ def test_decisions_are_insensitive_to_the_last_bit_of_the_combined_rhs(oracle, k
     the device, 1e-11 x evaluations of |u0| + |u|.  Every status is 0; condensation moves the state far above reltol, so a kernel
     that drops the term cannot pass."""
     u0, base = box_reference_cached(kind, n)
-    _, pert = box_reference(oracle, kind, n, perturb=H.last_bit_noise(1))
+    _, pert = box_reference(oracle, kind, n, perturb=last_bit_noise(1))
     _, coal_only = H.two_gamma_reference_cached(kind, n)
     attempts = base["accepted"] + base["rejected"]
     diff = (base["accepted"] != pert["accepted"]) | (base["rejected"] != pert["rejected"])
@@ -255,7 +238,7 @@ def test_decisions_are_insensitive_to_the_last_bit_of_the_combined_rhs(oracle, k
     cond_moves = (np.abs(base["u"] - coal_only["u"]) / scale).max(axis=1)
     print(f"{kind} n={n}: attempts {attempts.min()} .. {attempts.max()}; {int(diff.sum())} of {n} parcels change (accepted, rejected) "
           f"under last-bit noise; the others move by {moved:.1e} x evaluations; condensation moves the planes by {cond_moves}")
-    assert np.all(base["status"] == H.DONE) and np.all(pert["status"] == H.DONE)
+    assert np.all(base["status"] == DONE) and np.all(pert["status"] == DONE)
     assert attempts.min() == 1 and attempts.max() >= 5
     assert diff.sum() <= 0.05 * n, diff.sum()
     assert moved < TOL_EVAL, moved

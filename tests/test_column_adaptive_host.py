@@ -1,6 +1,6 @@
 """CPU-only checks of the per-column adaptive Tsit5 for rainshaft columns (cloudy_rainshaft_tsit5_adaptive, csrc/adaptive_column.hpp):
-a NumPy restatement of its rules (`adaptive_tsit5_column_host`: one controller per column, the clamp of u and u_new, the column
-norm; the tableau and the controller constants are those of test_tsit5_adaptive_host), the restatement against the per-parcel one
+the NumPy restatement of its rules (tsit5_restated.adaptive_tsit5 with nz cells per group and clamp=True: one controller per
+column, the clamp of u and u_new, the column norm), the restatement against the per-parcel one
 for columns of one cell, the batch the GPU tests use -- picked on the oracle alone -- with the range of its attempts and the
 sensitivity of its accept / reject decisions to the last bit of the right-hand side, the symbol in the header, the ctypes table,
 the Julia shim and the Python wrapper, every argument check of the C entry point, and the plan-time units compiling for gfx950
@@ -18,91 +18,11 @@ import pytest
 
 import bench
 from test_gpu_column_sources import DZ, GOLOVIN, NCOL, NZ, VEL, XI, column_set, supersaturation
-from test_host_abi import INF, ROOT, _c_prototypes, _julia_ccalls
-from test_tsit5_adaptive_host import (A_ROWS, BETA1, BETA2, BTILDE, DONE, DT_MIN, EPS, GAMMA, MAX_STEPS, QMAX, QMIN, QOLD0,
-                                      adaptive_tsit5_host, default_opts, last_bit_noise, plane_norms)
+from test_host_abi import INF, ROOT
+from tsit5_restated import (DONE, adaptive_tsit5, assert_adaptive_opts_refusals, assert_symbol_agrees, default_opts, last_bit_noise,
+                            plane_norms)
 
 NAME = "cloudy_rainshaft_tsit5_adaptive"
-
-
-def adaptive_tsit5_column_host(rhs, u0, nz, t_span, opts):
-    """Every column of u0 (planes, nz * n_columns; column c holds cells c nz .. (c + 1) nz) from t = 0 to t_span.  rhs(u) -> du/dt
-    on the whole batch, physical units, evaluated on a clamped copy of its argument by the caller's function.  opts: reltol,
-    abstol, max_steps; dt (None / 0: automatic, a float, or one value per column); plane_norms (planes,): the plan's mom_norms
-    (the state is physical: abstol_i = abstol norm_i).  Returns dict(u, t, dt, accepted, rejected, status, evals), one entry per
-    column but for u."""
-    reltol, abstol, max_steps = float(opts["reltol"]), float(opts["abstol"]), int(opts["max_steps"])
-    norms = np.asarray(opts["plane_norms"], dtype=np.float64)[:, None]
-    planes, n = u0.shape
-    ncol = n // nz
-    assert ncol * nz == n
-    count = planes * nz
-    cells = lambda x: np.repeat(x, nz)   # noqa: E731  a column's value on its cells
-
-    def column_sum(x):
-        """(planes, n) -> (ncol,): the planes of a cell first, then the column's cells in cell order"""
-        part = x.sum(axis=0).reshape(ncol, nz)
-        s = np.zeros(ncol)
-        for j in range(nz):
-            s = s + part[:, j]
-        return s
-
-    t = np.zeros(ncol)
-    accepted, rejected, status = np.zeros(ncol, np.int64), np.zeros(ncol, np.int64), np.zeros(ncol, np.int64)
-    evals = np.zeros(ncol, np.int64)
-    if not t_span > 0:
-        return dict(u=u0.copy(), t=t, dt=np.zeros(ncol), accepted=accepted, rejected=rejected, status=status, evals=evals)
-    with np.errstate(all="ignore"):
-        u = np.where(u0 < 0, 0.0, u0)   # the clamp of the first evaluation, in place in the reference
-        atol = abstol * norms * np.ones_like(u)
-        k1 = rhs(u)
-        evals += 1
-        dt0 = opts.get("dt")
-        dt = np.zeros(ncol) if dt0 is None else np.broadcast_to(np.asarray(dt0, dtype=np.float64), (ncol,)).copy()
-        auto = ~((dt > 0) & np.isfinite(dt))
-        sc = atol + reltol * np.abs(u)
-        d0, d1 = np.sqrt(column_sum((u / sc) ** 2) / count), np.sqrt(column_sum((k1 / sc) ** 2) / count)
-        dt = np.where(auto, np.where(d1 == 0, t_span, 0.01 * d0 / d1), dt)
-        dt = np.where(dt > t_span, t_span, dt)
-        qold = np.full(ncol, QOLD0)
-        active = np.ones(ncol, bool)
-        t_last, dt_min = t_span * (1 - 4 * EPS), 1e-14 * t_span
-        while True:
-            over = active & (accepted + rejected >= max_steps)
-            status[over], active[over] = MAX_STEPS, False
-            small = active & (~(dt >= dt_min) | ~np.isfinite(dt))
-            status[small], active[small] = DT_MIN, False
-            if not active.any():
-                break
-            last = t + dt >= t_last
-            h = np.where(last, t_span - t, dt)
-            hc = cells(h)
-            k = [k1]
-            for row in A_ROWS[:-1]:
-                k.append(rhs(u + hc * sum(a * ki for a, ki in zip(row, k))))
-            u_new = u + hc * sum(a * ki for a, ki in zip(A_ROWS[-1], k))
-            u_new = np.where(u_new < 0, 0.0, u_new)
-            k.append(rhs(u_new))
-            evals[active] += 6
-            err = hc * sum(b * ki for b, ki in zip(BTILDE, k))
-            sc = atol + reltol * np.maximum(np.abs(u), np.abs(u_new))
-            eest = np.sqrt(column_sum((err / sc) ** 2) / count)
-            fin = np.isfinite(eest)
-            q11 = np.where(eest > 0, np.where(fin, eest, 1.0) ** BETA1, 0.0)
-            q = np.clip(q11 / qold ** BETA2 / GAMMA, 1 / QMAX, 1 / QMIN)
-            acc = active & fin & (eest <= 1)
-            rej = active & ~acc
-            dt_acc = np.maximum(h / q, np.minimum(dt, dt / q))
-            dt_rej = np.where(fin, h / np.minimum(1 / QMIN, q11 / GAMMA), h / 5.0)
-            t = np.where(acc, np.where(last, t_span, t + h), t)
-            dt = np.where(acc, dt_acc, np.where(rej, dt_rej, dt))
-            qold = np.where(acc, np.maximum(eest, QOLD0), qold)
-            u = np.where(cells(acc), u_new, u)
-            k1 = np.where(cells(acc), k[6], k1)
-            accepted += acc
-            rejected += rej
-            active &= ~(acc & last)
-    return dict(u=u, t=t, dt=dt, accepted=accepted, rejected=rejected, status=status, evals=evals)
 
 
 def column_rhs_host(oracle, op, nz, dz, xi=0.0, s=None):
@@ -156,9 +76,10 @@ def column_reference(oracle, case, reltol=1e-6, max_steps=10000, dt=None, t_span
     s = supersaturation(NZ, DZ, NCOL)[: u0.shape[1]]
     f = column_rhs_host(oracle, op, NZ, DZ, xi, s if cond else None)
     rhs = f if perturb is None else (lambda u: f(u) * perturb(u.shape))
-    res = adaptive_tsit5_column_host(rhs, u0, NZ, T_SPAN[case] if t_span is None else t_span,
-                                     dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, dt=dt,
-                                          plane_norms=plane_norms((3,) * len(dist_types))))
+    # normalised=False: the column kernels keep the state physical (abstol_i = abstol norm_i), whatever the plan's thresholds
+    res = adaptive_tsit5(rhs, u0, T_SPAN[case] if t_span is None else t_span,
+                         dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, dt=dt, plane_norms=plane_norms((3,) * len(dist_types)),
+                              normalised=False), nz=NZ, clamp=True)
     return u0, s, res
 
 
@@ -177,7 +98,7 @@ def column_reference_cached(case, first="auto", reltol=1e-6, max_steps=10000, co
 def test_columns_of_one_cell_are_the_per_parcel_restatement(oracle):
     """nz = 1: the column norm is the parcel's, nothing couples the cells, and -- on an input on which the clamp never acts (a
     Golovin box: M0 falls towards a positive limit, M1 stays, M2 grows) -- the restatement reproduces
-    adaptive_tsit5_host(normalised=False) bit for bit: state, t, dt and counts."""
+    adaptive_tsit5(clamp=False), both with normalised=False, bit for bit: state, t, dt and counts."""
     from test_tsit5_adaptive_host import GOLOVIN_KC, GOLOVIN_T, golovin_batch
 
     op = oracle.make_params([oracle.GAMMA], np.array(GOLOVIN_KC), (INF,), norms=bench.NORMS)
@@ -188,9 +109,10 @@ def test_columns_of_one_cell_are_the_per_parcel_restatement(oracle):
         seen.append(float(u.min()))
         return oracle.rhs_coal_batch(op, u)
 
-    o = dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=plane_norms((3,)), dt=GOLOVIN_T / 6)   # (a first step the dense parcels reject)
-    want = adaptive_tsit5_host(rhs, u0, GOLOVIN_T, dict(o, normalised=False))
-    got = adaptive_tsit5_column_host(rhs, u0, 1, GOLOVIN_T, o)
+    # (dt: a first step the dense parcels reject)
+    o = dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=plane_norms((3,)), dt=GOLOVIN_T / 6, normalised=False)
+    want = adaptive_tsit5(rhs, u0, GOLOVIN_T, o)
+    got = adaptive_tsit5(rhs, u0, GOLOVIN_T, o, nz=1, clamp=True)
     assert min(seen) > 0.0                              # the clamp never acted, in either run
     assert want["rejected"].sum() > 0 and want["accepted"].max() > 4 * want["accepted"].min()
     for key in ("u", "t", "dt", "accepted", "rejected", "status", "evals"):
@@ -238,17 +160,11 @@ ARGS = ["ptr", "size_t", "size_t", "size_t", "ptr", "ptr", "int", "ptr", "double
 
 
 def test_symbol_in_header_ctypes_table_julia_shim_and_python(cloudy):
-    protos = _c_prototypes()
-    assert protos[NAME] == ("int", ARGS)
-    res, argtypes = cloudy._lib.SYMBOLS[NAME]
-    assert res is C.c_int and len(argtypes) == len(ARGS) and hasattr(cloudy.lib(), NAME)
+    assert_symbol_agrees(cloudy, NAME, ARGS)
     ctype_of = {"ptr": (C.c_void_p, C.POINTER(cloudy._lib.AdaptiveOptsC)), "size_t": (C.c_size_t,), "int": (C.c_int,), "double": (C.c_double,)}
-    for a, c in zip(argtypes, ARGS):
+    for a, c in zip(cloudy._lib.SYMBOLS[NAME][1], ARGS):
         assert a in ctype_of[c], (a, c)
-    src = open(os.path.join(ROOT, "julia", "CloudyHIP.jl")).read()
-    calls = [c for c in _julia_ccalls(src) if c[0] == NAME]
-    assert len(calls) == 1 and calls[0][1] == "Cint" and len(calls[0][2]) == len(ARGS)
-    assert "function solve_rainshaft_tsit5_adaptive!(u, plan::Plan, nz, dz, t_span;" in src
+    assert "function solve_rainshaft_tsit5_adaptive!(u, plan::Plan, nz, dz, t_span;" in open(os.path.join(ROOT, "julia", "CloudyHIP.jl")).read()
     assert "solve_rainshaft_tsit5_adaptive" in cloudy.__all__
     sig = inspect.signature(cloudy.solve_rainshaft_tsit5_adaptive).parameters
     assert list(sig) == ["par", "u", "t_span", "xi", "s", "reltol", "abstol", "dt", "max_steps", "out", "dt_dev", "info", "stream"]
@@ -261,7 +177,7 @@ def test_symbol_in_header_ctypes_table_julia_shim_and_python(cloudy):
 
 def test_argument_checks_answer_einval_with_a_message(cloudy):
     L, E = cloudy.lib(), cloudy._lib
-    nan, inf = float("nan"), float("inf")
+    nan = float("nan")
     dummy = C.c_void_p(64)   # never dereferenced: every check below precedes any device work
 
     def call(opts="default", nz=20, ncol=2, ld=40, t_span=1.0, u_in=dummy, u_out=dummy, sources=3, xi=1e-8, dz=150.0, **kw):
@@ -275,25 +191,7 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
     assert call() == E.EINVAL and msg() == "plan is NULL"          # everything else is in order
     assert call(sources=1) == E.EINVAL and msg() == "plan is NULL"
     assert call(ncol=0, ld=0, u_in=None, u_out=None) == E.EINVAL and msg() == "plan is NULL"
-    assert call(opts=None) == E.EINVAL and msg() == "opts is NULL"
-    short = default_opts(cloudy)
-    short.struct_size -= 8
-    assert call(opts=short) == E.EINVAL and "struct_size" in msg()
-    for bad in (0.0, -1e-6, nan, inf):
-        assert call(reltol=bad) == E.EINVAL and "reltol" in msg(), bad
-    for bad in (-1e-9, nan, inf):
-        assert call(abstol=bad) == E.EINVAL and "abstol" in msg(), bad
-    assert call(abstol=0.0) == E.EINVAL and msg() == "plan is NULL"
-    for bad in (-1.0, nan, inf):
-        assert call(dt_init=bad) == E.EINVAL and "dt_init" in msg(), bad
-    for bad in (-1.0, nan, inf, -inf):
-        assert call(t_span=bad) == E.EINVAL and "t_span" in msg(), bad
-    assert call(t_span=0.0) == E.EINVAL and msg() == "plan is NULL"
-    for bad in (0, -1, 1000001):
-        assert call(max_steps=bad) == E.EINVAL and "max_steps" in msg(), bad
-    assert call(ld=39) == E.EINVAL and "ld (39) must be >= n_parcels (40)" in msg()
-    assert call(u_in=None) == E.EINVAL and msg() == "device buffer is NULL"
-    assert call(u_out=None) == E.EINVAL and msg() == "device buffer is NULL"
+    assert_adaptive_opts_refusals(cloudy, call, msg, n_parcels=40)
     for bad in (0, 2, 4, -1):                           # CLOUDY_SRC_COND alone is not a column right-hand side
         assert call(sources=bad) == E.EINVAL and "sources" in msg(), bad
     assert call(nz=0, ncol=2, ld=40) == E.EINVAL and "nz" in msg()

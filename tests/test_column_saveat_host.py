@@ -1,7 +1,7 @@
 """CPU-only checks of the dense output of the per-column adaptive Tsit5 (cloudy_rainshaft_tsit5_adaptive_saveat,
-csrc/adaptive_column.hpp with SAVE = true): a NumPy restatement (`adaptive_tsit5_column_saveat_host`: the loop of
-test_column_adaptive_host.adaptive_tsit5_column_host plus the snapshot rule, one cursor per column, interpolated snapshots clamped
-to >= 0) that leaves the integration bit for bit alone, the snapshot paths the batch of the GPU tests walks, the sensitivity of the
+csrc/adaptive_column.hpp with SAVE = true): the NumPy restatement with snapshots (tsit5_restated.adaptive_tsit5 with nz cells per
+group, clamp=True and t_save: the loop of test_column_adaptive_host plus the snapshot rule, one cursor per column, interpolated snapshots
+clamped to >= 0) that leaves the integration bit for bit alone, the snapshot paths the batch of the GPU tests walks, the sensitivity of the
 snapshots to the last bit of the right-hand side, the accuracy of the interpolant inside a step against the step's end, the ABI,
 the argument checks of the C entry point in their order, and the plan-time units compiling for gfx950 without a device.
 
@@ -16,132 +16,18 @@ import numpy as np
 import pytest
 
 import bench
-from test_column_adaptive_host import (CASES, DT0, FIRST, T_SPAN, adaptive_tsit5_column_host, column_batch, column_reference,
-                                       column_reference_cached, column_rhs_host, oracle_case)
+from test_column_adaptive_host import (CASES, DT0, FIRST, T_SPAN, column_batch, column_reference, column_reference_cached, column_rhs_host,
+                                       oracle_case)
 from test_gpu_column_sources import DZ, GOLOVIN, NCOL, NZ, VEL, XI, supersaturation
-from test_host_abi import INF, ROOT, _c_prototypes, _julia_ccalls
-from test_tsit5_adaptive_host import (A_ROWS, BETA1, BETA2, BTILDE, DONE, DT_MIN, EPS, GAMMA, MAX_STEPS, QMAX, QMIN, QOLD0, default_opts,
-                                      last_bit_noise, plane_norms)
-from test_tsit5_saveat_host import SAVE_FRACS, interp_weights, save_times, saveat_tsit5_host
+from test_host_abi import INF, ROOT, _c_prototypes
+from tsit5_restated import (DONE, MAX_STEPS, SAVE_FRACS, adaptive_tsit5, assert_adaptive_opts_refusals, assert_symbol_agrees, default_opts,
+                            last_bit_noise, plane_norms, save_times)
 
 NAME = "cloudy_rainshaft_tsit5_adaptive_saveat"
 # what the GPU test asks of every snapshot, in units of the maximum of its plane (the bound of the column parity test), and what
 # the restatement must resolve for that bound to mean anything: a tenth
 SNAPSHOT_BOUND = 1e-9
 KEYS = ("u", "t", "dt", "accepted", "rejected", "status", "evals")
-
-
-def adaptive_tsit5_column_saveat_host(rhs, u0, nz, t_span, t_save, opts):
-    """adaptive_tsit5_column_host (same arguments, same loop, same expressions) + the snapshot rule of
-    cloudy_rainshaft_tsit5_adaptive_saveat.  Every COLUMN keeps a cursor; after an accepted step t -> t_new every save time
-    t_save[j] <= t_new the cursor has not passed gets, in every cell of the column, max(u + h sum_i b_i(th) k_i, 0) with
-    th = (t_save[j] - t) / h, or the clamped u_new itself where t_save[j] == t_new; a save time 0 gets the input as it is (not
-    clamped); what a column does not reach stays NaN; t_span = 0: every snapshot is the input.  Returns the dict of
-    adaptive_tsit5_column_host + saved (n_save, planes, n) + in_step: per column the number of save times that fell into each
-    accepted step (a save time 0 belongs to none) + rejected_before: per column the rejected steps it had when it took its first
-    snapshot inside a step (-1: it took none)."""
-    reltol, abstol, max_steps = float(opts["reltol"]), float(opts["abstol"]), int(opts["max_steps"])
-    norms = np.asarray(opts["plane_norms"], dtype=np.float64)[:, None]
-    t_save = np.asarray(t_save, dtype=np.float64)
-    n_save = t_save.size
-    planes, n = u0.shape
-    ncol = n // nz
-    assert ncol * nz == n
-    count = planes * nz
-    cells = lambda x: np.repeat(x, nz)   # noqa: E731  a column's value on its cells
-
-    def column_sum(x):
-        part = x.sum(axis=0).reshape(ncol, nz)
-        s = np.zeros(ncol)
-        for j in range(nz):
-            s = s + part[:, j]
-        return s
-
-    saved = np.full((n_save, planes, n), np.nan)
-    in_step = [[] for _ in range(ncol)]
-    rejected_before = np.full(ncol, -1, np.int64)
-    t = np.zeros(ncol)
-    accepted, rejected, status = np.zeros(ncol, np.int64), np.zeros(ncol, np.int64), np.zeros(ncol, np.int64)
-    evals = np.zeros(ncol, np.int64)
-    if not t_span > 0:
-        saved[:] = u0[None]
-        return dict(u=u0.copy(), t=t, dt=np.zeros(ncol), accepted=accepted, rejected=rejected, status=status, evals=evals, saved=saved,
-                    in_step=in_step, rejected_before=rejected_before)
-    cursor = np.zeros(ncol, np.int64)
-    if n_save and t_save[0] == 0.0:
-        saved[0] = u0
-        cursor += 1
-    with np.errstate(all="ignore"):
-        u = np.where(u0 < 0, 0.0, u0)
-        atol = abstol * norms * np.ones_like(u)
-        k1 = rhs(u)
-        evals += 1
-        dt0 = opts.get("dt")
-        dt = np.zeros(ncol) if dt0 is None else np.broadcast_to(np.asarray(dt0, dtype=np.float64), (ncol,)).copy()
-        auto = ~((dt > 0) & np.isfinite(dt))
-        sc = atol + reltol * np.abs(u)
-        d0, d1 = np.sqrt(column_sum((u / sc) ** 2) / count), np.sqrt(column_sum((k1 / sc) ** 2) / count)
-        dt = np.where(auto, np.where(d1 == 0, t_span, 0.01 * d0 / d1), dt)
-        dt = np.where(dt > t_span, t_span, dt)
-        qold = np.full(ncol, QOLD0)
-        active = np.ones(ncol, bool)
-        t_last, dt_min = t_span * (1 - 4 * EPS), 1e-14 * t_span
-        while True:
-            over = active & (accepted + rejected >= max_steps)
-            status[over], active[over] = MAX_STEPS, False
-            small = active & (~(dt >= dt_min) | ~np.isfinite(dt))
-            status[small], active[small] = DT_MIN, False
-            if not active.any():
-                break
-            last = t + dt >= t_last
-            h = np.where(last, t_span - t, dt)
-            hc = cells(h)
-            k = [k1]
-            for row in A_ROWS[:-1]:
-                k.append(rhs(u + hc * sum(a * ki for a, ki in zip(row, k))))
-            u_new = u + hc * sum(a * ki for a, ki in zip(A_ROWS[-1], k))
-            u_new = np.where(u_new < 0, 0.0, u_new)
-            k.append(rhs(u_new))
-            evals[active] += 6
-            err = hc * sum(b * ki for b, ki in zip(BTILDE, k))
-            sc = atol + reltol * np.maximum(np.abs(u), np.abs(u_new))
-            eest = np.sqrt(column_sum((err / sc) ** 2) / count)
-            fin = np.isfinite(eest)
-            q11 = np.where(eest > 0, np.where(fin, eest, 1.0) ** BETA1, 0.0)
-            q = np.clip(q11 / qold ** BETA2 / GAMMA, 1 / QMAX, 1 / QMIN)
-            acc = active & fin & (eest <= 1)
-            rej = active & ~acc
-            dt_acc = np.maximum(h / q, np.minimum(dt, dt / q))
-            dt_rej = np.where(fin, h / np.minimum(1 / QMIN, q11 / GAMMA), h / 5.0)
-            t_new = np.where(last, t_span, t + h)
-            # ---- the snapshots of this step (nothing below feeds back into the integration)
-            taken = np.zeros(ncol, np.int64)
-            while n_save:
-                ts = t_save[np.minimum(cursor, n_save - 1)]
-                m = acc & (cursor < n_save) & (ts <= t_new)
-                if not m.any():
-                    break
-                b = interp_weights(cells((ts - t) / h))
-                mid = u + hc * sum(bi * ki for bi, ki in zip(b, k))
-                val = np.where(cells(ts == t_new), u_new, np.where(mid < 0, 0.0, mid))
-                for c in np.flatnonzero(m):
-                    saved[cursor[c], :, c * nz:(c + 1) * nz] = val[:, c * nz:(c + 1) * nz]
-                    if rejected_before[c] < 0:
-                        rejected_before[c] = rejected[c]
-                cursor[m] += 1
-                taken[m] += 1
-            for c in np.flatnonzero(acc):
-                in_step[c].append(int(taken[c]))
-            t = np.where(acc, t_new, t)
-            dt = np.where(acc, dt_acc, np.where(rej, dt_rej, dt))
-            qold = np.where(acc, np.maximum(eest, QOLD0), qold)
-            u = np.where(cells(acc), u_new, u)
-            k1 = np.where(cells(acc), k[6], k1)
-            accepted += acc
-            rejected += rej
-            active &= ~(acc & last)
-    return dict(u=u, t=t, dt=dt, accepted=accepted, rejected=rejected, status=status, evals=evals, saved=saved, in_step=in_step,
-                rejected_before=rejected_before)
 
 
 def column_saveat_reference(oracle, case, reltol=1e-6, max_steps=10000, dt=None, t_span=None, t_save=None, perturb=None):
@@ -154,8 +40,9 @@ def column_saveat_reference(oracle, case, reltol=1e-6, max_steps=10000, dt=None,
     rhs = f if perturb is None else (lambda u: f(u) * perturb(u.shape))
     t_span = T_SPAN[case] if t_span is None else t_span
     ts = save_times(t_span) if t_save is None else np.asarray(t_save, dtype=np.float64)
-    res = adaptive_tsit5_column_saveat_host(rhs, u0, NZ, t_span, ts, dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, dt=dt,
-                                                                          plane_norms=plane_norms((3,) * len(dist_types))))
+    res = adaptive_tsit5(rhs, u0, t_span, dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, dt=dt,
+                                               plane_norms=plane_norms((3,) * len(dist_types)), normalised=False),
+                         nz=NZ, clamp=True, t_save=ts)   # (normalised=False: the state of a column is physical, as in column_reference)
     return u0, s, ts, res
 
 
@@ -194,14 +81,14 @@ def test_restatement_integrates_as_the_one_without_snapshots(case, first):
     assert res["saved"].shape == (len(SAVE_FRACS), u0.shape[0], NCOL * NZ) and np.isfinite(res["saved"]).all()
     assert np.array_equal(res["saved"][0], u0) and np.array_equal(res["saved"][-1], res["u"])
     assert all(sum(st) == len(SAVE_FRACS) - 1 and len(st) == a for st, a in zip(res["in_step"], res["accepted"]))
-    zero = adaptive_tsit5_column_saveat_host(None, u0, NZ, 0.0, [0.0], dict(reltol=1e-6, abstol=1e-9, max_steps=10,
-                                                                              plane_norms=np.ones(u0.shape[0])))
+    zero = adaptive_tsit5(None, u0, 0.0, dict(reltol=1e-6, abstol=1e-9, max_steps=10, plane_norms=np.ones(u0.shape[0]), normalised=False),
+                          nz=NZ, clamp=True, t_save=[0.0])
     assert np.array_equal(zero["saved"][0], u0)
 
 
 def test_columns_of_one_cell_are_the_per_parcel_restatement_with_snapshots(oracle):
     """nz = 1 on the Golovin batch of test_columns_of_one_cell_are_the_per_parcel_restatement, on which the clamp never acts:
-    saveat_tsit5_host(normalised=False) bit for bit, the snapshots included."""
+    adaptive_tsit5(clamp=False), both with normalised=False and the save times, bit for bit, the snapshots included."""
     from test_tsit5_adaptive_host import GOLOVIN_KC, GOLOVIN_T, golovin_batch
 
     op = oracle.make_params([oracle.GAMMA], np.array(GOLOVIN_KC), (INF,), norms=bench.NORMS)
@@ -213,9 +100,9 @@ def test_columns_of_one_cell_are_the_per_parcel_restatement_with_snapshots(oracl
         return oracle.rhs_coal_batch(op, u)
 
     ts = save_times(GOLOVIN_T)
-    o = dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=plane_norms((3,)), dt=GOLOVIN_T / 6)
-    want = saveat_tsit5_host(rhs, u0, GOLOVIN_T, ts, dict(o, normalised=False))
-    got = adaptive_tsit5_column_saveat_host(rhs, u0, 1, GOLOVIN_T, ts, o)
+    o = dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=plane_norms((3,)), dt=GOLOVIN_T / 6, normalised=False)
+    want = adaptive_tsit5(rhs, u0, GOLOVIN_T, o, t_save=ts)
+    got = adaptive_tsit5(rhs, u0, GOLOVIN_T, o, nz=1, clamp=True, t_save=ts)
     assert min(seen) > 0.0 and want["saved"].min() > 0.0    # the clamp never acted, on a stage argument or on a snapshot
     assert want["rejected"].sum() > 0
     for key in KEYS + ("saved",):
@@ -306,17 +193,14 @@ ARGS = ["ptr", "size_t", "size_t", "size_t", "ptr", "ptr", "int", "ptr", "double
 
 def test_symbol_in_header_ctypes_table_julia_shim_and_python(cloudy):
     protos = _c_prototypes()
-    assert len(ARGS) == 20 and protos[NAME] == ("int", ARGS)
+    assert len(ARGS) == 20
+    assert_symbol_agrees(cloudy, NAME, ARGS)
     assert protos[NAME][1] == protos["cloudy_rainshaft_tsit5_adaptive"][1] + protos["cloudy_tsit5_adaptive_saveat"][1][-3:]
-    res, argtypes = cloudy._lib.SYMBOLS[NAME]
-    assert res is C.c_int and len(argtypes) == len(ARGS) and hasattr(cloudy.lib(), NAME)
     ctype_of = {"ptr": (C.c_void_p, C.POINTER(cloudy._lib.AdaptiveOptsC), C.POINTER(C.c_double)), "size_t": (C.c_size_t,), "int": (C.c_int,),
                 "double": (C.c_double,)}
-    for a, c in zip(argtypes, ARGS):
+    for a, c in zip(cloudy._lib.SYMBOLS[NAME][1], ARGS):
         assert a in ctype_of[c], (a, c)
     src = open(os.path.join(ROOT, "julia", "CloudyHIP.jl")).read()
-    calls = [c for c in _julia_ccalls(src) if c[0] == NAME]
-    assert len(calls) == 1 and calls[0][1] == "Cint" and len(calls[0][2]) == len(ARGS)
     assert "function solve_rainshaft_tsit5_adaptive_saveat!(u, usave, plan::Plan, nz, dz, t_span, t_save;" in src
     assert "solve_rainshaft_tsit5_adaptive_saveat" in cloudy.__all__
     sig = inspect.signature(cloudy.solve_rainshaft_tsit5_adaptive_saveat).parameters
@@ -339,11 +223,11 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
     cap = int(re.search(r"#define CLOUDY_MAX_SAVE_TIMES (\d+)", open(os.path.join(ROOT, "include", "cloudy_hip.h")).read()).group(1))
 
     def call(times=(0.0, 0.25, 1.0), n_save=None, t_save="times", u_save=dummy, nz=20, ncol=2, ld=40, t_span=1.0, u_in=dummy, u_out=dummy,
-             sources=3, xi=1e-8, dz=150.0, **kw):
-        o = default_opts(cloudy, **kw)
+             sources=3, xi=1e-8, dz=150.0, opts="default", **kw):
+        o = default_opts(cloudy, **kw) if opts == "default" else opts
         arr = (C.c_double * max(len(times), 1))(*times)
-        return getattr(L, NAME)(None, nz, ncol, ld, u_in, u_out, sources, None, 0.01, xi, dz, t_span, C.byref(o), None, None, None, None,
-                                len(times) if n_save is None else n_save, arr if t_save == "times" else t_save, u_save)
+        return getattr(L, NAME)(None, nz, ncol, ld, u_in, u_out, sources, None, 0.01, xi, dz, t_span, None if o is None else C.byref(o), None,
+                                None, None, None, len(times) if n_save is None else n_save, arr if t_save == "times" else t_save, u_save)
 
     def msg():
         return L.cloudy_last_error().decode()
@@ -365,9 +249,8 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
         assert call(times=bad, **later) == E.EINVAL and "t_save" in msg() and "strictly increasing" in msg(), bad
     # then the column's checks, in the order of cloudy_rainshaft_tsit5_adaptive
     assert call(reltol=0.0, ld=1, sources=0) == E.EINVAL and "reltol" in msg()
-    assert call(times=(), t_save=None, u_save=None, t_span=-1.0) == E.EINVAL and "t_span" in msg()
-    assert call(ld=39, sources=0, dz=-1.0) == E.EINVAL and "ld (39) must be >= n_parcels (40)" in msg()
-    assert call(u_in=None, sources=0) == E.EINVAL and msg() == "device buffer is NULL"
+    assert_adaptive_opts_refusals(cloudy, call, msg, n_parcels=40, no_times=dict(times=(), t_save=None, u_save=None),
+                                  later=(dict(sources=0), dict(sources=0, dz=-1.0)))
     for bad in (0, 2, 4, -1):
         assert call(sources=bad, nz=0, dz=-1.0) == E.EINVAL and "sources" in msg(), bad
     assert call(nz=0, ncol=2, ld=40, xi=nan) == E.EINVAL and "nz" in msg()

@@ -1,6 +1,6 @@
 """GPU tests of cloudy_box_tsit5_adaptive (csrc/adaptive_box.hpp): per-parcel adaptive Tsit5 of du/dt = [coal](u) + [cond](u; s, xi).
-The references are the NumPy restatements adaptive_tsit5_host / saveat_tsit5_host driven by the unchanged oracle's rhs_coal_batch +
-rhs_condensation_batch (tests/test_box_adaptive_host.py holds the batches and measures the restatement on them), the closed form of
+The reference is the NumPy restatement tsit5_restated.adaptive_tsit5 (without and with t_save) driven by the unchanged oracle's
+rhs_coal_batch + rhs_condensation_batch (tests/test_box_adaptive_host.py holds the batches and measures the restatement on them), the closed form of
 a Monodisperse mode under condensation, the fixed-step tableau (_tsit5_host) at a fine step, and cloudy_tsit5_adaptive itself.
 
 Run with `-m gpu`.  Batch sizes 1, 65 and 257: a single parcel, a partial wave past one wave, a partial workgroup past one
@@ -15,10 +15,10 @@ import pytest
 import bench
 import test_box_adaptive_host as B
 import test_tsit5_adaptive_host as H
-import test_tsit5_saveat_host as S
 from test_gpu_parity import INF, _tsit5_host, dev, make_case
 from test_gpu_tsit5_adaptive import SENTINEL, SIZES, adaptive, same_counts, sentinel_planes, two_gamma_plan
 from test_gpu_tsit5_saveat import SENTINEL32, bits_equal, blank_bits
+from tsit5_restated import adaptive_tsit5, default_opts, plane_norms, save_times
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +52,7 @@ def box_adaptive(cloudy, plan, u0, t_span, s, xi, sources=COAL | COND, times=(),
     n_save = len(times)
     snap = dev(cloudy, blank(max(n_save, 1) * planes))
     arr = (C.c_double * max(n_save, 1))(*times)
-    opts = H.default_opts(cloudy, reltol=reltol, abstol=abstol, max_steps=max_steps)
+    opts = default_opts(cloudy, reltol=reltol, abstol=abstol, max_steps=max_steps)
     rc = L.cloudy_box_tsit5_adaptive(plan.handle, n, ld, u_in.ptr, u_out.ptr, sources, None if s_d is None else s_d.ptr,
                                      0.0 if s_d is not None else float(s), xi, t_span, C.byref(opts), dt_d.ptr, t_d.ptr, info.ptr, None,
                                      n_save, arr if n_save else None, snap.ptr if n_save else None)
@@ -72,7 +72,7 @@ def box_runs(cloudy, oracle, kind, n):
     u0 = H.two_gamma_batch(n, kind=kind)
     t_span, s = H.TWO_GAMMA_T[kind], B.box_supersaturation(n)
     return (u0, box_adaptive(cloudy, plan, u0, t_span, s, B.XI_BOX, ld=n + 15),
-            box_adaptive(cloudy, plan, u0, t_span, s, B.XI_BOX, times=S.save_times(t_span), ld=n + 15))
+            box_adaptive(cloudy, plan, u0, t_span, s, B.XI_BOX, times=save_times(t_span), ld=n + 15))
 
 
 # ---- 1. closed form
@@ -192,7 +192,7 @@ def test_batch_independence(gpu_cloudy, oracle, which):
 def test_dense_output(gpu_cloudy, oracle, case):
     """The twelve save times: u_out, dt, t, info have the bits of the n_save = 0 call; the snapshot at 0 has the input's bits, the
     one at t_span u_out's; for the parcels with the restatement's counts (at least 95 %) every snapshot agrees with
-    saveat_tsit5_host to 1e-11 x evaluations of |u0| + |want| (the bound of test_gpu_tsit5_saveat with this file's tolerance);
+    adaptive_tsit5 with t_save to 1e-11 x evaluations of |u0| + |want| (the bound of test_gpu_tsit5_saveat with this file's tolerance);
     padding untouched."""
     cloudy = gpu_cloudy
     if case == "cond":
@@ -200,7 +200,7 @@ def test_dense_output(gpu_cloudy, oracle, case):
         n = 257
         u0, s, _, ref, _ = B.cond_case(n, 1e-6, True)
         base = box_adaptive(cloudy, plan, u0, B.COND_T, s, B.XI_COND, sources=COND, ld=n + 15)
-        got = box_adaptive(cloudy, plan, u0, B.COND_T, s, B.XI_COND, sources=COND, times=S.save_times(B.COND_T), ld=n + 15)
+        got = box_adaptive(cloudy, plan, u0, B.COND_T, s, B.XI_COND, sources=COND, times=save_times(B.COND_T), ld=n + 15)
     else:
         n = 257 if case == "allinf" else 65
         u0, base, got = box_runs(cloudy, oracle, case, n)
@@ -226,7 +226,7 @@ def test_budget_leaves_nan_beyond_the_time_reached(gpu_cloudy, oracle):
     _, _, plan = two_gamma_plan(cloudy, oracle, "allinf")
     u0, s = H.two_gamma_batch(257), B.box_supersaturation(257)
     t_span = H.TWO_GAMMA_T["allinf"]
-    ts = S.save_times(t_span)
+    ts = save_times(t_span)
     got = box_adaptive(cloudy, plan, u0, t_span, s, B.XI_BOX, times=ts, max_steps=3, ld=257 + 15)
     slow = got["status"] == 1
     assert 5 <= slow.sum() < 257 and np.all(got["status"][~slow] == 0) and np.all(got["t"][slow] < t_span)
@@ -289,8 +289,8 @@ def test_served_and_refused(gpu_cloudy, oracle):
     numerical = cloudy.numerical_plan([1, 1], cloudy.LinearKernelFunction(5e-3), bench.NORMS, 10, quad_mode=cloudy.QUAD_FIXED)
     op, _, _, _ = H.two_gamma_case(oracle, "allinf")
     u0, s = H.two_gamma_batch(65), B.box_supersaturation(65)
-    ref = H.adaptive_tsit5_host(lambda u: oracle.rhs_condensation_batch(op, B.XI_COND, s, u), u0, B.COND_T,
-                                dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=H.plane_norms((3, 3))))
+    ref = adaptive_tsit5(lambda u: oracle.rhs_condensation_batch(op, B.XI_COND, s, u), u0, B.COND_T,
+                         dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=plane_norms((3, 3))))
     got = box_adaptive(cloudy, numerical, u0, B.COND_T, s, B.XI_COND, sources=COND, ld=80)
     assert np.all(ref["status"] == 0) and np.all(got["status"] == 0) and np.all(got["t"] == B.COND_T)
     same = same_counts(got, ref)
@@ -303,7 +303,7 @@ def test_served_and_refused(gpu_cloudy, oracle):
     _, _, fast = two_gamma_plan(cloudy, oracle, "fixed", dtype=2)          # CLOUDY_F32_FAST
     _, _, aot = two_gamma_plan(cloudy, oracle, "allinf", specialize=-1)    # no plan-time compilation
     for what, plan, batch in (("numerical", numerical, g0), ("CLOUDY_F32_FAST", fast, g0.astype(np.float32)), ("specialize = -1", aot, g0)):
-        ts = S.save_times(1e-3)
+        ts = save_times(1e-3)
         got = box_adaptive(cloudy, plan, batch, 1e-3, 0.05, B.XI_BOX, times=ts, expect=E.EUNSUPPORTED)
         msg = L.cloudy_last_error().decode()
         assert "cloudy_cond_evap" in msg and "stage by stage" in msg, (what, msg)
@@ -318,7 +318,7 @@ def test_python_wrapper(gpu_cloudy, oracle):
     n = 257
     u0, s = H.two_gamma_batch(n), B.box_supersaturation(n)
     t_span = H.TWO_GAMMA_T["allinf"]
-    ts = S.save_times(t_span)
+    ts = save_times(t_span)
     want = box_adaptive(cloudy, plan, u0, t_span, s, B.XI_BOX, times=ts)
     s_d = dev(cloudy, s[None, :])
     u = dev(cloudy, u0)

@@ -1,7 +1,7 @@
 """GPU tests of the per-column adaptive Tsit5 for rainshaft columns (cloudy_rainshaft_tsit5_adaptive, csrc/adaptive_column.hpp).
 
-The reference is the NumPy restatement of tests/test_column_adaptive_host.py (adaptive_tsit5_column_host) on the oracle's column
-right-hand side, on the batch that module picks: 27 columns of 20 cells -- two workgroups at 512 threads, three at 256 --
+The reference is the NumPy restatement of tests/test_column_adaptive_host.py (tsit5_restated.adaptive_tsit5 with clamp=True) on the
+oracle's column right-hand side, on the batch that module picks: 27 columns of 20 cells -- two workgroups at 512 threads, three at 256 --
 amplitudes over a decade, the supersaturation profile of test_gpu_column_sources.  Run with `-m gpu`."""
 import ctypes as C
 
@@ -11,7 +11,7 @@ import pytest
 from test_column_adaptive_host import CASES, DT0, FIRST, T_SPAN, column_reference_cached
 from test_gpu_column_sources import DZ, NCOL, NZ, SENTINEL, VEL, XI, reference_case
 from test_gpu_parity import dev
-from test_tsit5_adaptive_host import DONE, DT_MIN, MAX_STEPS, default_opts
+from tsit5_restated import DONE, DT_MIN, MAX_STEPS, default_opts
 
 pytestmark = pytest.mark.gpu
 COAL, COALCOND = 1, 3

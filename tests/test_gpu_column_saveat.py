@@ -1,10 +1,10 @@
 """GPU tests of the dense output of the per-column adaptive Tsit5 (cloudy_rainshaft_tsit5_adaptive_saveat, csrc/adaptive_column.hpp
 with SAVE = true).
 
-The reference is the NumPy restatement of tests/test_column_saveat_host.py (adaptive_tsit5_column_saveat_host) on the oracle's
-column right-hand side, on the batch of tests/test_column_adaptive_host.py -- 27 columns of 20 cells, two workgroups at 512 threads,
-COAL | COND with the supersaturation profile on, from the caller's first step DT0 -- at the twelve save times of
-test_tsit5_saveat_host.  Run with `-m gpu`."""
+The reference is the NumPy restatement of tests/test_column_saveat_host.py (tsit5_restated.adaptive_tsit5 with clamp=True and t_save)
+on the oracle's column right-hand side, on the batch of tests/test_column_adaptive_host.py -- 27 columns of 20 cells, two workgroups
+at 512 threads, COAL | COND with the supersaturation profile on, from the caller's first step DT0 -- at the twelve save times of
+tsit5_restated.SAVE_FRACS.  Run with `-m gpu`."""
 import ctypes as C
 
 import numpy as np
@@ -15,7 +15,7 @@ from test_column_saveat_host import SNAPSHOT_BOUND, column_saveat_reference_cach
 from test_gpu_column_adaptive import COALCOND, plan_of, run
 from test_gpu_column_sources import DZ, NCOL, NZ, SENTINEL, VEL, XI
 from test_gpu_parity import dev
-from test_tsit5_adaptive_host import DONE, MAX_STEPS, default_opts
+from tsit5_restated import DONE, MAX_STEPS, default_opts
 
 pytestmark = pytest.mark.gpu
 SENTINEL32 = np.uint32(0x7FC05EED)   # a float NaN no arithmetic produces

@@ -1,6 +1,6 @@
 """GPU tests of cloudy_parcel_tsit5_adaptive (csrc/adaptive_thermo.hpp): per-parcel adaptive Tsit5 of the adiabatic parcel.  The
-references are the NumPy restatements adaptive_tsit5_host / saveat_tsit5_host with plane_norms = (1, 1, 1, 1, the plan's mom_norms)
-on the restated right-hand side of test_parcel_host (tests/test_parcel_adaptive_host.py holds the batches and measures the
+reference is the NumPy restatement tsit5_restated.adaptive_tsit5 (without and with t_save) with plane_norms = (1, 1, 1, 1, the
+plan's mom_norms) on the restated right-hand side of test_parcel_host (tests/test_parcel_adaptive_host.py holds the batches and measures the
 restatement on them), and a reltol = 1e-11 run of the same restatement.
 
 Run with `-m gpu`.  Batch sizes 1, 65 and 257 in buffers of leading dimension n + 15."""
@@ -12,10 +12,10 @@ import pytest
 
 import test_parcel_adaptive_host as A
 import test_tsit5_adaptive_host as H
-import test_tsit5_saveat_host as S
 from test_gpu_parity import INF, dev, make_case
 from test_gpu_tsit5_adaptive import SENTINEL, SIZES, same_counts, sentinel_planes, two_gamma_plan
 from test_gpu_tsit5_saveat import bits_equal, blank_bits
+from tsit5_restated import adaptive_tsit5, default_opts, plane_norms, save_times
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +47,7 @@ def parcel_adaptive(cloudy, plan, y0, w, t_span, sources=COND, times=(), reltol=
     n_save = len(times)
     snap = dev(cloudy, sentinel_planes(max(n_save, 1) * planes, ld))
     arr = (C.c_double * max(n_save, 1))(*times)
-    opts = H.default_opts(cloudy, reltol=reltol, abstol=1e-9, max_steps=max_steps)
+    opts = default_opts(cloudy, reltol=reltol, abstol=1e-9, max_steps=max_steps)
     c = cloudy.ParcelParams().to_c()
     rc = L.cloudy_parcel_tsit5_adaptive(plan.handle, n, ld, y_in.ptr, y_out.ptr, sources, None if w_d is None else w_d.ptr,
                                         0.0 if w_d is not None else float(w), C.byref(c), t_span, C.byref(opts), dt_d.ptr, t_d.ptr,
@@ -115,13 +115,13 @@ def test_decision_parity_with_coalescence(gpu_cloudy, oracle):
 def test_dense_output(gpu_cloudy, oracle):
     """the twelve save times on the decade batch (n = 257): y_out, dt, t and info have the bits of the call without snapshots; the
     snapshot at 0 has the input's bits, the one at t_span y_out's; the snapshots of the parcels with the restatement's counts agree
-    with saveat_tsit5_host to 1e-11 x evaluations; padding untouched."""
+    with adaptive_tsit5(t_save) to 1e-11 x evaluations; padding untouched."""
     cloudy = gpu_cloudy
     n = 257
     _, _, plan = plan_of(cloudy, oracle, (2,))
     y0, w, ref = A.decade_case(n, 1e-6, saveat=True, plan=True)
     base = parcel_adaptive(cloudy, plan, y0, w, A.T_SPAN, ld=n + 15)
-    got = parcel_adaptive(cloudy, plan, y0, w, A.T_SPAN, times=S.save_times(A.T_SPAN), ld=n + 15)
+    got = parcel_adaptive(cloudy, plan, y0, w, A.T_SPAN, times=save_times(A.T_SPAN), ld=n + 15)
     for k in KEYS:
         assert bits_equal(got[k], base[k]), k
     assert np.all(got["status"] == 0) and np.isfinite(got["saved"]).all()
@@ -154,7 +154,7 @@ def test_budget_leaves_nan_beyond_the_time_reached(gpu_cloudy, oracle):
     n = 257
     _, _, plan = plan_of(cloudy, oracle, (2,))
     y0, w = A.decade_batch(n)
-    ts = S.save_times(A.T_SPAN)
+    ts = save_times(A.T_SPAN)
     got = parcel_adaptive(cloudy, plan, y0, w, A.T_SPAN, times=ts, max_steps=3, ld=n + 15)
     slow = got["status"] == 1
     assert 0 < slow.sum() < n and np.all(got["status"][~slow] == 0) and np.all(got["t"][slow] < A.T_SPAN)
@@ -191,7 +191,7 @@ def test_batch_independence(gpu_cloudy, oracle):
     n = 257
     _, _, plan = plan_of(cloudy, oracle, (2,))
     y0, w = A.decade_batch(n)
-    ts = S.save_times(A.T_SPAN)
+    ts = save_times(A.T_SPAN)
     whole = parcel_adaptive(cloudy, plan, y0, w, A.T_SPAN, times=ts)
     attempts = whole["accepted"] + whole["rejected"]
     for i in (int(np.argmax(attempts)), int(np.argmin(attempts)), 0, 63, 64, 255, 256):
@@ -216,9 +216,9 @@ def test_driver_plans_with_the_oracle_tendency(gpu_cloudy, oracle, name):
     N, w = A.decade_draws(n)
     moms = np.array(mom)[:, None] * (N / 2e8)[None, :]
     y0 = np.ascontiguousarray(np.vstack([A.thermo_rows(moms[rows].sum(axis=0)), moms]))
-    norms = np.concatenate([np.ones(4), H.plane_norms(tuple(3 if t in (1, 3) else 2 for t in types), A.NORMS)])
+    norms = np.concatenate([np.ones(4), plane_norms(tuple(3 if t in (1, 3) else 2 for t in types), A.NORMS)])
     rhs = A.oracle_rhs(oracle, op, w, rows, False)
-    run = lambda tol: H.adaptive_tsit5_host(rhs, y0, A.T_SPAN, dict(reltol=tol, abstol=1e-9, max_steps=10000, plane_norms=norms))  # noqa: E731
+    run = lambda tol: adaptive_tsit5(rhs, y0, A.T_SPAN, dict(reltol=tol, abstol=1e-9, max_steps=10000, plane_norms=norms))  # noqa: E731
     ref, tight = run(1e-6), run(1e-11)
     got = parcel_adaptive(cloudy, plan, y0, w, A.T_SPAN, ld=n + 15)
     assert np.all(ref["status"] == 0) and np.all(got["status"] == 0) and np.all(got["t"] == A.T_SPAN)
@@ -249,7 +249,7 @@ def test_served_and_refused(gpu_cloudy, oracle):
     _, _, moving = two_gamma_plan(cloudy, oracle, "moving")
     _, _, f32 = plan_of(cloudy, oracle, (1, 1), golovin, None, A.NORMS, 1)
     _, _, aot = plan_of(cloudy, oracle, (1, 1), golovin, None, A.NORMS, 0, -1)
-    ts = S.save_times(1.0)
+    ts = save_times(1.0)
     for what, plan, sources in (("cfg3b", cfg3b, COAL | COND), ("thresholds", thresholded, COAL | COND), ("moving", moving, COAL | COND),
                                 ("numerical", numerical, COAL | COND), ("F32", f32, COND), ("specialize = -1", aot, COND)):
         got = parcel_adaptive(cloudy, plan, y0, w, 1.0, sources=sources, times=ts, expect=E.EUNSUPPORTED)
@@ -265,7 +265,7 @@ def test_python_wrapper(gpu_cloudy, oracle):
     n = 257
     par, _, plan = plan_of(cloudy, oracle, (2,))
     y0, w = A.decade_batch(n)
-    ts = S.save_times(A.T_SPAN)
+    ts = save_times(A.T_SPAN)
     want = parcel_adaptive(cloudy, plan, y0, w, A.T_SPAN, times=ts)
     w_d = dev(cloudy, w[None, :])
     y = dev(cloudy, y0)

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import bench
+from tsit5_restated import A_ROWS
 
 pytestmark = pytest.mark.gpu
 
@@ -761,22 +762,14 @@ def test_cfg1_single_box_trajectory_ssprk33(gpu_cloudy, oracle):
     assert np.array_equal(u_out.to_numpy(), u0) and np.array_equal(u_in.to_numpy(), u0)
 
 
-_TSIT5_A = ((0.161,),
-            (-0.008480655492356989, 0.335480655492357),
-            (2.8971530571054935, -6.359448489975075, 4.3622954328695815),
-            (5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525),
-            (5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383),
-            (0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774))
-
-
 def _tsit5_host(rhs_fn, u, dt, n_steps):
     """the Tsit5 tableau (Tsitouras 2011; OrdinaryDiffEq's Tsit5()) with a fixed step and a host-side RHS callable"""
     u = u.copy()
     for _ in range(n_steps):
         k = [rhs_fn(u)]
-        for row in _TSIT5_A[:-1]:
+        for row in A_ROWS[:-1]:
             k.append(rhs_fn(u + dt * sum(a * ki for a, ki in zip(row, k))))
-        u = u + dt * sum(a * ki for a, ki in zip(_TSIT5_A[-1], k))
+        u = u + dt * sum(a * ki for a, ki in zip(A_ROWS[-1], k))
     return u
 
 

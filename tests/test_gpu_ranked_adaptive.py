@@ -21,11 +21,11 @@ import pytest
 import test_box_adaptive_host as B
 import test_ranked_adaptive_host as R
 import test_tsit5_adaptive_host as H
-import test_tsit5_saveat_host as S
 from test_gpu_box_adaptive import box_adaptive
 from test_gpu_parity import _tsit5_host, dev
 from test_gpu_tsit5_adaptive import adaptive, same_counts, sentinel_planes, two_gamma_plan
 from test_gpu_tsit5_saveat import bits_equal, blank_bits, saveat
+from tsit5_restated import default_opts, save_times
 
 pytestmark = pytest.mark.gpu
 
@@ -44,8 +44,8 @@ def run(cloudy, oracle, entry, kind, u0, s, t_span, **kw):
     if entry == "adaptive":
         return adaptive(cloudy, plan, u0, t_span, **kw)
     if entry == "saveat":
-        return saveat(cloudy, plan, u0, t_span, S.save_times(t_span), **kw)
-    times = S.save_times(t_span) if SAVES[entry] else ()
+        return saveat(cloudy, plan, u0, t_span, save_times(t_span), **kw)
+    times = save_times(t_span) if SAVES[entry] else ()
     return box_adaptive(cloudy, plan, u0, t_span, np.ascontiguousarray(s), B.XI_BOX, times=times, **kw)
 
 
@@ -63,11 +63,11 @@ def direct(cloudy, oracle, entry, kind, u0, s, t_span, dt_in="zeros", max_steps=
     dt_d = None if dt_in is None else dev(cloudy, (np.zeros(ld) if isinstance(dt_in, str) else np.pad(dt_in, (0, ld - n)))[None, :])
     dt_p = None if dt_d is None else dt_d.ptr
     t_d, info = dev(cloudy, sentinel_planes(1, ld)), cloudy.DeviceArray.zeros(3, ld, np.int32)
-    times = S.save_times(t_span) if SAVES[entry] else ()
+    times = save_times(t_span) if SAVES[entry] else ()
     n_save = len(times)
     snap = dev(cloudy, sentinel_planes(max(n_save, 1) * planes, ld))
     arr = (C.c_double * max(n_save, 1))(*times)
-    opts = H.default_opts(cloudy, max_steps=max_steps)
+    opts = default_opts(cloudy, max_steps=max_steps)
     if entry == "adaptive":
         rc = L.cloudy_tsit5_adaptive(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), dt_p, t_d.ptr, info.ptr, None)
     elif entry == "saveat":
@@ -250,7 +250,7 @@ def test_budget(gpu_cloudy, oracle, entry, kind):
     assert dt_rel[same].max() <= 1e-5, dt_rel[same].max()
     assert rel[:, same].max() <= R.TOL_EVAL[family], rel[:, same].max()
     if SAVES[entry]:
-        beyond = S.save_times(t_span)[:, None] > got["t"][None, :]
+        beyond = save_times(t_span)[:, None] > got["t"][None, :]
         assert beyond[:, slow].any() and (~beyond[:, slow]).any() and not beyond[:, ~slow].any()
         nan, fin = np.isnan(got["saved"]), np.isfinite(got["saved"])
         assert np.all(nan.all(axis=1) == beyond) and np.all(fin.all(axis=1) == ~beyond)

@@ -13,6 +13,7 @@ import pytest
 import bench
 import test_tsit5_adaptive_host as H
 from test_gpu_parity import INF, _tsit5_host, dev, make_case
+from tsit5_restated import default_opts
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +55,7 @@ def adaptive(cloudy, plan, u0, t_span, reltol=1e-6, abstol=1e-9, dt=0.0, max_ste
     dt_d = None if dt_in is None else dev(cloudy, (np.zeros(ld) if isinstance(dt_in, str) else np.pad(dt_in, (0, ld - n)))[None, :])
     t_d = dev(cloudy, sentinel_planes(1, ld))
     info = cloudy.DeviceArray.zeros(3, ld, np.int32)
-    opts = H.default_opts(cloudy, reltol=reltol, abstol=abstol, dt_init=dt, max_steps=max_steps)
+    opts = default_opts(cloudy, reltol=reltol, abstol=abstol, dt_init=dt, max_steps=max_steps)
     rc = L.cloudy_tsit5_adaptive(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), None if dt_d is None else dt_d.ptr,
                                  t_d.ptr, info.ptr, None)
     assert rc == expect, (rc, L.cloudy_last_error().decode())

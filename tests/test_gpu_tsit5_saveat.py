@@ -5,7 +5,7 @@ move a bit of the integration.
 
 Run with `-m gpu`.  Batches, plans and t_span are those of tests/test_gpu_tsit5_adaptive.py (1, 65 and 257 parcels in buffers of
 leading dimension n + 15; thresholded plans at 65 parcels: their oracle is slow); the save times are the twelve of
-test_tsit5_saveat_host.SAVE_FRACS."""
+tsit5_restated.SAVE_FRACS."""
 import ctypes as C
 import functools
 
@@ -16,6 +16,7 @@ import test_tsit5_adaptive_host as H
 import test_tsit5_saveat_host as S
 from test_gpu_parity import dev
 from test_gpu_tsit5_adaptive import SENTINEL, SIZES, adaptive, golovin_plan, same_counts, sentinel_planes, two_gamma_plan
+from tsit5_restated import SAVE_FRACS, default_opts, save_times
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +44,7 @@ def saveat(cloudy, plan, u0, t_span, times, reltol=1e-6, abstol=1e-9, max_steps=
     n_save = len(times)
     snap = dev(cloudy, blank(max(n_save, 1) * planes))
     arr = (C.c_double * max(n_save, 1))(*times)
-    opts = H.default_opts(cloudy, reltol=reltol, abstol=abstol, max_steps=max_steps)
+    opts = default_opts(cloudy, reltol=reltol, abstol=abstol, max_steps=max_steps)
     rc = L.cloudy_tsit5_adaptive_saveat(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), dt_d.ptr, t_d.ptr, info.ptr, None,
                                         n_save, arr, snap.ptr)
     assert rc == expect, (rc, L.cloudy_last_error().decode())
@@ -78,7 +79,7 @@ def device_runs(cloudy, oracle, kind, n):
     _, _, plan = two_gamma_plan(cloudy, oracle, kind)
     u0 = H.two_gamma_batch(n, kind=kind)
     t_span = H.TWO_GAMMA_T[kind]
-    return u0, adaptive(cloudy, plan, u0, t_span, ld=n + 15), saveat(cloudy, plan, u0, t_span, S.save_times(t_span), ld=n + 15)
+    return u0, adaptive(cloudy, plan, u0, t_span, ld=n + 15), saveat(cloudy, plan, u0, t_span, save_times(t_span), ld=n + 15)
 
 
 # ---- 1. closed form
@@ -116,7 +117,7 @@ def test_saving_does_not_disturb_the_integration(gpu_cloudy, oracle, kind, n):
     for k in KEYS:
         assert bits_equal(got[k], base[k]), k
     none = saveat(cloudy, plan, u0, t_span, (), ld=n + 15)
-    inplace = saveat(cloudy, plan, u0, t_span, S.save_times(t_span), ld=n + 15, in_place=True)
+    inplace = saveat(cloudy, plan, u0, t_span, save_times(t_span), ld=n + 15, in_place=True)
     for k in KEYS:
         assert bits_equal(none[k], base[k]), k
         assert bits_equal(inplace[k], base[k]), k
@@ -130,7 +131,7 @@ def test_end_points_padding_and_input(gpu_cloudy, oracle, kind, n):
     """The snapshot at t_span has the bits of u_out, the one at 0 those of u_in; the columns n .. ld of every snapshot plane and
     of u_out keep the sentinel; u_in is untouched out of place."""
     u0, base, got = device_runs(gpu_cloudy, oracle, kind, n)
-    assert got["saved"].shape == (len(S.SAVE_FRACS), 6, n) and np.isfinite(got["saved"]).all()
+    assert got["saved"].shape == (len(SAVE_FRACS), 6, n) and np.isfinite(got["saved"]).all()
     assert bits_equal(got["saved"][-1], got["u"])
     assert bits_equal(got["saved"][0], u0)
     assert got["saved_pad"].shape[2] == 15 and np.all(blank_bits(got["saved_pad"])) and np.all(blank_bits(got["pad"]))
@@ -141,7 +142,7 @@ def test_end_points_padding_and_input(gpu_cloudy, oracle, kind, n):
 @pytest.mark.parametrize("kind,n", CASES)
 def test_snapshot_parity_with_the_restatement(gpu_cloudy, oracle, kind, n):
     """At most 5 % of the parcels differ from the restatement in (accepted, rejected) (as decision_parity; the restatement
-    integrates as adaptive_tsit5_host does -- test_tsit5_saveat_host -- whose own sensitivity on these batches the existing tests
+    integrates as the one without does -- test_tsit5_saveat_host -- whose own sensitivity on these batches the existing tests
     bound); for the others EVERY snapshot agrees to 1e-13 x the evaluations the parcel took, of |u0| + |want| per plane: the bound
     already asserted for the final state -- the interpolant adds a few dozen FMAs with coefficients <= 48, a rounding contribution
     of order 1e-14 of |h k|."""
@@ -165,7 +166,7 @@ def test_budget_leaves_nan_beyond_the_time_reached(gpu_cloudy, oracle):
     _, _, plan = two_gamma_plan(cloudy, oracle, "allinf")
     u0 = H.two_gamma_batch(257)
     t_span = H.TWO_GAMMA_T["allinf"]
-    ts = S.save_times(t_span)
+    ts = save_times(t_span)
     got = saveat(cloudy, plan, u0, t_span, ts, max_steps=3, ld=257 + 15)
     base = adaptive(cloudy, plan, u0, t_span, max_steps=3, ld=257 + 15)
     for k in KEYS:
@@ -189,7 +190,7 @@ def test_batch_independence_all_inf(gpu_cloudy, oracle):
     t_span = H.TWO_GAMMA_T["allinf"]
 
     def check(lo, hi):
-        part = saveat(cloudy, plan, np.ascontiguousarray(u0[:, lo:hi]), t_span, S.save_times(t_span))
+        part = saveat(cloudy, plan, np.ascontiguousarray(u0[:, lo:hi]), t_span, save_times(t_span))
         assert bits_equal(whole["saved"][:, :, lo:hi], part["saved"]), (lo, hi)
         for k in KEYS:
             assert bits_equal(whole[k][..., lo:hi], part[k]), (k, lo, hi)
@@ -211,7 +212,7 @@ def test_float_planes(gpu_cloudy, oracle, kind):
     n = 257 if kind == "allinf" else 65
     u32 = H.two_gamma_batch(n, kind=kind).astype(np.float32)
     t_span = H.TWO_GAMMA_T[kind]
-    ts = S.save_times(t_span)
+    ts = save_times(t_span)
     want = saveat(cloudy, plan64, u32.astype(np.float64), t_span, ts, ld=n + 15)
     got = saveat(cloudy, plan32, u32, t_span, ts, ld=n + 15)
     assert got["saved"].dtype == np.float32 and np.all(got["status"] == 0)
@@ -236,7 +237,7 @@ def test_refusals_name_the_alternative_and_leave_every_output_alone(gpu_cloudy, 
     _, _, aot = two_gamma_plan(cloudy, oracle, "allinf", specialize=-1)    # no plan-time compilation
     numerical = cloudy.numerical_plan([1, 1], cloudy.LinearKernelFunction(5e-3), bench.NORMS, 10, quad_mode=cloudy.QUAD_FIXED)
     for what, plan, batch in (("CLOUDY_F32_FAST", fast, u0.astype(np.float32)), ("specialize = -1", aot, u0), ("numerical", numerical, u0)):
-        got = saveat(cloudy, plan, batch, 1e-3, S.save_times(1e-3), expect=E.EUNSUPPORTED)
+        got = saveat(cloudy, plan, batch, 1e-3, save_times(1e-3), expect=E.EUNSUPPORTED)
         msg = L.cloudy_last_error().decode()
         assert "cloudy_tsit5_steps" in msg, (what, msg)
         assert np.all(blank_bits(got["saved_bits"])), what
@@ -249,7 +250,7 @@ def test_python_wrapper_returns_the_bits_of_the_c_call(gpu_cloudy, oracle):
     cloudy = gpu_cloudy
     par, _, plan = golovin_plan(cloudy, oracle, "gamma")
     u0 = H.golovin_batch("gamma", 257)
-    ts = S.save_times(H.GOLOVIN_T)
+    ts = save_times(H.GOLOVIN_T)
     want = saveat(cloudy, plan, u0, H.GOLOVIN_T, ts)
     u = dev(cloudy, u0)
     saved, acc, rej, status, t = cloudy.solve_tsit5_adaptive_saveat(par, u, H.GOLOVIN_T, ts, info=True)

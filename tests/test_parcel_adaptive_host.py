@@ -1,7 +1,7 @@
 """CPU-only checks of cloudy_parcel_tsit5_adaptive (csrc/adaptive_thermo.hpp): per-parcel adaptive Tsit5 of the adiabatic parcel
 Y = (S, p, T, q_v, mom...).  The error norm treats the four thermodynamic components as planes of norm 1, so the NumPy
-restatements of the controller (test_tsit5_adaptive_host.adaptive_tsit5_host, with snapshots
-test_tsit5_saveat_host.saveat_tsit5_host) describe the device loop with plane_norms = (1, 1, 1, 1, norms...), normalised = True, on
+restatement of the controller (tsit5_restated.adaptive_tsit5, with snapshots: its t_save) describes the device loop with
+plane_norms = (1, 1, 1, 1, norms...), normalised = True, on
 the restated right-hand side of test_parcel_host (parcel_rhs_numpy); no second restatement of the controller is written.  Here: the
 ABI, every argument check of the C entry point, the plan-time unit compiling for gfx950 without a device, the restatement on the
 batches the GPU tests use (attempt ranges, sensitivity of its decisions to the last bit of the right-hand side, error against a
@@ -19,9 +19,9 @@ import pytest
 
 import bench
 import test_parcel_host as P
-import test_tsit5_adaptive_host as H
-import test_tsit5_saveat_host as S
-from test_host_abi import INF, ROOT, _c_prototypes, _julia_ccalls
+from test_host_abi import INF, ROOT, _c_prototypes
+from tsit5_restated import (DONE, adaptive_tsit5, assert_adaptive_opts_refusals, assert_symbol_agrees, default_opts, last_bit_noise, plane_norms,
+                            save_times)
 
 NAME = "cloudy_parcel_tsit5_adaptive"
 NORMS = (1e8, 1e-12)
@@ -85,13 +85,13 @@ def decade_run(n, reltol, max_steps=10000, perturb=None, times=None, dt=None, t_
     y0 = base if y0 is None else y0
     opts = dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, plane_norms=decade_norms(plan), dt=dt)
     rhs = decade_rhs(w, perturb)
-    return y0, w, (H.adaptive_tsit5_host(rhs, y0, t_span, opts) if times is None else S.saveat_tsit5_host(rhs, y0, t_span, times, opts))
+    return y0, w, adaptive_tsit5(rhs, y0, t_span, opts, t_save=times)
 
 
 @functools.lru_cache(maxsize=None)
 def decade_case(n, reltol, max_steps=10000, saveat=False, plan=False):
     """the unperturbed restatement on the decade batch, once per session and shared (treat the arrays as read-only)"""
-    return decade_run(n, reltol, max_steps, times=S.save_times(T_SPAN) if saveat else None, plan=plan)
+    return decade_run(n, reltol, max_steps, times=save_times(T_SPAN) if saveat else None, plan=plan)
 
 
 @functools.lru_cache(maxsize=None)
@@ -123,13 +123,13 @@ def two_gamma_params(oracle):
 
 
 def two_gamma_norms():
-    return np.concatenate([np.ones(4), H.plane_norms((3, 3), NORMS)])
+    return np.concatenate([np.ones(4), plane_norms((3, 3), NORMS)])
 
 
 def two_gamma_run(oracle, n, coal=True, reltol=1e-6, perturb=None):
     y0, w = two_gamma_batch(n)
     rhs = oracle_rhs(oracle, two_gamma_params(oracle), w, [1, 4], coal, perturb)
-    return y0, w, H.adaptive_tsit5_host(rhs, y0, COAL_T, dict(reltol=reltol, abstol=1e-9, max_steps=10000, plane_norms=two_gamma_norms()))
+    return y0, w, adaptive_tsit5(rhs, y0, COAL_T, dict(reltol=reltol, abstol=1e-9, max_steps=10000, plane_norms=two_gamma_norms()))
 
 
 @functools.lru_cache(maxsize=None)
@@ -160,13 +160,9 @@ def test_symbol_in_header_ctypes_table_julia_shim_and_python(cloudy):
     protos = _c_prototypes()
     plain, steps = protos["cloudy_tsit5_adaptive_saveat"][1], protos["cloudy_parcel_ssprk33_steps"][1]
     # (plan, n, ld, in, out) + (sources, w_dev, w, params) + (t_span, opts, dt_dev, t_dev, info_dev, stream, n_save, t_save, save)
-    assert protos[NAME] == ("int", plain[:5] + steps[5:9] + plain[5:])
     assert len(protos[NAME][1]) == 18
-    res, argtypes = cloudy._lib.SYMBOLS[NAME]
-    assert res is C.c_int and len(argtypes) == 18 and hasattr(cloudy.lib(), NAME)
+    assert_symbol_agrees(cloudy, NAME, plain[:5] + steps[5:9] + plain[5:])
     src = open(os.path.join(ROOT, "julia", "CloudyHIP.jl")).read()
-    mine = [c for c in _julia_ccalls(src) if c[0] == NAME]
-    assert len(mine) == 1 and mine[0][1] == "Cint" and len(mine[0][2]) == 18
     assert re.search(r"function solve_parcel_tsit5_adaptive!\(y, plan::Plan, w, t_span; params::ParcelParams = ParcelParams\(\), "
                      r"coal::Bool = false", src)
     assert "solve_parcel_tsit5_adaptive" in cloudy.__all__
@@ -191,7 +187,7 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
 
     def call(times=(0.0, 0.25, 1.0), t_save="times", y_save=dummy, n=4, ld=4, t_span=1.0, y_in=dummy, y_out=dummy, sources=COND, w=10.0,
              params=ok, opts="default", **kw):
-        o = H.default_opts(cloudy, **kw) if opts == "default" else opts
+        o = default_opts(cloudy, **kw) if opts == "default" else opts
         arr = (C.c_double * max(len(times), 1))(*times)
         return L.cloudy_parcel_tsit5_adaptive(None, n, ld, y_in, y_out, sources, None, w, None if params is None else C.byref(params),
                                               t_span, None if o is None else C.byref(o), None, None, None, None, len(times),
@@ -213,23 +209,8 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
     cap = int(re.search(r"#define CLOUDY_MAX_SAVE_TIMES (\d+)", open(os.path.join(ROOT, "include", "cloudy_hip.h")).read()).group(1))
     assert call(times=tuple(np.linspace(0.0, 1.0, cap + 1))) == E.EINVAL and "n_save" in msg()
     # then those of cloudy_tsit5_adaptive
-    assert call(opts=None, params=None) == E.EINVAL and msg() == "opts is NULL"
-    short = H.default_opts(cloudy)
-    short.struct_size -= 8
-    assert call(opts=short, params=None) == E.EINVAL and "opts.struct_size" in msg()
-    for bad in (0.0, -1e-6, nan, inf):
-        assert call(reltol=bad, sources=0) == E.EINVAL and "reltol" in msg(), bad
-    for bad in (-1e-9, nan, inf):
-        assert call(abstol=bad, params=None) == E.EINVAL and "abstol" in msg(), bad
-    for bad in (-1.0, nan, inf):
-        assert call(dt_init=bad, params=None) == E.EINVAL and "dt_init" in msg(), bad
-    for bad in (-1.0, nan, inf):
-        assert call(times=(), t_save=None, y_save=None, t_span=bad, params=None) == E.EINVAL and "t_span" in msg(), bad
-    for bad in (0, -1, 1000001):
-        assert call(max_steps=bad, params=None) == E.EINVAL and "max_steps" in msg(), bad
-    assert call(n=4, ld=3, params=None) == E.EINVAL and "ld (3) must be >= n_parcels (4)" in msg()
-    assert call(y_in=None, sources=COAL) == E.EINVAL and msg() == "device buffer is NULL"
-    assert call(y_out=None, params=None) == E.EINVAL and msg() == "device buffer is NULL"
+    assert_adaptive_opts_refusals(cloudy, call, msg, buffers=("y_in", "y_out"), no_times=dict(times=(), t_save=None, y_save=None),
+                                  later=(dict(params=None), dict(sources=0), dict(sources=COAL)))
     # then the parcel's: params, a constant, sources
     assert call(params=None, sources=COAL) == E.EINVAL and msg() == "params is NULL"
     short_p = cloudy.ParcelParams().to_c()
@@ -297,7 +278,7 @@ def test_restatement_on_the_decade_batch(n, reltol, lo, hi):
     -- so no implementation of this controller meets 1e-4 there; the figure is printed, and the GPU tests bound the device per parcel
     by the restatement's own error.  (n = 257 at 1e-9: 7.8e-10 in M1, asserted.)"""
     y0, _, base = decade_case(n, reltol)
-    _, _, pert = decade_run(n, reltol, perturb=H.last_bit_noise(1))
+    _, _, pert = decade_run(n, reltol, perturb=last_bit_noise(1))
     attempts = base["accepted"] + base["rejected"]
     diff = (base["accepted"] != pert["accepted"]) | (base["rejected"] != pert["rejected"])
     moved = float((rel_to(pert["u"], base["u"], y0) / base["evals"])[:, ~diff].max())
@@ -305,7 +286,7 @@ def test_restatement_on_the_decade_batch(n, reltol, lo, hi):
     print(f"n={n} reltol={reltol:g}: attempts {attempts.min()} .. {attempts.max()}, rejected at most {base['rejected'].max()}; "
           f"{int(diff.sum())} parcels change (accepted, rejected) under last-bit noise, the others move by {moved:.1e} x evaluations; "
           f"error against reltol = 1e-11 per plane {err}")
-    assert np.all(base["status"] == H.DONE) and np.all(pert["status"] == H.DONE) and np.all(base["t"] == T_SPAN)
+    assert np.all(base["status"] == DONE) and np.all(pert["status"] == DONE) and np.all(base["t"] == T_SPAN)
     assert (attempts.min(), attempts.max()) == (lo, hi)
     if (n, reltol) == (257, 1e-6):
         assert base["rejected"].max() == 5
@@ -325,7 +306,7 @@ def test_decisions_are_insensitive_to_the_last_bit_of_the_coalcond_rhs(oracle):
     |y0| + |y| (S by 7e-4, q_v by 3e-4)."""
     n = 257
     y0, _, base = two_gamma_case(n)
-    _, _, pert = two_gamma_run(oracle, n, perturb=H.last_bit_noise(1))
+    _, _, pert = two_gamma_run(oracle, n, perturb=last_bit_noise(1))
     _, _, cond_only = two_gamma_run(oracle, n, coal=False)
     attempts = base["accepted"] + base["rejected"]
     diff = (base["accepted"] != pert["accepted"]) | (base["rejected"] != pert["rejected"])
@@ -333,7 +314,7 @@ def test_decisions_are_insensitive_to_the_last_bit_of_the_coalcond_rhs(oracle):
     coal_moves = rel_to(cond_only["u"], base["u"], y0).max(axis=1)
     print(f"COAL | COND n={n}: attempts {attempts.min()} .. {attempts.max()}; {int(diff.sum())} parcels change (accepted, rejected); the "
           f"others move by {moved:.1e} x evaluations; coalescence moves the planes by {coal_moves}")
-    assert np.all(base["status"] == H.DONE) and np.all(pert["status"] == H.DONE)
+    assert np.all(base["status"] == DONE) and np.all(pert["status"] == DONE)
     assert attempts.max() >= 5
     assert diff.sum() <= 0.05 * n, diff.sum()
     assert moved < TOL_EVAL, moved
@@ -346,8 +327,8 @@ def test_rogers_1975_through_dense_output():
     points and mean radius within 0.05 um of Rogers's points, the bounds of test_restatement_against_rogers_1975."""
     y0, ts = rogers_states()
     rhs = lambda Y: P.parcel_rhs_numpy(P.DEFAULTS, Y, 10.0, [1], monodisperse_cond_closed(P.DEFAULTS))  # noqa: E731
-    res = S.saveat_tsit5_host(rhs, y0, T_SPAN, ts, dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=decade_norms()))
-    assert res["status"][0] == H.DONE and np.isfinite(res["saved"]).all()
+    res = adaptive_tsit5(rhs, y0, T_SPAN, dict(reltol=1e-6, abstol=1e-9, max_steps=10000, plane_norms=decade_norms()), t_save=ts)
+    assert res["status"][0] == DONE and np.isfinite(res["saved"]).all()
     d_ss, d_r = rogers_from_series(ts, res["saved"][:, :, 0])
     print(f"dense output vs Rogers 1975: supersaturation {d_ss:.4f} percentage points, radius {d_r:.4f} um; "
           f"{res['accepted'][0]} accepted, {res['rejected'][0]} rejected steps")

@@ -5,7 +5,7 @@ tests/test_gpu_ranked_adaptive.py is chosen here, on the oracle alone, and every
 
   * the workgroup sizes (BLOCK) are read out of the code that generates the plan-time units, so that n = BS + 1 and n = 2 BS + 1 are a full
     workgroup + one lane and two full workgroups + one lane for the kernel that actually runs;
-  * the restatement (test_tsit5_saveat_host.saveat_tsit5_host on the unchanged oracle) answers last-bit noise of its right-hand
+  * the restatement (tsit5_restated.adaptive_tsit5 with t_save on the unchanged oracle) answers last-bit noise of its right-hand
     side at those n with at most 5 % of changed (accepted, rejected) and RESOLUTION x evaluations of movement of the others;
   * the parcels run alone (SINGLETONS), the budget (BUDGET), the hostile neighbours (hostile_batch) and the batch whose stages
     leave the domain of the right-hand side (H5).
@@ -26,7 +26,7 @@ import pytest
 
 import test_box_adaptive_host as B
 import test_tsit5_adaptive_host as H
-import test_tsit5_saveat_host as S
+from tsit5_restated import DONE, DT_MIN, MAX_STEPS, adaptive_tsit5, last_bit_noise, plane_norms, save_times
 
 KINDS = ("fixed", "moving")
 FAMILIES = ("coal", "box")   # coal: cloudy_tsit5_adaptive[_saveat]; box: cloudy_box_tsit5_adaptive with COAL | COND
@@ -105,11 +105,11 @@ def batch(family, kind, n, hostile=False):
 
 
 def restatement(oracle, family, kind, n, max_steps=10000, t_mult=1, hostile=False, dt=None, t_span=None, perturb=None, seen=None):
-    """saveat_tsit5_host (it integrates as adaptive_tsit5_host does and adds the snapshots) at the twelve save times"""
+    """adaptive_tsit5 with t_save (it integrates as without and adds the snapshots) at the twelve save times"""
     u0, s, _ = batch(family, kind, n, hostile)
     t_span = H.TWO_GAMMA_T[kind] * t_mult if t_span is None else t_span
-    opts = dict(reltol=1e-6, abstol=1e-9, max_steps=max_steps, dt=dt, plane_norms=H.plane_norms((3, 3)), normalised=False)
-    return S.saveat_tsit5_host(rhs(oracle, family, kind, s, perturb, seen), u0, t_span, S.save_times(t_span), opts)
+    opts = dict(reltol=1e-6, abstol=1e-9, max_steps=max_steps, dt=dt, plane_norms=plane_norms((3, 3)), normalised=False)
+    return adaptive_tsit5(rhs(oracle, family, kind, s, perturb, seen), u0, t_span, opts, t_save=save_times(t_span))
 
 
 @functools.lru_cache(maxsize=None)
@@ -128,7 +128,7 @@ def h5_reference(family):
 
     seen = np.zeros(H5["n"], bool)
     ref = restatement(cloudy_oracle, family, H5["kind"], H5["n"], t_span=H5["t_span"], dt=H5["dt"], seen=seen)
-    return ref, seen & (ref["status"] == H.DONE) & (ref["rejected"] >= 1)
+    return ref, seen & (ref["status"] == DONE) & (ref["rejected"] >= 1)
 
 
 @functools.lru_cache(maxsize=None)
@@ -203,12 +203,12 @@ def test_decisions_are_insensitive_to_the_last_bit_of_the_rhs_at_two_workgroups(
     n = sizes(family, kind)[1]
     u0, _, _ = batch(family, kind, n)
     base = reference(family, kind, n)
-    pert = restatement(oracle, family, kind, n, perturb=H.last_bit_noise(1))
+    pert = restatement(oracle, family, kind, n, perturb=last_bit_noise(1))
     diff, moved = changed_and_moved(u0, base, pert)
     att = base["accepted"] + base["rejected"]
     print(f"{family} {kind} n={n}: attempts {att.min()} .. {att.max()}; {int(diff.sum())} parcels change (accepted, rejected) under "
           f"last-bit noise; the others move by {moved:.1e} x evaluations")
-    assert np.all(base["status"] == H.DONE) and np.all(pert["status"] == H.DONE)
+    assert np.all(base["status"] == DONE) and np.all(pert["status"] == DONE)
     assert att.min() == 1 and att.max() >= 4 and np.any((att[:-1] == 1) & (att[1:] >= 3))
     assert diff.sum() <= 0.05 * n, diff.sum()
     assert moved <= RESOLUTION[family], moved
@@ -240,20 +240,20 @@ def test_budget_choice(oracle, family, kind):
     bs, n = BLOCK[family, kind], sizes(family, kind)[1]
     budget = BUDGET[kind]
     ref = reference(family, kind, n, **budget)
-    per = [((ref["status"][lo:lo + bs] == H.MAX_STEPS).sum(), (ref["status"][lo:lo + bs] == H.DONE).sum()) for lo in range(0, n, bs)]
-    assert np.all((ref["status"] == H.MAX_STEPS) | (ref["status"] == H.DONE))
+    per = [((ref["status"][lo:lo + bs] == MAX_STEPS).sum(), (ref["status"][lo:lo + bs] == DONE).sum()) for lo in range(0, n, bs)]
+    assert np.all((ref["status"] == MAX_STEPS) | (ref["status"] == DONE))
     assert all(stopped >= 5 and 2 * done >= bs for stopped, done in per[:-1]), per
     assert per[-1] == (0, 1)
-    slow = ref["status"] == H.MAX_STEPS
+    slow = ref["status"] == MAX_STEPS
     t_span = H.TWO_GAMMA_T[kind] * budget["t_mult"]
     assert np.all((ref["accepted"] + ref["rejected"])[slow] == budget["max_steps"])
     assert np.all(ref["t"][slow] < t_span) and np.all(ref["t"][slow] > 0) and np.all(ref["t"][~slow] == t_span)
-    beyond = S.save_times(t_span)[:, None] > ref["t"][None, :]
+    beyond = save_times(t_span)[:, None] > ref["t"][None, :]
     assert beyond[:, slow].any() and (~beyond[:, slow]).any() and not beyond[:, ~slow].any()
     assert np.array_equal(np.isnan(ref["saved"]).all(axis=1), beyond) and np.array_equal(np.isfinite(ref["saved"]).all(axis=1), ~beyond)
     moved = 0.0
     for seed in (1, 2):
-        pert = restatement(oracle, family, kind, n, perturb=H.last_bit_noise(seed), **budget)
+        pert = restatement(oracle, family, kind, n, perturb=last_bit_noise(seed), **budget)
         assert np.array_equal(pert["status"], ref["status"])
         assert np.array_equal(pert["accepted"], ref["accepted"]) and np.array_equal(pert["rejected"], ref["rejected"])
         moved = max(moved, float((np.abs(pert["t"] - ref["t"]) / ref["t"]).max()))
@@ -273,16 +273,16 @@ def test_hostile_parcels_in_the_restatement(family, kind):
     t_span = H.TWO_GAMMA_T[kind]
     assert all((role == r).sum() >= n // 6 for r in range(4)) and np.array_equal(role == -1, np.arange(n) % 4 == 0)
     bad = (role == 1) | (role == 2)
-    assert np.all(ref["status"][bad] == H.DT_MIN) and not ref["accepted"][bad].any() and not ref["rejected"][bad].any()
+    assert np.all(ref["status"][bad] == DT_MIN) and not ref["accepted"][bad].any() and not ref["rejected"][bad].any()
     assert np.all(ref["t"][bad] == 0.0) and np.isnan(ref["saved"][1:, :, bad]).all()
     zero = role == 0
-    assert np.all(ref["status"][zero] == H.DONE) and np.all(ref["accepted"][zero] == 1) and not ref["rejected"][zero].any()
+    assert np.all(ref["status"][zero] == DONE) and np.all(ref["accepted"][zero] == 1) and not ref["rejected"][zero].any()
     assert np.all(ref["t"][zero] == t_span) and not ref["u"][:, zero].any()
     kept = role == -1
     for k in ("u", "t", "dt", "accepted", "rejected", "status"):
         assert np.array_equal(ref[k][..., kept], whole[k][..., kept]), k
     dense = int(np.argmax(H.two_gamma_batch(n, kind=kind)[0]))
-    assert np.all(ref["status"][role == 3] == H.DONE)
+    assert np.all(ref["status"][role == 3] == DONE)
     if family == "coal":   # (the box's copies keep the supersaturation of their own column)
         assert np.all(ref["u"][:, role == 3] == whole["u"][:, [dense]])
 
@@ -294,13 +294,13 @@ def test_nonfinite_estimate_is_rejected_and_recovered_from(oracle, family):
     x evaluations), so that the GPU test may hold the device to the same bounds."""
     ref, took = h5_reference(family)
     u0, _, _ = batch(family, H5["kind"], H5["n"])
-    pert = restatement(oracle, family, H5["kind"], H5["n"], t_span=H5["t_span"], dt=H5["dt"], perturb=H.last_bit_noise(1))
+    pert = restatement(oracle, family, H5["kind"], H5["n"], t_span=H5["t_span"], dt=H5["dt"], perturb=last_bit_noise(1))
     diff, moved = changed_and_moved(u0, ref, pert)
     att = ref["accepted"] + ref["rejected"]
     print(f"{family}: parcels {np.flatnonzero(took)} take the h / 5 rejection (rejected {ref['rejected'][took]}, attempts {att[took]}); "
           f"{int(diff.sum())} parcels change under last-bit noise, the others move by {moved:.1e} x evaluations")
     assert took.sum() >= 1 and np.isfinite(u0).all()
-    assert np.all(ref["status"] == H.DONE) and np.all(ref["t"] == H5["t_span"]) and np.isfinite(ref["u"]).all()
+    assert np.all(ref["status"] == DONE) and np.all(ref["t"] == H5["t_span"]) and np.isfinite(ref["u"]).all()
     assert diff.sum() <= 0.05 * H5["n"], diff.sum()
     assert moved <= RESOLUTION[family], moved
     idx, fine = h5_fine(family)
@@ -317,7 +317,7 @@ def test_status_2_after_an_attempt_is_not_reached_by_a_physical_input(oracle):
     s = np.full(65, -0.02)
     op, _, _, _ = H.two_gamma_case(oracle, "fixed")
     f = lambda u: oracle.rhs_coal_batch(op, u) + oracle.rhs_condensation_batch(op, 1e-4, s, u)  # noqa: E731
-    res = H.adaptive_tsit5_host(f, H.two_gamma_batch(65, kind="fixed"), 30.0,
-                                dict(reltol=1e-6, abstol=1e-9, max_steps=300, plane_norms=H.plane_norms((3, 3)), normalised=False))
+    res = adaptive_tsit5(f, H.two_gamma_batch(65, kind="fixed"), 30.0,
+                         dict(reltol=1e-6, abstol=1e-9, max_steps=300, plane_norms=plane_norms((3, 3)), normalised=False))
     print(f"statuses {np.bincount(res['status'], minlength=3)}")
     assert np.array_equal(np.bincount(res["status"], minlength=3), [54, 11, 0])

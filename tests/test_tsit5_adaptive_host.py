@@ -1,5 +1,5 @@
-"""CPU-only checks of the per-parcel adaptive Tsit5 (cloudy_tsit5_adaptive, csrc/adaptive.hpp): a NumPy restatement of the
-algorithm (`adaptive_tsit5_host`, its own copy of every constant, vectorised over parcels with per-parcel masks), the order
+"""CPU-only checks of the per-parcel adaptive Tsit5 (cloudy_tsit5_adaptive, csrc/adaptive.hpp): the NumPy restatement of the
+algorithm (tsit5_restated.adaptive_tsit5, its own copy of every constant, vectorised over parcels with per-parcel masks), the order
 conditions of the error weights, the restatement against the closed form of the single-mode Golovin box, the sensitivity of its
 accept / reject decisions to the last bit of the right-hand side on the batches the GPU tests use, every argument check of the C
 entry point, and the plan-time unit compiling for gfx950 without a device.
@@ -15,105 +15,14 @@ import pytest
 
 import bench
 from test_host_abi import INF, ROOT, _c_prototypes, _julia_ccalls
-
-EPS = float(np.finfo(np.float64).eps)
-
-# ---- the tableau and the controller, restated (Tsitouras 2011; the PI controller of include/cloudy_hip.h)
-C_NODES = (0.0, 0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0)
-A_ROWS = ((0.161,),
-          (-0.008480655492356989, 0.335480655492357),
-          (2.8971530571054935, -6.359448489975075, 4.3622954328695815),
-          (5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525),
-          (5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383),
-          (0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774))
-BTILDE = (-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629, 0.5823571654525552,
-          -0.45808210592918697, 0.015151515151515152)
-BETA1, BETA2, GAMMA, QMIN, QMAX, QOLD0 = 7 / 50, 2 / 25, 9 / 10, 1 / 5, 10.0, 1e-4
-DONE, MAX_STEPS, DT_MIN = 0, 1, 2
-
-
-def adaptive_tsit5_host(rhs, u0, t_span, opts):
-    """Every column of u0 (planes, n) from t = 0 to t_span.  rhs(u) -> du/dt on the whole batch, in the units of u0 (physical).
-    opts: reltol, abstol, max_steps; dt (None / 0: automatic, a float, or one value per parcel); plane_norms (planes,): the plan's
-    mom_norms; normalised (bool): the state the controller sees is u / plane_norms (all-Inf plans) or u itself with abstol scaled
-    by plane_norms (thresholded plans).  Returns dict(u, t, dt, accepted, rejected, status, evals)."""
-    reltol, abstol, max_steps = float(opts["reltol"]), float(opts["abstol"]), int(opts["max_steps"])
-    norms = np.asarray(opts["plane_norms"], dtype=np.float64)[:, None]
-    normalised = bool(opts.get("normalised", True))
-    n = u0.shape[1]
-    if normalised:
-        u = u0 / norms
-        f = lambda v: rhs(v * norms) / norms  # noqa: E731
-        atol = np.full_like(u, abstol)
-    else:
-        u = u0.copy()
-        f = rhs
-        atol = abstol * norms * np.ones_like(u)
-    count = u.shape[0]
-    t = np.zeros(n)
-    accepted, rejected, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64)
-    evals = np.zeros(n, np.int64)
-    if not t_span > 0:
-        return dict(u=u0.copy(), t=t, dt=np.zeros(n), accepted=accepted, rejected=rejected, status=status, evals=evals)
-    with np.errstate(all="ignore"):
-        k1 = f(u)
-        evals += 1
-        dt0 = opts.get("dt")
-        dt = np.zeros(n) if dt0 is None else np.broadcast_to(np.asarray(dt0, dtype=np.float64), (n,)).copy()
-        auto = ~((dt > 0) & np.isfinite(dt))
-        sc = atol + reltol * np.abs(u)
-        d0, d1 = np.sqrt(((u / sc) ** 2).sum(axis=0) / count), np.sqrt(((k1 / sc) ** 2).sum(axis=0) / count)
-        dt = np.where(auto, np.where(d1 == 0, t_span, 0.01 * d0 / d1), dt)
-        dt = np.where(dt > t_span, t_span, dt)
-        qold = np.full(n, QOLD0)
-        active = np.ones(n, bool)
-        t_last, dt_min = t_span * (1 - 4 * EPS), 1e-14 * t_span
-        while True:
-            over = active & (accepted + rejected >= max_steps)
-            status[over], active[over] = MAX_STEPS, False
-            small = active & (~(dt >= dt_min) | ~np.isfinite(dt))
-            status[small], active[small] = DT_MIN, False
-            if not active.any():
-                break
-            last = t + dt >= t_last
-            h = np.where(last, t_span - t, dt)
-            k = [k1]
-            for row in A_ROWS[:-1]:
-                k.append(f(u + h * sum(a * ki for a, ki in zip(row, k))))
-            u_new = u + h * sum(a * ki for a, ki in zip(A_ROWS[-1], k))
-            k.append(f(u_new))
-            evals[active] += 6
-            err = h * sum(b * ki for b, ki in zip(BTILDE, k))
-            sc = atol + reltol * np.maximum(np.abs(u), np.abs(u_new))
-            eest = np.sqrt(((err / sc) ** 2).sum(axis=0) / count)
-            fin = np.isfinite(eest)
-            q11 = np.where(eest > 0, np.where(fin, eest, 1.0) ** BETA1, 0.0)
-            q = np.clip(q11 / qold ** BETA2 / GAMMA, 1 / QMAX, 1 / QMIN)
-            acc = active & fin & (eest <= 1)
-            rej = active & ~acc
-            dt_acc = np.maximum(h / q, np.minimum(dt, dt / q))
-            dt_rej = np.where(fin, h / np.minimum(1 / QMIN, q11 / GAMMA), h / 5.0)
-            t = np.where(acc, np.where(last, t_span, t + h), t)
-            dt = np.where(acc, dt_acc, np.where(rej, dt_rej, dt))
-            qold = np.where(acc, np.maximum(eest, QOLD0), qold)
-            u = np.where(acc, u_new, u)
-            k1 = np.where(acc, k[6], k1)
-            accepted += acc
-            rejected += rej
-            active &= ~(acc & last)
-    return dict(u=u * norms if normalised else u, t=t, dt=dt, accepted=accepted, rejected=rejected, status=status, evals=evals)
-
+from tsit5_restated import (A_ROWS, BTILDE, C_NODES, DONE, EPS, adaptive_tsit5, assert_adaptive_opts_refusals, default_opts, last_bit_noise,
+                            plane_norms)
 
 # ---- the batches (shared with the GPU tests): picked on the oracle alone
 GOLOVIN_B = 5.0
 GOLOVIN_KC = [[0.0, GOLOVIN_B], [GOLOVIN_B, 0.0]]
 GOLOVIN_T = 0.6     # b M1 t_span between 3e-3 and 3 over the batch
 TOLS = (1e-6, 1e-9)
-
-
-def plane_norms(nprog, norms=bench.NORMS):
-    """mom_norms of a plan (helper_functions.jl:40-53): n0 m0^order per plane"""
-    return np.array([norms[0] * norms[1] ** k for np_ in nprog for k in range(np_)])
 
 
 def golovin_batch(dist, n, seed=3):
@@ -148,8 +57,8 @@ def golovin_case(oracle, dist, n, reltol, seed=3):
     types, nprog = ([oracle.GAMMA], (3,)) if dist == "gamma" else ([oracle.EXPONENTIAL], (2,))
     op = oracle.make_params(types, np.array(GOLOVIN_KC), (INF,), norms=bench.NORMS)
     u0 = golovin_batch(dist, n, seed)
-    res = adaptive_tsit5_host(lambda u: oracle.rhs_coal_batch(op, u), u0, GOLOVIN_T,
-                              dict(reltol=reltol, abstol=1e-9, max_steps=10000, plane_norms=plane_norms(nprog)))
+    res = adaptive_tsit5(lambda u: oracle.rhs_coal_batch(op, u), u0, GOLOVIN_T,
+                         dict(reltol=reltol, abstol=1e-9, max_steps=10000, plane_norms=plane_norms(nprog)))
     exact = golovin_exact(u0, GOLOVIN_T)
     return u0, exact, res, plane_errors(res["u"], exact, u0)
 
@@ -192,8 +101,8 @@ def two_gamma_reference(oracle, kind, n, reltol=1e-6, max_steps=10000, dt=None, 
     u0 = two_gamma_batch(n, seed, kind)
     t_span = TWO_GAMMA_T[kind] if t_span is None else t_span
     rhs = (lambda u: oracle.rhs_coal_batch(op, u)) if perturb is None else (lambda u: oracle.rhs_coal_batch(op, u) * perturb(u.shape))
-    res = adaptive_tsit5_host(rhs, u0, t_span, dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, dt=dt,
-                                                    plane_norms=plane_norms((3, 3)), normalised=kind == "allinf"))
+    res = adaptive_tsit5(rhs, u0, t_span, dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, dt=dt,
+                                               plane_norms=plane_norms((3, 3)), normalised=kind == "allinf"))
     return u0, res
 
 
@@ -203,11 +112,6 @@ def two_gamma_reference_cached(kind, n, max_steps=10000):
     from oracle import cloudy_oracle
 
     return two_gamma_reference(cloudy_oracle, kind, n, max_steps=max_steps)
-
-
-def last_bit_noise(seed):
-    rng = np.random.default_rng(seed)
-    return lambda shape: 1.0 + 1e-15 * rng.choice([-1.0, 1.0], size=shape)
 
 
 # ---- 1. order conditions
@@ -263,9 +167,9 @@ def test_decisions_are_insensitive_to_the_last_bit_of_the_rhs(oracle, case, n, r
         op = oracle.make_params(types, np.array(GOLOVIN_KC), (INF,), norms=bench.NORMS)
         u0 = golovin_batch(dist, n)
         o = dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, plane_norms=plane_norms(nprog))
-        base = adaptive_tsit5_host(lambda u: oracle.rhs_coal_batch(op, u), u0, GOLOVIN_T, o)
+        base = adaptive_tsit5(lambda u: oracle.rhs_coal_batch(op, u), u0, GOLOVIN_T, o)
         noise = last_bit_noise(1)
-        pert = adaptive_tsit5_host(lambda u: oracle.rhs_coal_batch(op, u) * noise(u.shape), u0, GOLOVIN_T, o)
+        pert = adaptive_tsit5(lambda u: oracle.rhs_coal_batch(op, u) * noise(u.shape), u0, GOLOVIN_T, o)
     else:
         _, base = two_gamma_reference_cached(case, n, max_steps)
         _, pert = two_gamma_reference(oracle, case, n, max_steps=max_steps, perturb=last_bit_noise(1))
@@ -303,14 +207,6 @@ def test_symbols_in_header_ctypes_table_julia_shim_and_python(cloudy):
     assert sig["info"].default is False and sig["out"].default is None and sig["dt_dev"].default is None
 
 
-def default_opts(cloudy, **kw):
-    o = cloudy._lib.AdaptiveOptsC()
-    cloudy.lib().cloudy_adaptive_opts_init(C.byref(o))
-    for k, v in kw.items():
-        setattr(o, k, v)
-    return o
-
-
 def test_opts_defaults(cloudy):
     o = default_opts(cloudy)
     assert o.struct_size == C.sizeof(cloudy._lib.AdaptiveOptsC) == 40
@@ -320,7 +216,6 @@ def test_opts_defaults(cloudy):
 
 def test_argument_checks_answer_einval_with_a_message(cloudy):
     L, E = cloudy.lib(), cloudy._lib
-    nan, inf = float("nan"), float("inf")
     dummy = C.c_void_p(64)   # never dereferenced: every check below precedes any device work
 
     def call(opts="default", n=4, ld=4, t_span=1.0, u_in=dummy, u_out=dummy, **kw):
@@ -332,27 +227,7 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
 
     assert call() == E.EINVAL and msg() == "plan is NULL"          # everything else is in order
     assert call(n=0, ld=0, u_in=None, u_out=None) == E.EINVAL and msg() == "plan is NULL"
-    assert call(opts=None) == E.EINVAL and msg() == "opts is NULL"
-    short = default_opts(cloudy)
-    short.struct_size -= 8
-    assert call(opts=short) == E.EINVAL and "struct_size" in msg()
-    for bad in (0.0, -1e-6, nan, inf):
-        assert call(reltol=bad) == E.EINVAL and "reltol" in msg(), bad
-    for bad in (-1e-9, nan, inf):
-        assert call(abstol=bad) == E.EINVAL and "abstol" in msg(), bad
-    assert call(abstol=0.0) == E.EINVAL and msg() == "plan is NULL"
-    for bad in (-1.0, nan, inf):
-        assert call(dt_init=bad) == E.EINVAL and "dt_init" in msg(), bad
-    for bad in (-1.0, nan, inf, -inf):
-        assert call(t_span=bad) == E.EINVAL and "t_span" in msg(), bad
-    assert call(t_span=0.0) == E.EINVAL and msg() == "plan is NULL"
-    for bad in (0, -1, 1000001):
-        assert call(max_steps=bad) == E.EINVAL and "max_steps" in msg(), bad
-    for good in (1, 1000000):
-        assert call(max_steps=good) == E.EINVAL and msg() == "plan is NULL"
-    assert call(n=4, ld=3) == E.EINVAL and "ld (3) must be >= n_parcels (4)" in msg()
-    assert call(u_in=None) == E.EINVAL and msg() == "device buffer is NULL"
-    assert call(u_out=None) == E.EINVAL and msg() == "device buffer is NULL"
+    assert_adaptive_opts_refusals(cloudy, call, msg)
 
 
 # ---- 5. the plan-time unit

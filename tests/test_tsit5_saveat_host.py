@@ -1,6 +1,6 @@
 """CPU-only checks of the dense output of the per-parcel adaptive Tsit5 (cloudy_tsit5_adaptive_saveat, csrc/adaptive.hpp): the
-interpolant's coefficients as the kernel holds them against the tableau, a NumPy restatement (`saveat_tsit5_host`: the loop of
-test_tsit5_adaptive_host.adaptive_tsit5_host plus the snapshot rule) that leaves the integration bit for bit alone, the
+interpolant's coefficients as the kernel holds them against the tableau, the NumPy restatement with snapshots
+(tsit5_restated.adaptive_tsit5 with t_save: the same loop plus the snapshot rule) that leaves the integration bit for bit alone, the
 restatement against the closed form of the single-mode Golovin box AT THE SAVE TIMES, the ABI, every argument check of the C
 entry point, and the plan-time unit with both kernels compiling for gfx950 without a device.
 
@@ -17,137 +17,8 @@ import pytest
 import bench
 import test_tsit5_adaptive_host as H
 from test_host_abi import INF, ROOT, _c_prototypes, _julia_ccalls
-from test_tsit5_adaptive_host import A_ROWS, C_NODES
-
-# ---- the interpolant, restated (Tsitouras 2011, the free 4th-order interpolant over k1 .. k7): per weight the leading factor s,
-# the roots r1, r2 and the quadratic factor th^2 - p th + q, in the forms of interp_weights
-INTERP = {1: dict(s=-1.0530884977290216, r1=1.3299890189751412, p=1.4364028541716351, q=0.7139816917074209),
-          2: dict(s=0.1017, p=2.1966568338249754, q=1.2949852507374631),
-          3: dict(s=2.490627285651252793, p=2.38535645472061657, q=1.57803468208092486),
-          4: dict(s=-16.54810288924490272, r1=1.21712927295533244, r2=0.61620406037800089),
-          5: dict(s=47.37952196281928122, r1=1.203071208372362603, r2=0.658047292653547382),
-          6: dict(s=-34.87065786149660974, r1=1.2, r2=0.666666666666666667),
-          7: dict(s=2.5, r1=1.0, r2=0.6)}
-# the twelve save times of every test, as fractions of t_span
-SAVE_FRACS = (0.0, 0.013, 0.05, 0.051, 0.2, 0.37, 0.5, 0.62, 0.8, 0.97, 0.999, 1.0)
-
-
-def interp_weights(th, coef=INTERP):
-    """b_1 .. b_7 at th (a float or an array): b1 = s th (th - r1)(th^2 - p th + q), b2, b3 = s th^2 (th^2 - p th + q),
-    b4 .. b7 = s th^2 (th - r1)(th - r2)"""
-    th = np.asarray(th, dtype=np.float64)
-    th2 = th * th
-    quad = lambda c: th * (th - c["p"]) + c["q"]  # noqa: E731
-    b = [coef[1]["s"] * th * (th - coef[1]["r1"]) * quad(coef[1]), coef[2]["s"] * th2 * quad(coef[2]), coef[3]["s"] * th2 * quad(coef[3])]
-    b += [coef[i]["s"] * th2 * ((th - coef[i]["r1"]) * (th - coef[i]["r2"])) for i in (4, 5, 6, 7)]
-    return b
-
-
-def save_times(t_span):
-    return np.array([f * t_span for f in SAVE_FRACS])
-
-
-def saveat_tsit5_host(rhs, u0, t_span, t_save, opts):
-    """adaptive_tsit5_host (same arguments, same loop, same expressions) + the snapshot rule of cloudy_tsit5_adaptive_saveat: after
-    an accepted step t -> t_new every save time t_save[j] <= t_new the parcel's cursor has not passed gets u + h sum_i b_i(th) k_i,
-    th = (t_save[j] - t) / h, or u_new itself where t_save[j] == t_new; a save time 0 gets the input; what a parcel does not reach
-    stays NaN.  Returns adaptive_tsit5_host's dict + saved (n_save, planes, n), physical units, + in_step: per parcel the number
-    of save times that fell into each accepted step (a save time 0 belongs to no step)."""
-    from test_tsit5_adaptive_host import BETA1, BETA2, BTILDE, DT_MIN, EPS, GAMMA, MAX_STEPS, QMAX, QMIN, QOLD0
-
-    reltol, abstol, max_steps = float(opts["reltol"]), float(opts["abstol"]), int(opts["max_steps"])
-    norms = np.asarray(opts["plane_norms"], dtype=np.float64)[:, None]
-    normalised = bool(opts.get("normalised", True))
-    t_save = np.asarray(t_save, dtype=np.float64)
-    n_save = t_save.size
-    planes, n = u0.shape
-    saved = np.full((n_save, planes, n), np.nan)
-    in_step = [[] for _ in range(n)]
-    if normalised:
-        u = u0 / norms
-        f = lambda v: rhs(v * norms) / norms  # noqa: E731
-        atol = np.full_like(u, abstol)
-    else:
-        u = u0.copy()
-        f = rhs
-        atol = abstol * norms * np.ones_like(u)
-    count = u.shape[0]
-    t = np.zeros(n)
-    accepted, rejected, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64)
-    evals = np.zeros(n, np.int64)
-    if not t_span > 0:
-        saved[:] = u0[None]
-        return dict(u=u0.copy(), t=t, dt=np.zeros(n), accepted=accepted, rejected=rejected, status=status, evals=evals, saved=saved,
-                    in_step=in_step)
-    cursor = np.zeros(n, np.int64)
-    if n_save and t_save[0] == 0.0:
-        saved[0] = u0
-        cursor += 1
-    with np.errstate(all="ignore"):
-        k1 = f(u)
-        evals += 1
-        dt0 = opts.get("dt")
-        dt = np.zeros(n) if dt0 is None else np.broadcast_to(np.asarray(dt0, dtype=np.float64), (n,)).copy()
-        auto = ~((dt > 0) & np.isfinite(dt))
-        sc = atol + reltol * np.abs(u)
-        d0, d1 = np.sqrt(((u / sc) ** 2).sum(axis=0) / count), np.sqrt(((k1 / sc) ** 2).sum(axis=0) / count)
-        dt = np.where(auto, np.where(d1 == 0, t_span, 0.01 * d0 / d1), dt)
-        dt = np.where(dt > t_span, t_span, dt)
-        qold = np.full(n, QOLD0)
-        active = np.ones(n, bool)
-        t_last, dt_min = t_span * (1 - 4 * EPS), 1e-14 * t_span
-        while True:
-            over = active & (accepted + rejected >= max_steps)
-            status[over], active[over] = MAX_STEPS, False
-            small = active & (~(dt >= dt_min) | ~np.isfinite(dt))
-            status[small], active[small] = DT_MIN, False
-            if not active.any():
-                break
-            last = t + dt >= t_last
-            h = np.where(last, t_span - t, dt)
-            k = [k1]
-            for row in A_ROWS[:-1]:
-                k.append(f(u + h * sum(a * ki for a, ki in zip(row, k))))
-            u_new = u + h * sum(a * ki for a, ki in zip(A_ROWS[-1], k))
-            k.append(f(u_new))
-            evals[active] += 6
-            err = h * sum(b * ki for b, ki in zip(BTILDE, k))
-            sc = atol + reltol * np.maximum(np.abs(u), np.abs(u_new))
-            eest = np.sqrt(((err / sc) ** 2).sum(axis=0) / count)
-            fin = np.isfinite(eest)
-            q11 = np.where(eest > 0, np.where(fin, eest, 1.0) ** BETA1, 0.0)
-            q = np.clip(q11 / qold ** BETA2 / GAMMA, 1 / QMAX, 1 / QMIN)
-            acc = active & fin & (eest <= 1)
-            rej = active & ~acc
-            dt_acc = np.maximum(h / q, np.minimum(dt, dt / q))
-            dt_rej = np.where(fin, h / np.minimum(1 / QMIN, q11 / GAMMA), h / 5.0)
-            t_new = np.where(last, t_span, t + h)
-            # ---- the snapshots of this step (nothing below feeds back into the integration)
-            taken = np.zeros(n, np.int64)
-            while n_save:
-                ts = t_save[np.minimum(cursor, n_save - 1)]
-                m = acc & (cursor < n_save) & (ts <= t_new)
-                if not m.any():
-                    break
-                b = interp_weights((ts - t) / h)
-                val = np.where(ts == t_new, u_new, u + h * sum(bi * ki for bi, ki in zip(b, k)))
-                val = val * norms if normalised else val
-                idx = np.flatnonzero(m)
-                saved[cursor[idx], :, idx] = val[:, idx].T
-                cursor[idx] += 1
-                taken[idx] += 1
-            for i in np.flatnonzero(acc):
-                in_step[i].append(int(taken[i]))
-            t = np.where(acc, t_new, t)
-            dt = np.where(acc, dt_acc, np.where(rej, dt_rej, dt))
-            qold = np.where(acc, np.maximum(eest, QOLD0), qold)
-            u = np.where(acc, u_new, u)
-            k1 = np.where(acc, k[6], k1)
-            accepted += acc
-            rejected += rej
-            active &= ~(acc & last)
-    return dict(u=u * norms if normalised else u, t=t, dt=dt, accepted=accepted, rejected=rejected, status=status, evals=evals,
-                saved=saved, in_step=in_step)
+from tsit5_restated import (A_ROWS, C_NODES, INTERP, SAVE_FRACS, adaptive_tsit5, assert_adaptive_opts_refusals, default_opts, interp_weights,
+                            plane_norms, save_times)
 
 
 def golovin_saveat_case(oracle, dist, n, reltol, max_steps=10000):
@@ -156,8 +27,8 @@ def golovin_saveat_case(oracle, dist, n, reltol, max_steps=10000):
     op = oracle.make_params(types, np.array(H.GOLOVIN_KC), (INF,), norms=bench.NORMS)
     u0 = H.golovin_batch(dist, n)
     ts = save_times(H.GOLOVIN_T)
-    res = saveat_tsit5_host(lambda u: oracle.rhs_coal_batch(op, u), u0, H.GOLOVIN_T, ts,
-                            dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, plane_norms=H.plane_norms(nprog)))
+    res = adaptive_tsit5(lambda u: oracle.rhs_coal_batch(op, u), u0, H.GOLOVIN_T,
+                         dict(reltol=reltol, abstol=1e-9, max_steps=max_steps, plane_norms=plane_norms(nprog)), t_save=ts)
     return u0, ts, res
 
 
@@ -175,9 +46,9 @@ def two_gamma_saveat_cached(kind, n, max_steps=10000):
     op, _, _, _ = H.two_gamma_case(oracle, kind)
     u0 = H.two_gamma_batch(n, kind=kind)
     ts = save_times(H.TWO_GAMMA_T[kind])
-    res = saveat_tsit5_host(lambda u: oracle.rhs_coal_batch(op, u), u0, H.TWO_GAMMA_T[kind], ts,
-                            dict(reltol=1e-6, abstol=1e-9, max_steps=max_steps, plane_norms=H.plane_norms((3, 3)),
-                                 normalised=kind == "allinf"))
+    res = adaptive_tsit5(lambda u: oracle.rhs_coal_batch(op, u), u0, H.TWO_GAMMA_T[kind],
+                         dict(reltol=1e-6, abstol=1e-9, max_steps=max_steps, plane_norms=plane_norms((3, 3)),
+                              normalised=kind == "allinf"), t_save=ts)
     return u0, ts, res
 
 
@@ -233,7 +104,7 @@ def test_restatement_integrates_as_the_one_without_snapshots(oracle, case):
     assert np.array_equal(res["saved"][0], u0) and np.array_equal(res["saved"][-1], res["u"])
     assert all(sum(s) == len(SAVE_FRACS) - 1 and len(s) == a for s, a in zip(res["in_step"], res["accepted"]))
     # t_span = 0 and a budget that stops parcels
-    zero = saveat_tsit5_host(None, u0, 0.0, [0.0], dict(reltol=1e-6, abstol=1e-9, max_steps=10, plane_norms=np.ones(u0.shape[0])))
+    zero = adaptive_tsit5(None, u0, 0.0, dict(reltol=1e-6, abstol=1e-9, max_steps=10, plane_norms=np.ones(u0.shape[0])), t_save=[0.0])
     assert np.array_equal(zero["saved"][0], u0)
 
 
@@ -296,10 +167,11 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
     dummy = C.c_void_p(64)   # never dereferenced: every check below precedes any device work
     cap = int(re.search(r"#define CLOUDY_MAX_SAVE_TIMES (\d+)", open(os.path.join(ROOT, "include", "cloudy_hip.h")).read()).group(1))
 
-    def call(times=(0.0, 0.25, 1.0), n_save=None, t_save="times", u_save=dummy, t_span=1.0, **kw):
-        o = H.default_opts(cloudy, **kw)
+    def call(times=(0.0, 0.25, 1.0), n_save=None, t_save="times", u_save=dummy, t_span=1.0, opts="default", ld=4, u_in=dummy, u_out=dummy,
+             **kw):
+        o = default_opts(cloudy, **kw) if opts == "default" else opts
         arr = (C.c_double * max(len(times), 1))(*times)
-        return L.cloudy_tsit5_adaptive_saveat(None, 4, 4, dummy, dummy, t_span, C.byref(o), None, None, None, None,
+        return L.cloudy_tsit5_adaptive_saveat(None, 4, ld, u_in, u_out, t_span, None if o is None else C.byref(o), None, None, None, None,
                                               len(times) if n_save is None else n_save, arr if t_save == "times" else t_save, u_save)
 
     def msg():
@@ -319,10 +191,8 @@ def test_argument_checks_answer_einval_with_a_message(cloudy):
     assert call(times=big) == E.EINVAL and "n_save" in msg() and str(cap) in msg()
     assert call(times=big[:cap]) == E.EINVAL and msg() == "plan is NULL"
     # the checks of cloudy_tsit5_adaptive follow
-    assert call(reltol=0.0) == E.EINVAL and "reltol" in msg()
     assert call(times=(0.0,), t_span=nan) == E.EINVAL    # (a save time compared with a t_span that is no number)
-    assert call(times=(), t_save=None, u_save=None, t_span=-1.0) == E.EINVAL and "t_span" in msg()
-    assert call(max_steps=0) == E.EINVAL and "max_steps" in msg()
+    assert_adaptive_opts_refusals(cloudy, call, msg, no_times=dict(times=(), t_save=None, u_save=None))
 
 
 # ---- 6. the plan-time unit
