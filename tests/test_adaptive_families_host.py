@@ -104,7 +104,7 @@ def kernel_tensor(fid):
 
 def size_classes(fid):
     """per mode the range of its mean mass: between its fixed thresholds (1.5 x the lower .. 0.7 x the upper one; two decades where
-    one is missing), else the classes of bench.synth_moments (up to four modes) and of test_gpu_parity.many_mode_moments"""
+    one is missing), else the classes of bench.synth_moments (up to four modes) and of gpu_support.many_mode_moments"""
     f = FAMILIES[fid]
     N, thr = len(f["types"]), f["thr"]
     if f["moving"] or all_inf(fid):
@@ -169,7 +169,7 @@ def reference(fid, max_steps=10000, saveat=None, warm=True):
 def fine_reference(fid):
     """every parcel by the fixed-step tableau at FINE x the accepted steps of the restatement's slowest parcel"""
     from oracle import cloudy_oracle
-    from test_gpu_parity import _tsit5_host
+    from gpu_support import _tsit5_host
 
     n_fine = FINE * int(reference(fid)["accepted"].max())
     with np.errstate(all="ignore"):

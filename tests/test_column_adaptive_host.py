@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import bench
-from test_gpu_column_sources import DZ, GOLOVIN, NCOL, NZ, VEL, XI, column_set, supersaturation
+from gpu_support import DZ, GOLOVIN, NCOL, NZ, VEL, XI, column_set, supersaturation
 from test_host_abi import INF, ROOT
 from tsit5_restated import (DONE, adaptive_tsit5, assert_adaptive_opts_refusals, assert_symbol_agrees, default_opts, last_bit_noise,
                             plane_norms)
@@ -40,7 +40,7 @@ def column_rhs_host(oracle, op, nz, dz, xi=0.0, s=None):
 
 
 # ---- the batch (shared with the GPU tests): picked on the oracle alone
-# the 20-cell, dz = 150 columns of test_gpu_column_sources.column_set, column c scaled by 10^(c / 26 - 1 / 2): amplitudes over a
+# the 20-cell, dz = 150 columns of gpu_support.column_set, column c scaled by 10^(c / 26 - 1 / 2): amplitudes over a
 # decade (times the factors the set has already), supersaturation() on.  T_SPAN: at reltol = 1e-6 the columns take 7 .. 22
 # (gamma_mixture) and 8 .. 15 (single_gamma) attempts from the automatic first step.  Under this controller these columns reject
 # nothing from there (scanned on the oracle: t_span 5 .. 400, reltol 1e-3 .. 1e-6, amplitudes down to a thirtieth: no rejection),
@@ -53,7 +53,7 @@ CASES = ("gamma_mixture", "single_gamma")
 
 
 def oracle_case(oracle, case):
-    """-> (oracle params, dist_types, thresholds, amplitudes) of the reference's two column plans (test_gpu_column_sources.reference_case)"""
+    """-> (oracle params, dist_types, thresholds, amplitudes) of the reference's two column plans (gpu_support.reference_case)"""
     if case == "gamma_mixture":
         dist_types, thr, amp = [1, 1], (2e-10, INF), np.array([1e7, 1e-3, 2e-13, 0.0, 0.0, 0.0])
     else:

@@ -18,7 +18,7 @@ import pytest
 import bench
 from test_column_adaptive_host import (CASES, DT0, FIRST, T_SPAN, column_batch, column_reference, column_reference_cached, column_rhs_host,
                                        oracle_case)
-from test_gpu_column_sources import DZ, GOLOVIN, NCOL, NZ, VEL, XI, supersaturation
+from gpu_support import DZ, GOLOVIN, NCOL, NZ, VEL, XI, supersaturation
 from test_host_abi import INF, ROOT, _c_prototypes
 from tsit5_restated import (DONE, MAX_STEPS, SAVE_FRACS, adaptive_tsit5, assert_adaptive_opts_refusals, assert_symbol_agrees, default_opts,
                             last_bit_noise, plane_norms, save_times)

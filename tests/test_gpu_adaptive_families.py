@@ -8,7 +8,6 @@ Run with `-m gpu`.  Every family, batch, t_span and first step is chosen in test
 alone, with the conditions this file relies on asserted there; ld = n + 15, out of place, sentinel-filled outputs.  The bounds are
 the project's: F.TOL_EVAL x evaluations on the parcels with the restatement's (accepted, rejected), at most 5 % of parcels without,
 2 x the restatement's error + 1e-12 against the fine run."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -18,11 +17,7 @@ import bench
 import test_adaptive_families_host as F
 import test_box_adaptive_host as B
 import test_tsit5_adaptive_host as H
-from test_gpu_box_adaptive import box_adaptive
-from test_gpu_parity import dev, make_case
-from test_gpu_tsit5_adaptive import adaptive, same_counts, sentinel_planes
-from test_gpu_tsit5_saveat import bits_equal, blank_bits
-from tsit5_restated import default_opts
+from gpu_support import adaptive, bits_equal, box_adaptive, is_blank, make_case, same_counts, saveat
 
 pytestmark = pytest.mark.gpu
 
@@ -76,33 +71,11 @@ def test_decision_parity(gpu_cloudy, oracle, fid):
     assert (~same).sum() <= 0.05 * n, (~same).sum()
     assert np.all(err <= 2 * ref_err + 1e-12), (err, ref_err)
     assert worst <= F.TOL_EVAL[F.all_inf(fid)], worst
-    assert got["pad"].shape == (u0.shape[0], 15) and np.all(blank_bits(got["pad"])) and bits_equal(got["u_in"], got["buf"])
+    assert got["pad"].shape == (u0.shape[0], 15) and np.all(is_blank(got["pad"])) and bits_equal(got["u_in"], got["buf"])
 
 
 # ---- 2. snapshots
 saveat_times = F.saveat_times
-
-
-def guarded_saveat(cloudy, plan, u0, t_span, times, max_steps=10000):
-    """cloudy_tsit5_adaptive_saveat as test_gpu_tsit5_saveat.saveat calls it (ld = n + 15, automatic first steps), with ONE MORE
-    plane of sentinels behind the n_save x planes planes of u_save -> the drivers' dict + guard (that plane)"""
-    L = cloudy.lib()
-    planes, n = u0.shape
-    ld, n_save = n + 15, len(times)
-    buf = np.full((planes, ld), 7.0)
-    buf[:, :n] = u0
-    u_in, u_out = dev(cloudy, buf), dev(cloudy, sentinel_planes(planes, ld))
-    dt_d, t_d, info = dev(cloudy, np.zeros(ld)[None, :]), dev(cloudy, sentinel_planes(1, ld)), cloudy.DeviceArray.zeros(3, ld, np.int32)
-    snap = dev(cloudy, sentinel_planes(n_save * planes + 1, ld))
-    opts = default_opts(cloudy, max_steps=max_steps)
-    rc = L.cloudy_tsit5_adaptive_saveat(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), dt_d.ptr, t_d.ptr, info.ptr, None,
-                                        n_save, (C.c_double * n_save)(*times), snap.ptr)
-    assert rc == 0, (rc, L.cloudy_last_error().decode())
-    out, counts, sv = u_out.to_numpy(), info.to_numpy(), snap.to_numpy()
-    body = sv[:-1].reshape(n_save, planes, ld)
-    return dict(u=out[:, :n], pad=out[:, n:], u_in=u_in.to_numpy(), buf=buf, t=t_d.to_numpy()[0, :n], accepted=counts[0, :n],
-                rejected=counts[1, :n], status=counts[2, :n], dt=dt_d.to_numpy()[0, :n], saved=body[:, :, :n], saved_pad=body[:, :, n:],
-                guard=sv[-1])
 
 
 @pytest.mark.parametrize("fid", SAVEAT_IDS)
@@ -116,7 +89,7 @@ def test_snapshots(gpu_cloudy, oracle, fid):
     u0, _ = F.batch(fid)
     t_span = F.FAMILIES[fid]["t_span"]
     times = saveat_times(t_span)
-    got = guarded_saveat(cloudy, plan_of(cloudy, oracle, fid), u0, t_span, times)
+    got = saveat(cloudy, plan_of(cloudy, oracle, fid), u0, t_span, times, ld=u0.shape[1] + 15)
     assert_same_bits(got, device_run(cloudy, oracle, fid, warm=False))
     ref = F.reference(fid, saveat=tuple(times), warm=False)
     assert np.all(got["status"] == 0) and np.all(ref["status"] == 0) and np.isfinite(ref["saved"]).all()
@@ -128,7 +101,7 @@ def test_snapshots(gpu_cloudy, oracle, fid):
     assert (~same).sum() <= 0.05 * same.size
     assert got["saved"].shape == (len(times), sum(F.nprog(fid)), u0.shape[1])
     assert bits_equal(got["saved"][0], u0) and bits_equal(got["saved"][-1], got["u"])
-    assert np.all(blank_bits(got["guard"])) and np.all(blank_bits(got["saved_pad"])) and np.all(blank_bits(got["pad"]))
+    assert np.all(is_blank(got["guard"])) and np.all(is_blank(got["saved_pad"])) and np.all(is_blank(got["pad"]))
     assert bits_equal(got["u_in"], got["buf"])
     assert worst[list(F.SNAPSHOTS_RESOLVED[fid])].max() <= F.TOL_EVAL[F.all_inf(fid)], worst
 
@@ -141,14 +114,14 @@ def test_snapshots_under_a_budget(gpu_cloudy, oracle, fid):
     u0, _ = F.batch(fid)
     t_span = F.FAMILIES[fid]["t_span"]
     times = saveat_times(t_span)
-    got = guarded_saveat(cloudy, plan_of(cloudy, oracle, fid), u0, t_span, times, max_steps=3)
+    got = saveat(cloudy, plan_of(cloudy, oracle, fid), u0, t_span, times, ld=u0.shape[1] + 15, max_steps=3)
     ref = F.reference(fid, max_steps=3, saveat=tuple(times), warm=False)
     slow = ref["status"] == 1
     assert slow.sum() >= 3 and np.array_equal(got["status"], ref["status"])
     beyond = times[:, None] > got["t"][None, :]
     assert beyond[:, slow].any() and not beyond[:, ~slow].any()
     assert np.all(np.isnan(got["saved"]).all(axis=1) == beyond) and np.all(np.isfinite(got["saved"]).all(axis=1) == ~beyond)
-    assert np.all(blank_bits(got["guard"])) and np.all(blank_bits(got["saved_pad"]))
+    assert np.all(is_blank(got["guard"])) and np.all(is_blank(got["saved_pad"]))
 
 
 # ---- 3. the box entry point
@@ -172,7 +145,7 @@ def test_box_decision_parity_and_xi_zero(gpu_cloudy, oracle, fid):
     print(f"box {fid} n={n}: {(~same).sum()} of {n} parcels differ in (accepted, rejected); the others agree to {worst:.2e} x evaluations")
     assert (~same).sum() <= 0.05 * n, (~same).sum()
     assert worst <= B.TOL_EVAL, worst
-    assert np.all(blank_bits(got["pad"])) and bits_equal(got["u_in"], got["buf"])
+    assert np.all(is_blank(got["pad"])) and bits_equal(got["u_in"], got["buf"])
     plain = adaptive(cloudy, plan, u0, t_span, ld=n + 15, dt_in=dt)
     assert_same_bits(plain, box_adaptive(cloudy, plan, u0, t_span, s, 0.0, sources=COAL | COND, ld=n + 15, dt_in=dt))
     assert not bits_equal(plain["u"], got["u"])
@@ -221,7 +194,7 @@ def test_zero_t_span_copies_every_plane(gpu_cloudy, oracle, fid):
     cloudy = gpu_cloudy
     u0, dt = F.batch(fid)
     zero = adaptive(cloudy, plan_of(cloudy, oracle, fid), u0, 0.0, ld=u0.shape[1] + 15, dt_in=dt)
-    assert bits_equal(zero["u"], u0) and np.all(zero["t"] == 0) and np.all(blank_bits(zero["pad"]))
+    assert bits_equal(zero["u"], u0) and np.all(zero["t"] == 0) and np.all(is_blank(zero["pad"]))
     assert not zero["accepted"].any() and not zero["rejected"].any() and not zero["status"].any()
 
 

@@ -6,7 +6,6 @@ a Monodisperse mode under condensation, the fixed-step tableau (_tsit5_host) at 
 Run with `-m gpu`.  Batch sizes 1, 65 and 257: a single parcel, a partial wave past one wave, a partial workgroup past one
 workgroup of 256 threads -- the 512-thread kernel of COAL | COND on the `fixed` plan still runs a single, partly filled workgroup at
 257 (tests/test_gpu_ranked_adaptive.py runs it at 513 and 1025)."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -15,10 +14,8 @@ import pytest
 import bench
 import test_box_adaptive_host as B
 import test_tsit5_adaptive_host as H
-from test_gpu_parity import INF, _tsit5_host, dev, make_case
-from test_gpu_tsit5_adaptive import SENTINEL, SIZES, adaptive, same_counts, sentinel_planes, two_gamma_plan
-from test_gpu_tsit5_saveat import SENTINEL32, bits_equal, blank_bits
-from tsit5_restated import adaptive_tsit5, default_opts, plane_norms, save_times
+from gpu_support import INF, SENTINEL, SIZES, _tsit5_host, adaptive, bits_equal, box_adaptive, dev, is_blank, make_case, same_counts, two_gamma_plan
+from tsit5_restated import adaptive_tsit5, plane_norms, save_times
 
 pytestmark = pytest.mark.gpu
 
@@ -30,39 +27,6 @@ COAL, COND = 1, 2
 def cond_plan(cloudy, oracle):
     par, op, _ = make_case(cloudy, oracle, [2], [[1.0]], (INF,), bench.NORMS)
     return par, op, par.coal_data.plan([2])
-
-
-def box_adaptive(cloudy, plan, u0, t_span, s, xi, sources=COAL | COND, times=(), reltol=1e-6, abstol=1e-9, max_steps=10000, ld=None,
-                 dt_in="zeros", in_place=False, expect=0):
-    """the C entry point itself on a batch u0 (planes, n) in buffers of leading dimension ld; s: a float, or an array (through
-    s_dev) -> the dict of test_gpu_tsit5_saveat.saveat"""
-    L = cloudy.lib()
-    planes, n = u0.shape
-    ld = n if ld is None else ld
-    f64 = u0.dtype == np.float64
-    blank = (lambda p: sentinel_planes(p, ld)) if f64 else (lambda p: np.full((p, ld), SENTINEL32, dtype=np.uint32).view(np.float32))
-    buf = np.full((planes, ld), 7.0, dtype=u0.dtype)
-    buf[:, :n] = u0
-    u_in = dev(cloudy, buf)
-    u_out = u_in if in_place else dev(cloudy, blank(planes))
-    s_d = None if np.ndim(s) == 0 else dev(cloudy, np.pad(np.asarray(s, dtype=np.float64), (0, ld - n))[None, :])
-    dt_d = dev(cloudy, (np.zeros(ld) if isinstance(dt_in, str) else np.pad(dt_in, (0, ld - n)))[None, :])
-    t_d = dev(cloudy, sentinel_planes(1, ld))
-    info = cloudy.DeviceArray.zeros(3, ld, np.int32)
-    n_save = len(times)
-    snap = dev(cloudy, blank(max(n_save, 1) * planes))
-    arr = (C.c_double * max(n_save, 1))(*times)
-    opts = default_opts(cloudy, reltol=reltol, abstol=abstol, max_steps=max_steps)
-    rc = L.cloudy_box_tsit5_adaptive(plan.handle, n, ld, u_in.ptr, u_out.ptr, sources, None if s_d is None else s_d.ptr,
-                                     0.0 if s_d is not None else float(s), xi, t_span, C.byref(opts), dt_d.ptr, t_d.ptr, info.ptr, None,
-                                     n_save, arr if n_save else None, snap.ptr if n_save else None)
-    assert rc == expect, (rc, L.cloudy_last_error().decode())
-    out, counts, sv = u_out.to_numpy(), info.to_numpy(), snap.to_numpy()
-    bits = sv.view(np.uint64 if f64 else np.uint32)
-    sv = sv.reshape(max(n_save, 1), planes, ld)[:n_save]
-    return dict(u=out[:, :n], pad=out[:, n:], u_in=u_in.to_numpy(), buf=buf, t=t_d.to_numpy()[0, :n], accepted=counts[0, :n],
-                rejected=counts[1, :n], status=counts[2, :n], dt=dt_d.to_numpy()[0, :n], saved=sv[:, :, :n], saved_pad=sv[:, :, n:],
-                saved_bits=bits)
 
 
 @functools.lru_cache(maxsize=None)
@@ -93,7 +57,7 @@ def test_condensation_closed_form(gpu_cloudy, oracle, reltol, n):
     assert np.all(got["status"] == 0) and np.all(got["t"] == B.COND_T)
     assert np.all(err <= 2 * ref_err + 1e-12), (err, ref_err)
     assert bits_equal(got["u"][0], u0[0])
-    assert np.all(blank_bits(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
+    assert np.all(is_blank(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
 
 
 # ---- 2. decision parity
@@ -128,7 +92,7 @@ def test_decision_parity(gpu_cloudy, oracle, kind, n):
     assert (~same).sum() <= 0.05 * n, (~same).sum()
     assert worst <= B.TOL_EVAL, worst
     assert np.all(err <= 2 * ref_err + 1e-12), (err, ref_err)
-    assert np.all(blank_bits(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
+    assert np.all(is_blank(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
 
 
 # ---- 3. sources
@@ -209,7 +173,7 @@ def test_dense_output(gpu_cloudy, oracle, case):
         assert bits_equal(got[k], base[k]), k
     assert np.all(got["status"] == 0) and np.isfinite(got["saved"]).all()
     assert bits_equal(got["saved"][0], u0) and bits_equal(got["saved"][-1], got["u"])
-    assert np.all(blank_bits(got["saved_pad"])) and np.all(blank_bits(got["pad"]))
+    assert np.all(is_blank(got["saved_pad"])) and np.all(is_blank(got["pad"]))
     same = same_counts(got, ref)
     assert (~same).sum() <= 0.05 * n, (~same).sum()
     rel = np.abs(got["saved"] - ref["saved"]) / np.maximum(np.abs(u0)[None] + np.abs(ref["saved"]), 1e-300) / ref["evals"][None, None, :]
@@ -234,7 +198,7 @@ def test_budget_leaves_nan_beyond_the_time_reached(gpu_cloudy, oracle):
     assert beyond[:, slow].any() and (~beyond[:, slow]).any() and not beyond[:, ~slow].any()
     nan, fin = np.isnan(got["saved"]), np.isfinite(got["saved"])
     assert np.all(nan.all(axis=1) == beyond) and np.all(fin.all(axis=1) == ~beyond)
-    assert np.all(blank_bits(got["saved_pad"]))
+    assert np.all(is_blank(got["saved_pad"]))
 
 
 # ---- 6. warm start
@@ -274,7 +238,7 @@ def test_float_planes(gpu_cloudy, oracle, kind):
     err = np.abs(got["u"].astype(np.float64) - want["u"])[fin] / np.abs(want["u"])[fin]
     print(f"float planes, {kind}: max relative difference {err.max():.2e}")
     assert err.max() <= 2.0 ** -24, err.max()
-    assert np.all(blank_bits(got["pad"]))
+    assert np.all(is_blank(got["pad"]))
 
 
 # ---- 8. served and refused
@@ -298,7 +262,7 @@ def test_served_and_refused(gpu_cloudy, oracle):
     print(f"numerical plan, COND: {(~same).sum()} of 65 parcels differ in (accepted, rejected); the others agree to "
           f"{rel[:, same].max():.2e} x evaluations; the state moved by {(np.abs(ref['u'] - u0) / np.abs(u0)).max():.2e}")
     assert (~same).sum() <= 0.05 * 65 and rel[:, same].max() <= B.TOL_EVAL
-    assert bits_equal(got["u"][[0, 3]], u0[[0, 3]]) and np.all(blank_bits(got["pad"]))
+    assert bits_equal(got["u"][[0, 3]], u0[[0, 3]]) and np.all(is_blank(got["pad"]))
     g0 = H.two_gamma_batch(65)
     _, _, fast = two_gamma_plan(cloudy, oracle, "fixed", dtype=2)          # CLOUDY_F32_FAST
     _, _, aot = two_gamma_plan(cloudy, oracle, "allinf", specialize=-1)    # no plan-time compilation
@@ -307,7 +271,7 @@ def test_served_and_refused(gpu_cloudy, oracle):
         got = box_adaptive(cloudy, plan, batch, 1e-3, 0.05, B.XI_BOX, times=ts, expect=E.EUNSUPPORTED)
         msg = L.cloudy_last_error().decode()
         assert "cloudy_cond_evap" in msg and "stage by stage" in msg, (what, msg)
-        assert np.all(blank_bits(got["saved_bits"])) and np.all(blank_bits(got["u"])), what
+        assert np.all(is_blank(got["saved_bits"])) and np.all(is_blank(got["u"])), what
         assert not got["accepted"].any() and np.all(got["t"].view(np.uint64) == SENTINEL)
 
 

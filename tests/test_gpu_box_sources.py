@@ -10,37 +10,18 @@ import numpy as np
 import pytest
 
 import bench
-from test_gpu_parity import INF, TOL_POLY, TOL_QUAD, _ssprk33_host, dev, make_case, many_mode_moments, mixed_moments
+from gpu_support import (INF, SENTINEL, TOL_POLY, TOL_QUAD, _ssprk33_host, blank, dev, make_case, many_mode_moments, mixed_moments, oracle_reference,
+                         rel_err)
 
 pytestmark = pytest.mark.gpu
 
 XI = 1e-8
-SENTINEL = np.float64(np.nan).view(np.uint64) | np.uint64(0x5EED)   # a NaN no arithmetic produces
-
-
-def oracle_reference(oracle, op, mom, dt, n_steps, xi, s, coal, cond):
-    """SSPRK33 with the oracle's right-hand sides"""
-    def rhs(u):
-        f = np.zeros_like(u)
-        if coal:
-            f = f + oracle.rhs_coal_batch(op, u)
-        if cond:
-            f = f + oracle.rhs_condensation_batch(op, xi, s, u)
-        return f
-
-    with np.errstate(all="ignore"):
-        return _ssprk33_host(rhs, mom, dt, n_steps)
 
 
 def regular(mom, want):
     """the regular parcels of test_fused_ssprk33_batch_vs_oracle_stepping: finite and within a factor 10 of their initial state"""
     with np.errstate(all="ignore"):
         return np.isfinite(want).all(axis=0) & (np.abs(want[:3]) <= 10 * np.abs(mom[:3]) + 1e-300).all(axis=0)
-
-
-def rel_err(got, want, mom, ok):
-    ref = np.abs(mom) + np.abs(want)
-    return np.abs(got - want)[:, ok] / np.maximum(ref[:, ok], 1e-300)
 
 
 def supersaturation(n):
@@ -108,7 +89,7 @@ def test_condensation_only_batch_four_closure_families(gpu_cloudy, oracle):
     buf[:, :n] = mom
     s_dev = dev(cloudy, s[None, :])
     u_in = dev(cloudy, buf)
-    u_out = dev(cloudy, np.full((nm, ld), SENTINEL, dtype=np.uint64).view(np.float64))
+    u_out = dev(cloudy, blank(nm, ld))
     cloudy._lib.check(box_steps(cloudy, plan, u_in, u_out, n, ld, cloudy.SRC_COND, s_dev, dt, n_steps))
     got = u_out.to_numpy()
     assert np.all(got[:, n:].view(np.uint64) == SENTINEL), "the padding columns were written"
@@ -116,7 +97,7 @@ def test_condensation_only_batch_four_closure_families(gpu_cloudy, oracle):
     err = rel_err(got[:, :n], want, mom, ok)
     print(f"condensation only, four closure families: {ok.sum()} regular parcels of {n}, max rel err {err.max():.2e}")
     assert err.max() < 1e-11, err.max()
-    u_zero = dev(cloudy, np.full((nm, ld), SENTINEL, dtype=np.uint64).view(np.float64))
+    u_zero = dev(cloudy, blank(nm, ld))
     cloudy._lib.check(box_steps(cloudy, plan, u_in, u_zero, n, ld, cloudy.SRC_COND, s_dev, dt, 0))
     z = u_zero.to_numpy()
     assert np.array_equal(z[:, :n], mom) and np.all(z[:, n:].view(np.uint64) == SENTINEL)
@@ -210,7 +191,7 @@ def test_two_moment_mode_partial_workgroup_and_moving_threshold(gpu_cloudy, orac
     buf = np.full((5, ld), 7.0)
     buf[:, :n] = mom
     u_in = dev(cloudy, buf)
-    u_out = dev(cloudy, np.full((5, ld), SENTINEL, dtype=np.uint64).view(np.float64))
+    u_out = dev(cloudy, blank(5, ld))
     cloudy._lib.check(box_steps(cloudy, plan, u_in, u_out, n, ld, cloudy.SRC_COAL | cloudy.SRC_COND, dev(cloudy, s[None, :]), dt, n_steps))
     got = u_out.to_numpy()
     assert np.all(got[:, n:].view(np.uint64) == SENTINEL), "the padding columns were written"

@@ -8,49 +8,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_support import DZ, NCOL, NZ, VEL, XI, blank, dev, is_blank, moving_column_case
+from gpu_support import column_plan as plan_of
+from gpu_support import column_run as run
 from test_column_adaptive_host import CASES, DT0, FIRST, T_SPAN, column_reference_cached
-from test_gpu_column_sources import DZ, NCOL, NZ, SENTINEL, VEL, XI, reference_case
-from test_gpu_parity import dev
 from tsit5_restated import DONE, DT_MIN, MAX_STEPS, default_opts
 
 pytestmark = pytest.mark.gpu
 COAL, COALCOND = 1, 3
-_PLANS = {}
-
-
-def plan_of(cloudy, oracle, case, dtype=0, **kw):
-    key = (case, dtype, tuple(sorted(kw.items())))
-    if key not in _PLANS:
-        par, _, dist_types, _ = reference_case(cloudy, oracle, case)
-        _PLANS[key] = (par, par.coal_data.plan(dist_types, vel=VEL, dtype=dtype, **kw))
-    return _PLANS[key]
-
-
-def run(cloudy, plan, u0, s, t_span, sources=COALCOND, xi=XI, ld=None, dt_in=None, dtype=np.float64, expect=0, **opts):
-    """one call of the C entry point on a host batch -> dict(u, dt, t, accepted, rejected, status, buf: the whole output buffer)"""
-    L = cloudy.lib()
-    nm, n = u0.shape
-    ncol = n // NZ
-    ld = n if ld is None else ld
-    buf = np.zeros((nm, ld), dtype)
-    buf.view(np.uint64 if dtype == np.float64 else np.uint32)[:] = SENTINEL if dtype == np.float64 else 0x7FC05EED
-    buf[:, :n] = u0
-    u_in, u_out = dev(cloudy, buf), dev(cloudy, buf)
-    s_dev = None if s is None else dev(cloudy, np.ascontiguousarray(s, dtype=np.float64)[None, :])
-    # (dt_dev, where given, is where the first step comes from: without a caller's array it holds opts.dt_init)
-    dt_dev = dev(cloudy, (np.full(max(ncol, 1), float(opts.get("dt_init", 0.0))) if dt_in is None else np.asarray(dt_in, dtype=np.float64))[None, :])
-    t_dev = cloudy.DeviceArray.zeros(1, max(ncol, 1))
-    info = cloudy.DeviceArray.zeros(3, max(ncol, 1), dtype=np.int32)
-    o = default_opts(cloudy, **opts)
-    rc = L.cloudy_rainshaft_tsit5_adaptive(plan.handle, NZ, ncol, ld, u_in.ptr, u_out.ptr, sources, None if s_dev is None else s_dev.ptr, 0.0,
-                                           xi, DZ, t_span, C.byref(o), dt_dev.ptr, t_dev.ptr, info.ptr, None)
-    assert rc == expect, L.cloudy_last_error().decode()
-    cloudy._lib.check(L.cloudy_stream_synchronize(None))
-    out = u_out.to_numpy()
-    i = info.to_numpy()[:, :ncol]
-    assert np.array_equal(u_in.to_numpy().view(np.uint8), buf.view(np.uint8))     # out of place: the input stays
-    return dict(u=out[:, :n], buf=out, dt=dt_dev.to_numpy()[0, :ncol], t=t_dev.to_numpy()[0, :ncol], accepted=i[0], rejected=i[1],
-                status=i[2])
 
 
 # ---- 1. decision parity
@@ -188,7 +153,7 @@ def test_warm_start_and_edge_cases(gpu_cloudy, oracle, case):
     _, plan = plan_of(cloudy, oracle, case)
     n = u0.shape[1]
     cold = run(cloudy, plan, u0, s, T_SPAN[case], ld=n + 37)
-    assert np.all(cold["buf"].view(np.uint64)[:, n:] == SENTINEL)
+    assert cold["pad"].shape[1] == 37 and np.all(is_blank(cold["pad"]))
     assert np.array_equal(cold["u"], run(cloudy, plan, u0, s, T_SPAN[case])["u"])
     warm = run(cloudy, plan, cold["u"], s, T_SPAN[case], dt_in=cold["dt"])
     a_w, a_c = warm["accepted"] + warm["rejected"], cold["accepted"] + cold["rejected"]
@@ -197,13 +162,10 @@ def test_warm_start_and_edge_cases(gpu_cloudy, oracle, case):
     still = run(cloudy, plan, u0, s, 0.0)
     assert np.array_equal(still["u"].view(np.uint64), u0.view(np.uint64))
     assert not still["accepted"].any() and not still["rejected"].any() and not still["status"].any() and not still["t"].any()
-    o = default_opts(cloudy)
+    o = default_opts(cloudy)   # (a direct call: no column, no leading dimension and no buffer is not a batch the driver can build)
     assert L.cloudy_rainshaft_tsit5_adaptive(plan.handle, NZ, 0, 0, None, None, COALCOND, None, 0.0, XI, DZ, 1.0, C.byref(o), None, None,
                                              None, None) == 0
-    ud, sd = dev(cloudy, u0), dev(cloudy, s[None, :])
-    cloudy._lib.check(L.cloudy_rainshaft_tsit5_adaptive(plan.handle, NZ, NCOL, n, ud.ptr, ud.ptr, COALCOND, sd.ptr, 0.0, XI, DZ, T_SPAN[case],
-                                                        C.byref(o), None, None, None, None))
-    assert np.array_equal(ud.to_numpy(), cold["u"])
+    assert np.array_equal(run(cloudy, plan, u0, s, T_SPAN[case], in_place=True, no_outputs=True)["u"], cold["u"])
 
 
 # ---- 7. float planes
@@ -216,7 +178,7 @@ def test_float_planes(gpu_cloudy, oracle, case):
     _, p64 = plan_of(gpu_cloudy, oracle, case)
     _, p32 = plan_of(gpu_cloudy, oracle, case, dtype=1)
     a = run(gpu_cloudy, p64, u32.astype(np.float64), s, T_SPAN[case], dt_init=DT0)
-    b = run(gpu_cloudy, p32, u32, s, T_SPAN[case], dt_init=DT0, dtype=np.float32)
+    b = run(gpu_cloudy, p32, u32, s, T_SPAN[case], dt_init=DT0)
     assert np.array_equal(b["u"], a["u"].astype(np.float32))
     for key in ("accepted", "rejected", "status", "t", "dt"):
         assert np.array_equal(a[key], b[key]), key
@@ -230,32 +192,24 @@ def test_refusals(gpu_cloudy, oracle):
     velocity terms: CLOUDY_EINVAL."""
     import bench
     from cloudy_jl_amd.box_model import _numerical_plan_for
-    from test_gpu_column_sources import _moving
 
     cloudy = gpu_cloudy
-    L, E = cloudy.lib(), cloudy._lib
+    E = cloudy._lib
     par, plan = plan_of(cloudy, oracle, "gamma_mixture")
-    mpar, mtypes, _, _ = _moving(cloudy, oracle)
+    mpar, _, mtypes, _ = moving_column_case(cloudy, oracle)
     plans = {"moving": (mpar.coal_data.plan(mtypes, vel=VEL), 6, "MovingThreshold"),
              "numerical": (_numerical_plan_for(bench.cfg4q_par(cloudy), 0), 9, "NumericalCoalStyle"),
              "f32_fast": (par.coal_data.plan([1, 1], vel=VEL, dtype=2), 6, "CLOUDY_F32_FAST"),
              "tall": (plan, 6, "1024"),
              "aot": (par.coal_data.plan([1, 1], vel=VEL, specialize=-1), 6, "compiled for the plan"),
              "no_velocity": (par.coal_data.plan([1, 1]), 6, "n_vel")}
-    o = default_opts(cloudy)
     for name, (p, nm, word) in plans.items():
         nz = 1025 if name == "tall" else 20
-        n = 2 * nz
-        fast = name == "f32_fast"
-        buf = np.zeros((nm, n), np.float32 if fast else np.float64)
-        buf.view(np.uint32 if fast else np.uint64)[:] = 0x7FC05EED if fast else SENTINEL
-        u, out = dev(cloudy, buf), dev(cloudy, buf)
-        rc = L.cloudy_rainshaft_tsit5_adaptive(p.handle, nz, 2, n, u.ptr, out.ptr, COALCOND, None, 0.01, XI, DZ, 1.0, C.byref(o), None, None,
-                                               None, None)
-        msg = L.cloudy_last_error().decode()
-        assert rc == (E.EINVAL if name == "no_velocity" else E.EUNSUPPORTED), (name, rc, msg)
+        got = run(cloudy, p, blank(nm, 2 * nz, np.float32 if name == "f32_fast" else np.float64), 0.01, 1.0, nz=nz, no_outputs=True,
+                  expect=E.EINVAL if name == "no_velocity" else E.EUNSUPPORTED)
+        msg = got["message"]
         assert word in msg and (name == "no_velocity" or "cloudy_rainshaft_cond_ssprk33_steps" in msg), (name, msg)
-        assert np.array_equal(out.to_numpy().view(np.uint8), buf.view(np.uint8)), name
+        assert np.all(is_blank(got["u"])), name
 
 
 # ---- 9. the Python wrapper

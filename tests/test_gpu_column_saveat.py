@@ -5,69 +5,22 @@ The reference is the NumPy restatement of tests/test_column_saveat_host.py (tsit
 on the oracle's column right-hand side, on the batch of tests/test_column_adaptive_host.py -- 27 columns of 20 cells, two workgroups
 at 512 threads, COAL | COND with the supersaturation profile on, from the caller's first step DT0 -- at the twelve save times of
 tsit5_restated.SAVE_FRACS.  Run with `-m gpu`."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from gpu_support import NCOL, NZ, VEL, XI, bits_equal, dev, is_blank, moving_column_case
+from gpu_support import column_plan as plan_of
+from gpu_support import column_run as run
 from test_column_adaptive_host import CASES, DT0, T_SPAN
 from test_column_saveat_host import SNAPSHOT_BOUND, column_saveat_reference_cached, snapshot_distance, snapshots_reached
-from test_gpu_column_adaptive import COALCOND, plan_of, run
-from test_gpu_column_sources import DZ, NCOL, NZ, SENTINEL, VEL, XI
-from test_gpu_parity import dev
-from tsit5_restated import DONE, MAX_STEPS, default_opts
+from tsit5_restated import DONE, MAX_STEPS
 
 pytestmark = pytest.mark.gpu
-SENTINEL32 = np.uint32(0x7FC05EED)   # a float NaN no arithmetic produces
 KEYS = ("u", "dt", "t", "accepted", "rejected", "status")
-NAME = "cloudy_rainshaft_tsit5_adaptive_saveat"
 
 
-def blank(planes, ld, dtype):
-    """(planes, ld) of the sentinel NaN of the plane type"""
-    f64 = dtype == np.float64
-    return np.full((planes, ld), SENTINEL if f64 else SENTINEL32, dtype=np.uint64 if f64 else np.uint32).view(dtype)
-
-
-def is_blank(x):
-    return x.view(np.uint64) == SENTINEL if x.dtype.itemsize == 8 else x.view(np.uint32) == SENTINEL32
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def saveat(cloudy, plan, u0, s, t_span, times, sources=COALCOND, xi=XI, ld=None, dtype=np.float64, in_place=False, nz=NZ, expect=0, **opts):
-    """one call of the C entry point on a host batch -> the dict of test_gpu_column_adaptive.run + saved (n_save, planes, n),
-    saved_pad (the columns n .. ld of every snapshot plane), beyond (one snapshot's worth of planes behind the last: never
-    written) and u_in (the input buffer after the call)"""
-    L = cloudy.lib()
-    nm, n = u0.shape
-    ncol = n // nz
-    ld = n if ld is None else ld
-    buf = blank(nm, ld, dtype)
-    buf[:, :n] = u0
-    u_in = dev(cloudy, buf)
-    u_out = u_in if in_place else dev(cloudy, blank(nm, ld, dtype))
-    s_dev = None if s is None else dev(cloudy, np.ascontiguousarray(s, dtype=np.float64)[None, :])
-    dt_dev = dev(cloudy, np.full(max(ncol, 1), float(opts.get("dt_init", 0.0)))[None, :])
-    t_dev = cloudy.DeviceArray.zeros(1, max(ncol, 1))
-    info = cloudy.DeviceArray.zeros(3, max(ncol, 1), dtype=np.int32)
-    n_save = len(times)
-    snap = dev(cloudy, blank((n_save + 1) * nm, ld, dtype))
-    arr = (C.c_double * max(n_save, 1))(*times)
-    o = default_opts(cloudy, **opts)
-    rc = getattr(L, NAME)(plan.handle, nz, ncol, ld, u_in.ptr, u_out.ptr, sources, None if s_dev is None else s_dev.ptr, 0.0, xi, DZ, t_span,
-                          C.byref(o), dt_dev.ptr, t_dev.ptr, info.ptr, None, n_save, arr if n_save else None, snap.ptr if n_save else None)
-    assert rc == expect, (rc, L.cloudy_last_error().decode())
-    cloudy._lib.check(L.cloudy_stream_synchronize(None))
-    out = u_out.to_numpy()
-    i = info.to_numpy()[:, :ncol]
-    sv = snap.to_numpy().reshape(n_save + 1, nm, ld)
-    return dict(u=out[:, :n], buf=out, dt=dt_dev.to_numpy()[0, :ncol], t=t_dev.to_numpy()[0, :ncol], accepted=i[0], rejected=i[1], status=i[2],
-                saved=sv[:n_save, :, :n], saved_pad=sv[:n_save, :, n:], beyond=sv[n_save], u_in=u_in.to_numpy(), input=buf,
-                message=L.cloudy_last_error().decode())
+def saveat(cloudy, plan, u0, s, t_span, times, **kw):
+    return run(cloudy, plan, u0, s, t_span, times=times, **kw)
 
 
 _RUNS = {}
@@ -100,7 +53,7 @@ def test_saving_does_not_disturb_the_integration(gpu_cloudy, oracle, case, block
     for key in KEYS:
         assert bits_equal(with_times[key], plain[key]), key
         assert bits_equal(without[key], plain[key]), key
-    assert is_blank(without["beyond"]).all()
+    assert is_blank(without["guard"]).all()
     if block:   # the snapshots do not depend on the workgroup size either
         assert bits_equal(with_times["saved"], device_run(gpu_cloudy, oracle, case)["saved"])
 
@@ -133,15 +86,15 @@ def test_end_points_and_padding(gpu_cloudy, oracle, case):
     n = u0.shape[1]
     assert ts[0] == 0.0 and ts[-1] == T_SPAN[case]
     assert bits_equal(got["saved"][0], u0) and bits_equal(got["saved"][-1], got["u"])
-    assert got["saved_pad"].shape[2] == 7 and is_blank(got["saved_pad"]).all() and is_blank(got["beyond"]).all()
-    assert is_blank(got["buf"][:, n:]).all()
-    assert bits_equal(got["u_in"], got["input"])
+    assert got["saved_pad"].shape[2] == 7 and is_blank(got["saved_pad"]).all() and is_blank(got["guard"]).all()
+    assert is_blank(got["pad"]).all()
+    assert bits_equal(got["u_in"], got["buf"])
     _, plan = plan_of(gpu_cloudy, oracle, case)
     same = saveat(gpu_cloudy, plan, u0, s, T_SPAN[case], ts, ld=n + 7, dt_init=DT0, in_place=True)
     assert bits_equal(same["saved"], got["saved"]) and bits_equal(same["u"], got["u"])
-    assert is_blank(same["saved_pad"]).all() and is_blank(same["beyond"]).all()
+    assert is_blank(same["saved_pad"]).all() and is_blank(same["guard"]).all()
     still = saveat(gpu_cloudy, plan, u0, s, 0.0, (0.0,), dt_init=DT0)          # t_span = 0: every snapshot is the input
-    assert bits_equal(still["saved"][0], u0) and bits_equal(still["u"], u0) and is_blank(still["beyond"]).all()
+    assert bits_equal(still["saved"][0], u0) and bits_equal(still["u"], u0) and is_blank(still["guard"]).all()
 
 
 # ---- 4. budget
@@ -165,7 +118,7 @@ def test_budget(gpu_cloudy, oracle, case):
     err = snapshot_distance(np.where(passed, got["saved"], 0.0), np.where(passed, want["saved"], 0.0))
     print(f"{case}, max_steps = 3: the snapshots the columns passed differ from the restatement's by {err:.2e} of the plane maxima")
     assert err < SNAPSHOT_BOUND
-    assert is_blank(got["beyond"]).all()
+    assert is_blank(got["guard"]).all()
 
 
 # ---- 5. independence
@@ -196,11 +149,11 @@ def test_float_planes(gpu_cloudy, oracle, case):
     _, p64 = plan_of(gpu_cloudy, oracle, case)
     _, p32 = plan_of(gpu_cloudy, oracle, case, dtype=1)
     a = saveat(gpu_cloudy, p64, u32.astype(np.float64), s, T_SPAN[case], ts, dt_init=DT0)
-    b = saveat(gpu_cloudy, p32, u32, s, T_SPAN[case], ts, dt_init=DT0, dtype=np.float32, ld=u0.shape[1] + 7)
+    b = saveat(gpu_cloudy, p32, u32, s, T_SPAN[case], ts, dt_init=DT0, ld=u0.shape[1] + 7)
     assert b["saved"].dtype == np.float32 and a["rejected"].sum() > 0
     assert np.array_equal(b["saved"], a["saved"].astype(np.float32))
     assert bits_equal(b["saved"][-1], b["u"]) and bits_equal(b["saved"][0], u32)
-    assert is_blank(b["saved_pad"]).all() and is_blank(b["beyond"]).all()
+    assert is_blank(b["saved_pad"]).all() and is_blank(b["guard"]).all()
     for key in ("accepted", "rejected", "status", "t", "dt"):
         assert np.array_equal(a[key], b[key]), key
 
@@ -211,12 +164,11 @@ def test_refusals(gpu_cloudy, oracle):
     fixed-step integrator; u_out and u_save keep their sentinel."""
     import bench
     from cloudy_jl_amd.box_model import _numerical_plan_for
-    from test_gpu_column_sources import _moving
 
     cloudy = gpu_cloudy
     E = cloudy._lib
     par, plan = plan_of(cloudy, oracle, "gamma_mixture")
-    mpar, mtypes, _, _ = _moving(cloudy, oracle)
+    mpar, _, mtypes, _ = moving_column_case(cloudy, oracle)
     plans = {"moving": (mpar.coal_data.plan(mtypes, vel=VEL), 6, "MovingThreshold"),
              "numerical": (_numerical_plan_for(bench.cfg4q_par(cloudy), 0), 9, "NumericalCoalStyle"),
              "f32_fast": (par.coal_data.plan([1, 1], vel=VEL, dtype=2), 6, "CLOUDY_F32_FAST"),
@@ -224,9 +176,9 @@ def test_refusals(gpu_cloudy, oracle):
     for name, (p, nm, word) in plans.items():
         nz = 1025 if name == "tall" else 20
         dtype = np.float32 if name == "f32_fast" else np.float64
-        got = saveat(cloudy, p, np.ones((nm, 2 * nz), dtype), None, 1.0, (0.0, 0.5, 1.0), nz=nz, dtype=dtype, expect=E.EUNSUPPORTED)
+        got = saveat(cloudy, p, np.ones((nm, 2 * nz), dtype), None, 1.0, (0.0, 0.5, 1.0), nz=nz, expect=E.EUNSUPPORTED)
         assert word in got["message"] and "cloudy_rainshaft_cond_ssprk33_steps" in got["message"], (name, got["message"])
-        assert is_blank(got["buf"]).all() and is_blank(got["saved"]).all() and is_blank(got["beyond"]).all(), name
+        assert is_blank(got["u"]).all() and is_blank(got["saved"]).all() and is_blank(got["guard"]).all(), name
 
 
 # ---- 8. the Python wrapper

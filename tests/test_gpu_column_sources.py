@@ -9,48 +9,13 @@ import numpy as np
 import pytest
 
 import bench
-from test_gpu_parity import EPS, INF, TOL_POLY, dev, make_case, run_rhs
+from gpu_support import (DT, DZ, EPS, GOLOVIN, INF, NCOL, NZ, SENTINEL, TOL_POLY, VEL, XI, column_set, dev, make_case, moving_column_case,
+                         reference_case, run_rhs, supersaturation)
 
 pytestmark = pytest.mark.gpu
 
-XI = 1e-8
-VEL = ((50.0, 1.0 / 6),)
-GOLOVIN = [[EPS / 1e6, 5.0], [5.0, 0.0]]
-NZ, DZ, DT, N_STEPS, NCOL = 20, 150.0, 1.0, 40, 27   # 25 columns per 512-thread workgroup at 20 cells: 27 spill into a second one
-SENTINEL = np.float64(np.nan).view(np.uint64) | np.uint64(0x5EED)   # a NaN no arithmetic produces
+N_STEPS = 40
 _CACHE = {}
-
-
-def supersaturation(nz, dz, ncol):
-    """one value per cell in the cell order of the state (cell col * nz + iz): 0.03 in the cloud layer (z >= 1350 m), -0.2 below,
-    scaled by a factor that differs from column to column -- a wrong cell-to-s mapping cannot pass"""
-    z = (np.arange(nz) + 0.5) * dz
-    prof = np.where(z >= 1350.0, 0.03, -0.2)
-    return np.concatenate([(0.5 + 0.05 * c) * prof for c in range(ncol)])
-
-
-def reference_case(cloudy, oracle, case):
-    """par, op, dist_types, amp of the two configurations of test_rainshaft_column_integrator_ssprk33"""
-    if case == "gamma_mixture":   # rainshaft_gamma_mixture.jl:15-60: the ranked body
-        dist_types, thr, amp = [1, 1], (2e-10, INF), np.array([1e7, 1e-3, 2e-13, 0.0, 0.0, 0.0])
-    else:                         # rainshaft_single_gamma.jl: the all-Inf body
-        dist_types, thr, amp = [1], (INF,), np.array([1e7, 1e-3, 2e-13])
-    par, op, _ = make_case(cloudy, oracle, dist_types, GOLOVIN, thr, bench.NORMS, vel=VEL)
-    par.dz, par.nz, par.dt = DZ, NZ, DT
-    return par, op, dist_types, amp
-
-
-def column_set(amp):
-    """the columns of test_rainshaft_column_integrator_ssprk33 (scaled slabs, the slab touching the top, the cell with -1e-30),
-    extended to 27 columns"""
-    z = (np.arange(NZ) + 0.5) * DZ
-    at = ((z >= 0.5 * z.max() - DZ / 2) & (z < 0.75 * z.max() - DZ / 2)).astype(float)
-    cols = [np.outer(amp * s, at) for s in (1.0, 0.3, 3.0)]
-    shifted = np.outer(amp, np.roll(at, 3))
-    dirty = np.outer(amp, at)
-    dirty[:, 2] = -1e-30
-    cols += [shifted, dirty] + [np.outer(amp * (0.5 + 0.1 * i), at) for i in range(NCOL - 5)]
-    return np.ascontiguousarray(np.concatenate(cols, axis=1))
 
 
 def oracle_stepping(oracle, op, u, nz, dz, dt, n_steps, xi, s):
@@ -261,18 +226,15 @@ def _moving(cloudy, oracle):
     """A MovingThreshold two-mode plan.  cloudy_rainshaft_rhs refuses such plans (the reference's make_rainshaft_rhs uses
     FixedThreshold), so the host-driven right-hand side of this case is put together from the entry points that serve them
     (rhs_parts)."""
-    par, op, ts = make_case(cloudy, oracle, [1, 1], GOLOVIN, (0.9, 1.0), bench.NORMS, moving=True, vel=VEL)
-    par.nz, par.dz, par.dt = NZ, DZ, DT
-    amp = np.array([1e7, 1e-3, 2e-13, 1e4, 1e-4, 2e-12])
-    u0 = column_set(amp)[:, : 3 * NZ].copy()
-    plan = par.coal_data.plan([1, 1], vel=VEL)
+    par, ts, dist_types, u0 = moving_column_case(cloudy, oracle)
+    plan = par.coal_data.plan(dist_types, vel=VEL)
 
     def rhs_fn(x, m):
         coal, div = rhs_parts(cloudy, par, plan, x, m, ts)
         return coal + div
 
     rhs_fn.ts = ts
-    return par, [1, 1], u0, rhs_fn
+    return par, dist_types, u0, rhs_fn
 
 
 @pytest.mark.parametrize("path", ["nz300_512_threads", "nz700_1024_threads", "nz1500_stage_by_stage", "five_modes_no_workgroup_fits",

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import bench
-from test_gpu_parity import INF, _ssprk33_host, assert_close_scaled, dev, mixed_moments
+from gpu_support import INF, _ssprk33_host, assert_close_scaled, converged_case, dev, mixed_moments, numerical_case
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,31 +35,6 @@ def assert_same_rule(got, want, scale, noise, what, tol=TOL_SAME_RULE):
     worst = float((np.maximum(excess, 0.0) / np.maximum(scale[ok], 1e-300)).max()) if err.size else 0.0
     assert worst <= tol, f"{what}: max (|diff| - 8 noise) / scale = {worst:.3e} > {tol:g}"
     return worst
-
-
-def kernel_funcs(cloudy, oracle):
-    return {
-        "constant": (cloudy.ConstantKernelFunction(1e-4), oracle.kernel_func(oracle.KF_CONSTANT, 1e-4)),
-        "linear": (cloudy.LinearKernelFunction(5.0), oracle.kernel_func(oracle.KF_LINEAR, 5.0)),
-        "hydro": (cloudy.HydrodynamicKernelFunction(1e2 * np.pi), oracle.kernel_func(oracle.KF_HYDRODYNAMIC, 1e2 * np.pi)),
-        "long": (cloudy.LongKernelFunction(5.236e-10, 9.44e9, 5.78), oracle.kernel_func(oracle.KF_LONG, 5.236e-10, 9.44e9, 5.78)),
-    }
-
-
-def numerical_case(cloudy, oracle, dist_types, kname, nq=10, k_range=None):
-    """product-side ODE parameters (p.kernel_func normalised, as the reference's drivers pass it) + oracle params"""
-    kf, okf = kernel_funcs(cloudy, oracle)[kname]
-    mk = {0: lambda: cloudy.ExponentialPrimitiveParticleDistribution(1.0, 1.0),
-          1: lambda: cloudy.GammaPrimitiveParticleDistribution(1.0, 1.0, 1.0),
-          3: lambda: cloudy.LognormalPrimitiveParticleDistribution(1.0, 1.0, 1.0)}
-    pd = tuple(mk[t]() for t in dist_types)
-    npm = tuple({0: 2, 1: 3, 3: 3}[t] for t in dist_types)
-    extra = {"k_range": k_range} if k_range else {}
-    par = cloudy.ODEParameters(pd, None, npm, NORMS, kernel_func=cloudy.get_normalized_kernel_func(kf, NORMS),
-                               quad_order=nq, quad_mode=cloudy.QUAD_FIXED, **extra)
-    op = oracle.make_params(list(dist_types), np.zeros((1, 1)), (INF,) * len(dist_types), norms=NORMS,
-                            **({"k_range": k_range} if k_range else {}))
-    return par, op, oracle.get_normalized_kernel_func(okf, NORMS)
 
 
 def run_numerical(cloudy, par, mom):
@@ -333,12 +308,6 @@ def test_configs3_at_its_full_1e8_parcels_on_one_gpu_and_its_shards(gpu_cloudy):
 
 # ---- CONVERGED mode (quad_mode = CLOUDY_QUAD_CONVERGED, csrc/quad_conv.hpp) --------------------------------------------
 TOL_CONVERGED = 1e-11   # HIP vs the same-rule oracle; the oracle vs adaptive quadrature is a CPU test (<= 1e-8 of scale)
-
-
-def converged_case(cloudy, oracle, dist_types, kname, q=8):
-    par, op, okf = numerical_case(cloudy, oracle, dist_types, kname, q)
-    par.quad_mode = cloudy.QUAD_CONVERGED
-    return par, op, okf
 
 
 @pytest.mark.parametrize("dist_types,kname,q", [

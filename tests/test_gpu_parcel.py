@@ -1,6 +1,6 @@
 """GPU tests of the adiabatic parcel (cloudy_parcel_ssprk33_steps, cloudy_parcel_rhs; csrc/parcel.hpp).
 
-The stepping reference is OrdinaryDiffEq's SSPRK33 formulas (_ssprk33_host of test_gpu_parity) over the NumPy right-hand side
+The stepping reference is OrdinaryDiffEq's SSPRK33 formulas (gpu_support._ssprk33_host) over the NumPy right-hand side
 of test_parcel_host (parcel_rhs_numpy) with the moments' tendency from the unchanged oracle,
     dmom = oracle.rhs_condensation_batch(op, 1.0, xi(T) (S - 1) (1000 / rho_l)^(1/3), mom)
 (the tendency is linear in xi s), plus oracle.rhs_coal_batch(op, mom) for coal = True.
@@ -15,24 +15,15 @@ import numpy as np
 import pytest
 
 import bench
-from test_gpu_parity import INF, _ssprk33_host, dev, make_case
+from gpu_support import INF, SENTINEL, _ssprk33_host, blank, dev, driver_case, make_case, mass_rows
 from test_parcel_host import DEFAULTS, M0_DROP, N0, driver_initial_state, mean_radius_um, p_vs, parcel_rhs_numpy, rogers_deviation
 
 pytestmark = pytest.mark.gpu
 
 NORMS = (1e8, 1e-12)
-SENTINEL = np.float64(np.nan).view(np.uint64) | np.uint64(0x5EED)   # a NaN no arithmetic produces
 TOL = 1e-10   # per plane, of |y0| + |want| (S: of the trajectory's max |S - 1|): the condensation right-hand side is asserted at
 #               1e-11 per evaluation elsewhere in this suite, the system relaxes rather than amplifies, and 120 evaluations at the
 #               measured ~1e-14 stay below 1e-11 -- 1e-10 leaves one order
-
-
-def mass_rows(dist_types):
-    rows, off = [], 0
-    for t in dist_types:
-        rows.append(off + 1)
-        off += 3 if t in (1, 3) else 2
-    return rows
 
 
 def reference(oracle, op, c, y0, w, dt, n_steps, rows, coal=False):
@@ -63,17 +54,6 @@ def steps(cloudy, plan, y_in, y_out, n, ld, sources, w, dt, n_steps, params=None
     c = (params or cloudy.ParcelParams()).to_c()
     return cloudy.lib().cloudy_parcel_ssprk33_steps(plan.handle, n, ld, y_in.ptr, y_out.ptr, sources, w_ptr, w_val, C.byref(c), dt,
                                                     n_steps, None)
-
-
-def driver_case(name):
-    """init_conditions of parcel_example.jl:114-146 -> (dist_types, moments)"""
-    N, m0 = N0, M0_DROP
-    if name == "monodisperse":
-        return [2], [N, N * m0]
-    if name == "gamma":   # k = 2, theta = m0 / 2
-        return [1], [N, N * m0, N * (m0 / 2) ** 2 * 6]
-    th_g = (N * m0 / 2) / (N / 10) / 2   # mixture: Exponential(0.9 N, .) + Gamma(0.1 N, ., 2), half the mass each
-    return [0, 1], [0.9 * N, N * m0 / 2, 0.1 * N, N * m0 / 2, 0.1 * N * th_g**2 * 6]
 
 
 @pytest.fixture(scope="module")
@@ -171,7 +151,7 @@ def batch_run(gpu_cloudy, oracle):
     buf[:, :n] = y0
     w_dev = dev(cloudy, w[None, :])
     y_in = dev(cloudy, buf)
-    y_out = dev(cloudy, np.full(buf.shape, SENTINEL, dtype=np.uint64).view(np.float64))
+    y_out = dev(cloudy, blank(*buf.shape))
     cloudy._lib.check(steps(cloudy, plan, y_in, y_out, n, ld, cloudy.SRC_COND, w_dev, dt, n_steps))
     return dict(plan=plan, par=par, n=n, ld=ld, dt=dt, n_steps=n_steps, y0=y0, w=w, want=want, smax=smax, buf=buf, y_in=y_in,
                 w_dev=w_dev, got=y_out.to_numpy())
@@ -190,7 +170,7 @@ def test_random_batch_four_closure_families(gpu_cloudy, batch_run):
     err = plane_err(got[:, :n], b["want"], y0, b["smax"])
     print(f"random batch: max err vs the reference stepping {err.max():.2e} (per plane {np.array2string(err.max(axis=1), precision=1)})")
     assert err.max() <= TOL, err.max(axis=1)
-    fresh = lambda: dev(cloudy, np.full(b["buf"].shape, SENTINEL, dtype=np.uint64).view(np.float64))   # noqa: E731
+    fresh = lambda: dev(cloudy, blank(*b["buf"].shape))   # noqa: E731
     z = fresh()
     cloudy._lib.check(steps(cloudy, plan, b["y_in"], z, n, ld, cloudy.SRC_COND, b["w_dev"], b["dt"], 0))
     z = z.to_numpy()

@@ -4,7 +4,6 @@ plan's mom_norms) on the restated right-hand side of test_parcel_host (tests/tes
 restatement on them), and a reltol = 1e-11 run of the same restatement.
 
 Run with `-m gpu`.  Batch sizes 1, 65 and 257 in buffers of leading dimension n + 15."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -12,10 +11,9 @@ import pytest
 
 import test_parcel_adaptive_host as A
 import test_tsit5_adaptive_host as H
-from test_gpu_parity import INF, dev, make_case
-from test_gpu_tsit5_adaptive import SENTINEL, SIZES, same_counts, sentinel_planes, two_gamma_plan
-from test_gpu_tsit5_saveat import bits_equal, blank_bits
-from tsit5_restated import adaptive_tsit5, default_opts, plane_norms, save_times
+from gpu_support import (INF, SENTINEL, SIZES, adaptive_call, bits_equal, dev, driver_case, is_blank, make_case, mass_rows, same_counts,
+                         two_gamma_plan)
+from tsit5_restated import adaptive_tsit5, plane_norms, save_times
 
 pytestmark = pytest.mark.gpu
 
@@ -30,35 +28,9 @@ def plan_of(cloudy, oracle, types, kc=((1.0,),), thr=None, norms=A.NORMS, dtype=
     return par, op, par.coal_data.plan(types, dtype=dtype, specialize=specialize)
 
 
-def parcel_adaptive(cloudy, plan, y0, w, t_span, sources=COND, times=(), reltol=1e-6, max_steps=10000, ld=None, dt_in="zeros",
-                    in_place=False, expect=0):
-    """the C entry point itself on a batch y0 (planes, n) in buffers of leading dimension ld; w: a float, or an array (through w_dev)"""
-    L = cloudy.lib()
-    planes, n = y0.shape
-    ld = n if ld is None else ld
-    buf = np.full((planes, ld), 7.0)
-    buf[:, :n] = y0
-    y_in = dev(cloudy, buf)
-    y_out = y_in if in_place else dev(cloudy, sentinel_planes(planes, ld))
-    w_d = None if np.ndim(w) == 0 else dev(cloudy, np.pad(np.asarray(w, dtype=np.float64), (0, ld - n))[None, :])
-    dt_d = dev(cloudy, (np.zeros(ld) if isinstance(dt_in, str) else np.pad(dt_in, (0, ld - n)))[None, :])
-    t_d = dev(cloudy, sentinel_planes(1, ld))
-    info = cloudy.DeviceArray.zeros(3, ld, np.int32)
-    n_save = len(times)
-    snap = dev(cloudy, sentinel_planes(max(n_save, 1) * planes, ld))
-    arr = (C.c_double * max(n_save, 1))(*times)
-    opts = default_opts(cloudy, reltol=reltol, abstol=1e-9, max_steps=max_steps)
-    c = cloudy.ParcelParams().to_c()
-    rc = L.cloudy_parcel_tsit5_adaptive(plan.handle, n, ld, y_in.ptr, y_out.ptr, sources, None if w_d is None else w_d.ptr,
-                                        0.0 if w_d is not None else float(w), C.byref(c), t_span, C.byref(opts), dt_d.ptr, t_d.ptr,
-                                        info.ptr, None, n_save, arr if n_save else None, snap.ptr if n_save else None)
-    assert rc == expect, (rc, L.cloudy_last_error().decode())
-    out, counts, sv = y_out.to_numpy(), info.to_numpy(), snap.to_numpy()
-    bits = sv.view(np.uint64)
-    sv = sv.reshape(max(n_save, 1), planes, ld)[:n_save]
-    return dict(u=out[:, :n], pad=out[:, n:], u_in=y_in.to_numpy(), buf=buf, t=t_d.to_numpy()[0, :n], accepted=counts[0, :n],
-                rejected=counts[1, :n], status=counts[2, :n], dt=dt_d.to_numpy()[0, :n], saved=sv[:, :, :n], saved_pad=sv[:, :, n:],
-                saved_bits=bits)
+def parcel_adaptive(cloudy, plan, y0, w, t_span, sources=COND, **kw):
+    """w: a float, or an array (through w_dev)"""
+    return adaptive_call("cloudy_parcel_tsit5_adaptive", cloudy, plan, y0, t_span, sources=sources, forcing=w, **kw)
 
 
 def parity(got, ref, tight, y0, n, what):
@@ -94,7 +66,7 @@ def test_decision_parity_on_the_decade_batch(gpu_cloudy, oracle, reltol, n):
     assert np.all(ref["status"] == 0) and np.all(got["status"] == 0) and np.all(got["t"] == A.T_SPAN)
     parity(got, ref, A.decade_tight(n, plan=True), y0, n, f"decade batch reltol={reltol:g} n={n}")
     assert bits_equal(got["u"][4], y0[4])
-    assert np.all(blank_bits(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
+    assert np.all(is_blank(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
 
 
 def test_decision_parity_with_coalescence(gpu_cloudy, oracle):
@@ -108,7 +80,7 @@ def test_decision_parity_with_coalescence(gpu_cloudy, oracle):
     assert np.all(got["status"] == 0) and np.all(got["t"] == A.COAL_T)
     parity(got, ref, tight, y0, n, "COAL | COND n=257")
     assert not bits_equal(got["u"][4], y0[4])
-    assert np.all(blank_bits(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
+    assert np.all(is_blank(got["pad"])) and np.array_equal(got["u_in"], got["buf"])
 
 
 # ---- 2. dense output
@@ -127,7 +99,7 @@ def test_dense_output(gpu_cloudy, oracle):
     assert np.all(got["status"] == 0) and np.isfinite(got["saved"]).all()
     assert bits_equal(got["saved"][0], y0) and bits_equal(got["saved"][-1], got["u"])
     assert bits_equal(got["saved"][:, 4], np.broadcast_to(y0[4], (12, n)))
-    assert np.all(blank_bits(got["saved_pad"])) and np.all(blank_bits(got["pad"]))
+    assert np.all(is_blank(got["saved_pad"])) and np.all(is_blank(got["pad"]))
     same = same_counts(got, ref)
     assert (~same).sum() <= 0.05 * n, (~same).sum()
     rel = np.abs(got["saved"] - ref["saved"]) / np.maximum(np.abs(y0)[None] + np.abs(ref["saved"]), 1e-300) / ref["evals"][None, None, :]
@@ -162,7 +134,7 @@ def test_budget_leaves_nan_beyond_the_time_reached(gpu_cloudy, oracle):
     assert beyond[:, slow].any() and (~beyond[:, slow]).any() and not beyond[:, ~slow].any()
     nan, fin = np.isnan(got["saved"]), np.isfinite(got["saved"])
     assert np.all(nan.all(axis=1) == beyond) and np.all(fin.all(axis=1) == ~beyond)
-    assert np.all(blank_bits(got["saved_pad"]))
+    assert np.all(is_blank(got["saved_pad"]))
 
 
 # ---- 4. warm start and in place
@@ -206,8 +178,6 @@ def test_batch_independence(gpu_cloudy, oracle):
 def test_driver_plans_with_the_oracle_tendency(gpu_cloudy, oracle, name):
     """a Gamma plan and an Exponential + Gamma plan with COND, n = 65, N and w spread as in the decade batch: the parity rule with
     the moments' tendency from the oracle"""
-    from test_gpu_parcel import driver_case, mass_rows
-
     cloudy = gpu_cloudy
     n = 65
     types, mom = driver_case(name)
@@ -224,7 +194,7 @@ def test_driver_plans_with_the_oracle_tendency(gpu_cloudy, oracle, name):
     assert np.all(ref["status"] == 0) and np.all(got["status"] == 0) and np.all(got["t"] == A.T_SPAN)
     parity(got, ref, tight, y0, n, name)
     number = [4 + r - 1 for r in rows]
-    assert bits_equal(got["u"][number], y0[number]) and np.all(blank_bits(got["pad"]))
+    assert bits_equal(got["u"][number], y0[number]) and np.all(is_blank(got["pad"]))
 
 
 def test_served_and_refused(gpu_cloudy, oracle):
@@ -255,7 +225,7 @@ def test_served_and_refused(gpu_cloudy, oracle):
         got = parcel_adaptive(cloudy, plan, y0, w, 1.0, sources=sources, times=ts, expect=E.EUNSUPPORTED)
         msg = L.cloudy_last_error().decode()
         assert "stage by stage" in msg and "cloudy_cond_evap" in msg, (what, msg)
-        assert np.all(blank_bits(got["saved_bits"])) and np.all(blank_bits(got["u"])), what
+        assert np.all(is_blank(got["saved_bits"])) and np.all(is_blank(got["u"])), what
         assert not got["accepted"].any() and np.all(got["t"].view(np.uint64) == SENTINEL)
 
 

@@ -20,80 +20,14 @@ import numpy as np
 import pytest
 
 import bench
-from tsit5_restated import A_ROWS
+from gpu_support import (EPS, INF, SENTINEL, TOL_POLY, TOL_QUAD, _ssprk33_host, _tsit5_host, assert_close_scaled, blank, converged_case, dev,
+                         make_case, many_mode_moments, mixed_moments, numerical_case, run_rhs)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-EPS = float(np.finfo(np.float64).eps)
-INF = float("inf")
-TOL_POLY = 1e-13   # all-Inf polynomial path (north_star: 1e-12)
-TOL_QUAD = 1e-12   # Simpson / incomplete-gamma path, fp64 (north_star: 1e-8)
-TOL_REL = 1e-10    # plain relative error of outputs that are not small differences of large terms
 TYPES = {"exponential": 0, "gamma": 1}
-
-
-def dev(cloudy, a):
-    return cloudy.DeviceArray.from_numpy(a)
-
-
-def run_rhs(cloudy, par, mom, ts=None):
-    rhs = cloudy.make_box_model_rhs(cloudy.AnalyticalCoalStyle(), ts)
-    m = dev(cloudy, mom)
-    dm = cloudy.DeviceArray.zeros(*mom.shape)
-    rhs(dm, m, par, 0.0)
-    return dm.to_numpy()
-
-
-def make_case(cloudy, oracle, dist_types, kc, thr, norms, moving=False, k_range=(EPS, 10.0), vel=()):
-    """product-side ODE parameters + oracle params for the same configuration"""
-    N = len(dist_types)
-    kc = np.asarray(kc, dtype=np.float64)
-    if kc.ndim == 2:
-        kc = np.broadcast_to(kc, (N, N) + kc.shape).copy()
-    kernels = tuple(tuple(cloudy.CoalescenceTensor(kc[j, k]) for k in range(N)) for j in range(N))
-    npm = tuple({0: 2, 1: 3, 2: 2, 3: 3}[t] for t in dist_types)
-    ts = cloudy.MovingThreshold() if moving else cloudy.FixedThreshold()
-    cd = cloudy.CoalescenceData(kernels, npm, thr, norms, ts)
-    mk = {0: lambda: cloudy.ExponentialPrimitiveParticleDistribution(1.0, 1.0),
-          1: lambda: cloudy.GammaPrimitiveParticleDistribution(1.0, 1.0, 1.0),
-          2: lambda: cloudy.MonodispersePrimitiveParticleDistribution(1.0, 1.0),
-          3: lambda: cloudy.LognormalPrimitiveParticleDistribution(1.0, 1.0, 1.0)}
-    pd = tuple(mk[t]() for t in dist_types)
-    extra = {"vel": vel} if len(vel) else {}
-    par = cloudy.ODEParameters(pd, cd, npm, norms, k_range=k_range, **extra)
-    op = oracle.make_params(list(dist_types), kc, thr, norms=norms, threshold_style=1 if moving else 0,
-                            k_range=k_range, vel=vel)
-    return par, op, ts
-
-
-def assert_close_scaled(got, want, scale, tol, what=""):
-    assert got.shape == want.shape
-    nan_g, nan_w = np.isnan(got), np.isnan(want)
-    assert np.array_equal(nan_g, nan_w), f"{what}: NaN pattern differs"
-    ok = ~nan_w
-    err = np.abs(got[ok] - want[ok])
-    bound = tol * scale[ok]
-    bad = err > bound
-    worst = (err / np.maximum(scale[ok], 1e-300)).max() if err.size else 0.0
-    assert not bad.any(), f"{what}: max |diff|/scale = {worst:.3e} > {tol:g} ({bad.sum()} of {err.size})"
-    if tol <= TOL_QUAD:   # fp64 comparisons: outputs that are not cancellations must also agree RELATIVELY
-        big = np.abs(want[ok]) > 1e-3 * scale[ok]
-        rel = err[big] / np.abs(want[ok][big])
-        assert not (rel > TOL_REL).any(), f"{what}: max relative error of non-cancelling outputs {rel.max():.3e} > {TOL_REL:g}"
-    return worst
-
-
-def mixed_moments(dist_types, n, seed):
-    """physical moments for a mixed Exp/Gamma mode list, (nmom, n)"""
-    if len(dist_types) > 4:   # (bench.synth_moments knows the four size classes of the reference's examples)
-        return many_mode_moments(dist_types, n, seed)[0]
-    full = bench.synth_moments(len(dist_types), n, seed)
-    rows = []
-    for i, t in enumerate(dist_types):
-        rows += [full[3 * i], full[3 * i + 1]] + ([full[3 * i + 2]] if t in (1, 3) else [])
-    return np.ascontiguousarray(np.stack(rows))
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -289,25 +223,6 @@ def test_mode_and_order_families_vs_oracle(gpu_cloudy, oracle, dist_types, P, th
     tol = TOL_QUAD if any(np.isfinite(thr)) else TOL_POLY
     worst = assert_close_scaled(d, want, scale, tol, f"N={N} P={P}")
     print(f"N={N} P={P} thr={thr}: max |hip-oracle|/scale = {worst:.2e}")
-
-
-def many_mode_moments(dist_types, n, seed):
-    """physical moments of N size classes between 1e-12 and 1e-4 kg (one decade each for N = 8), number densities falling
-    with size as in bench.synth_moments, 1 % degenerate parcels per mode; -> (moments, mask of the parcels without a degenerate mode)"""
-    N = len(dist_types)
-    regular = np.ones(n, dtype=bool)
-    rng = np.random.Generator(np.random.Philox(key=seed))
-    edges = np.logspace(-12, -4, N + 1)
-    rows = []
-    for i, t in enumerate(dist_types):
-        hi = 1e9 * 10.0 ** (-1.5 * i * 8 / N)
-        m = bench._gamma_mode(rng, n, hi * 1e-3, hi, 0.5 if i == 0 else 1.0, 7.0, edges[i], edges[i + 1])
-        z = rng.choice(n, max(n // 100, 1), replace=False)
-        m[:, z[: len(z) // 2]] = 0.0
-        m[2, z[len(z) // 2:]] = m[1, z[len(z) // 2:]] ** 2 / m[0, z[len(z) // 2:]]
-        regular[z] = False
-        rows += [m[0], m[1]] + ([m[2]] if t in (1, 3) else [])
-    return np.ascontiguousarray(np.stack(rows)), regular
 
 
 @pytest.mark.parametrize("dist_types,P,thr,moving", [
@@ -720,20 +635,6 @@ def test_full_size_properties_cfg4_cfg5_1p25e7(gpu_cloudy):
     assert np.all(np.abs(f2[:, ok] - 2.0 * f[:, ok]) <= 3e-7 * np.abs(f2[:, ok]))       # linear in the velocity coefficient
 
 
-def _ssprk33_host(rhs_fn, u, dt, n_steps):
-    """OrdinaryDiffEq's SSPRK33 update formulas with a host-side RHS callable (numpy)."""
-    u = u.copy()
-    for _ in range(n_steps):
-        up = u.copy()
-        k = rhs_fn(u)
-        u = up + dt * k
-        k = rhs_fn(u)
-        u = (3.0 * up + u + dt * k) / 4.0
-        k = rhs_fn(u)
-        u = (up + 2.0 * u + 2.0 * dt * k) / 3.0
-    return u
-
-
 def test_cfg1_single_box_trajectory_ssprk33(gpu_cloudy, oracle):
     """BASELINE configs[0] / box_single_gamma.jl:15-36: one 0-D box, Gamma(1e8, 1e-10, 1), Golovin b = 5 (order-1
     tensor), norms (1e6, 1e-9), tspan (0, 120), SSPRK33 with dt = 10.  The fused device integrator against (i) the
@@ -760,17 +661,6 @@ def test_cfg1_single_box_trajectory_ssprk33(gpu_cloudy, oracle):
     u_in, u_out = dev(cloudy, u0), cloudy.DeviceArray.zeros(3, 64)
     cloudy.solve_ssprk33(par, u_in, dt, 0, out=u_out)
     assert np.array_equal(u_out.to_numpy(), u0) and np.array_equal(u_in.to_numpy(), u0)
-
-
-def _tsit5_host(rhs_fn, u, dt, n_steps):
-    """the Tsit5 tableau (Tsitouras 2011; OrdinaryDiffEq's Tsit5()) with a fixed step and a host-side RHS callable"""
-    u = u.copy()
-    for _ in range(n_steps):
-        k = [rhs_fn(u)]
-        for row in A_ROWS[:-1]:
-            k.append(rhs_fn(u + dt * sum(a * ki for a, ki in zip(row, k))))
-        u = u + dt * sum(a * ki for a, ki in zip(A_ROWS[-1], k))
-    return u
 
 
 def test_cfg0_single_box_tsit5_fixed_step(gpu_cloudy, oracle):
@@ -863,7 +753,6 @@ def test_tsit5_serves_every_plan_family_ssprk33_serves(gpu_cloudy, oracle):
     cloudy._lib.check(cloudy.lib().cloudy_tsit5_steps(plan_aot.handle, 600, 600, ua.ptr, ua.ptr, dt, ns, None))
     assert (np.abs(ua.to_numpy() - got)[:, ok] / np.maximum(ref[:, ok], 1e-300)).max() < 1e-12
     # (ii) NumericalCoalStyle: converged mode (the drop-in's default) and the 10-point rule, 3 Gamma modes, hydrodynamic
-    from test_gpu_numerical import converged_case, numerical_case
     mom = bench.synth_moments(3, 300, seed=12, degenerate_frac=0.0)
     for conv in (True, False):
         par, opn, okf = (converged_case if conv else numerical_case)(cloudy, oracle, [1, 1, 1], "hydro")
@@ -1053,7 +942,6 @@ def test_fused_integrators_two_moment_mode_partial_workgroup_and_padding(gpu_clo
     # reference's 5e-10 kg the Exponential cloud mode feeds the rain mode by more than a factor 10 in two steps: 208)
     mom = mixed_moments(dist_types, n, seed=7)
     tol = TOL_QUAD if any(np.isfinite(thr)) else TOL_POLY
-    sentinel = np.float64(np.nan).view(np.uint64) | np.uint64(0x5EED)   # a NaN no arithmetic produces
     L = cloudy.lib()
     for what, host, entry in (("SSPRK33", _ssprk33_host, L.cloudy_ssprk33_steps), ("Tsit5", _tsit5_host, L.cloudy_tsit5_steps)):
         with np.errstate(all="ignore"):
@@ -1063,10 +951,10 @@ def test_fused_integrators_two_moment_mode_partial_workgroup_and_padding(gpu_clo
         buf = np.full((5, ld), 7.0)
         buf[:, :n] = mom
         u_in = dev(cloudy, buf)
-        u_out = dev(cloudy, np.full((5, ld), sentinel, dtype=np.uint64).view(np.float64))
+        u_out = dev(cloudy, blank(5, ld))
         cloudy._lib.check(entry(plan.handle, n, ld, u_in.ptr, u_out.ptr, dt, n_steps, None))
         got = u_out.to_numpy()
-        assert np.all(got[:, n:].view(np.uint64) == sentinel), f"{what}: the padding columns were written"
+        assert np.all(got[:, n:].view(np.uint64) == SENTINEL), f"{what}: the padding columns were written"
         assert np.array_equal(u_in.to_numpy(), buf), f"{what}: the input changed"
         ref = np.abs(mom) + np.abs(want)
         err = np.abs(got[:, :n] - want)[:, ok] / np.maximum(ref[:, ok], 1e-300)

@@ -12,7 +12,6 @@ references are the restatement there, a fine fixed-step run, and the device itse
 without, 2 x the restatement's error + 1e-12 against the fine run.
 
 No case reaches status 2 after an attempt: the host file's docstring says what was tried."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -21,11 +20,8 @@ import pytest
 import test_box_adaptive_host as B
 import test_ranked_adaptive_host as R
 import test_tsit5_adaptive_host as H
-from test_gpu_box_adaptive import box_adaptive
-from test_gpu_parity import _tsit5_host, dev
-from test_gpu_tsit5_adaptive import adaptive, same_counts, sentinel_planes, two_gamma_plan
-from test_gpu_tsit5_saveat import bits_equal, blank_bits, saveat
-from tsit5_restated import default_opts, save_times
+from gpu_support import _tsit5_host, adaptive, bits_equal, box_adaptive, is_blank, same_counts, saveat, two_gamma_plan
+from tsit5_restated import save_times
 
 pytestmark = pytest.mark.gpu
 
@@ -37,52 +33,14 @@ both = pytest.mark.parametrize("entry,kind", CASES)
 
 
 def run(cloudy, oracle, entry, kind, u0, s, t_span, **kw):
-    """one call of an entry point on (u0, s); ld = n + 15 unless given.  -> the drivers' dict"""
+    """one call of an entry point on (u0, s); ld = n + 15 unless given.  -> the driver's dict"""
     _, _, plan = two_gamma_plan(cloudy, oracle, kind)
     kw.setdefault("ld", u0.shape[1] + 15)
     u0 = np.ascontiguousarray(u0)
-    if entry == "adaptive":
-        return adaptive(cloudy, plan, u0, t_span, **kw)
-    if entry == "saveat":
-        return saveat(cloudy, plan, u0, t_span, save_times(t_span), **kw)
     times = save_times(t_span) if SAVES[entry] else ()
+    if FAMILY[entry] == "coal":
+        return (saveat if SAVES[entry] else adaptive)(cloudy, plan, u0, t_span, times, **kw)
     return box_adaptive(cloudy, plan, u0, t_span, np.ascontiguousarray(s), B.XI_BOX, times=times, **kw)
-
-
-def direct(cloudy, oracle, entry, kind, u0, s, t_span, dt_in="zeros", max_steps=10000):
-    """The C entry points called as the drivers call them (ld = n + 15, out of place, sentinel-filled outputs, the drivers' dict), for
-    what the drivers leave out: a caller's dt_dev for cloudy_tsit5_adaptive_saveat, and dt_dev = NULL (dt_in = None) for
-    cloudy_box_tsit5_adaptive."""
-    L = cloudy.lib()
-    _, _, plan = two_gamma_plan(cloudy, oracle, kind)
-    planes, n = u0.shape
-    ld = n + 15
-    buf = np.full((planes, ld), 7.0)
-    buf[:, :n] = u0
-    u_in, u_out = dev(cloudy, buf), dev(cloudy, sentinel_planes(planes, ld))
-    dt_d = None if dt_in is None else dev(cloudy, (np.zeros(ld) if isinstance(dt_in, str) else np.pad(dt_in, (0, ld - n)))[None, :])
-    dt_p = None if dt_d is None else dt_d.ptr
-    t_d, info = dev(cloudy, sentinel_planes(1, ld)), cloudy.DeviceArray.zeros(3, ld, np.int32)
-    times = save_times(t_span) if SAVES[entry] else ()
-    n_save = len(times)
-    snap = dev(cloudy, sentinel_planes(max(n_save, 1) * planes, ld))
-    arr = (C.c_double * max(n_save, 1))(*times)
-    opts = default_opts(cloudy, max_steps=max_steps)
-    if entry == "adaptive":
-        rc = L.cloudy_tsit5_adaptive(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), dt_p, t_d.ptr, info.ptr, None)
-    elif entry == "saveat":
-        rc = L.cloudy_tsit5_adaptive_saveat(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), dt_p, t_d.ptr, info.ptr, None,
-                                            n_save, arr, snap.ptr)
-    else:
-        s_d = dev(cloudy, np.pad(np.asarray(s, dtype=np.float64), (0, ld - n))[None, :])
-        rc = L.cloudy_box_tsit5_adaptive(plan.handle, n, ld, u_in.ptr, u_out.ptr, 3, s_d.ptr, 0.0, B.XI_BOX, t_span, C.byref(opts), dt_p,
-                                         t_d.ptr, info.ptr, None, n_save, arr if n_save else None, snap.ptr if n_save else None)
-    assert rc == 0, (rc, L.cloudy_last_error().decode())
-    out, counts = u_out.to_numpy(), info.to_numpy()
-    sv = snap.to_numpy().reshape(max(n_save, 1), planes, ld)[:n_save]
-    return dict(u=out[:, :n], pad=out[:, n:], u_in=u_in.to_numpy(), buf=buf, t=t_d.to_numpy()[0, :n], accepted=counts[0, :n],
-                rejected=counts[1, :n], status=counts[2, :n], dt=None if dt_d is None else dt_d.to_numpy()[0, :n],
-                saved=sv[:, :, :n], saved_pad=sv[:, :, n:])
 
 
 def keys(entry):
@@ -104,9 +62,9 @@ def assert_same_bits(entry, base, part, idx, flip=False):
 
 
 def untouched(entry, got):
-    assert np.all(blank_bits(got["pad"])) and bits_equal(got["u_in"], got["buf"])
+    assert np.all(is_blank(got["pad"])) and bits_equal(got["u_in"], got["buf"])
     if SAVES[entry]:
-        assert np.all(blank_bits(got["saved_pad"]))
+        assert np.all(is_blank(got["saved_pad"]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -214,7 +172,7 @@ def test_hostile_neighbours(gpu_cloudy, oracle, entry, kind):
             assert bits_equal(lanes, np.repeat(base[k][..., dense:dense + 1], lanes.shape[-1], axis=-1)), k
     if SAVES[entry]:
         assert bits_equal(got["saved"][0], h0)
-        assert np.isnan(got["saved"][1:, :, bad]).all() and not np.any(blank_bits(got["saved"][:, :, bad]))
+        assert np.isnan(got["saved"][1:, :, bad]).all() and not np.any(is_blank(got["saved"][:, :, bad]))
         assert np.isfinite(got["saved"][:, :, zero | (role == 3)]).all()
     untouched(entry, got)
 
@@ -254,7 +212,7 @@ def test_budget(gpu_cloudy, oracle, entry, kind):
         assert beyond[:, slow].any() and (~beyond[:, slow]).any() and not beyond[:, ~slow].any()
         nan, fin = np.isnan(got["saved"]), np.isfinite(got["saved"])
         assert np.all(nan.all(axis=1) == beyond) and np.all(fin.all(axis=1) == ~beyond)
-        assert not np.any(blank_bits(got["saved"]))
+        assert not np.any(is_blank(got["saved"]))
         both_fin = fin & np.isfinite(ref["saved"])
         srel = np.abs(got["saved"] - ref["saved"]) / np.maximum(np.abs(u0)[None] + np.abs(ref["saved"]), 1e-300) / ref["evals"][None, None, :]
         worst = np.where(both_fin, srel, 0.0)[:, :, same].max()
@@ -275,7 +233,7 @@ def test_nonfinite_estimate_is_rejected_and_recovered_from(gpu_cloudy, oracle, e
     family, kind, n, t_span = FAMILY[entry], R.H5["kind"], R.H5["n"], R.H5["t_span"]
     ref, took = R.h5_reference(family)
     u0, s, _ = R.batch(family, kind, n)
-    got = direct(gpu_cloudy, oracle, entry, kind, u0, s, t_span, dt_in=np.full(n, R.H5["dt"]))
+    got = run(gpu_cloudy, oracle, entry, kind, u0, s, t_span, dt_in=np.full(n, R.H5["dt"]))
     assert took.any() and np.all(got["status"] == 0) and np.all(got["t"] == t_span) and np.isfinite(got["u"]).all()
     same = same_counts(got, ref)
     worst = parity(entry, u0, got, ref, same)
@@ -313,7 +271,7 @@ def test_warm_start_and_in_place(gpu_cloudy, oracle, entry):
     cold = run(cloudy, oracle, entry, kind, first["u"], s, t_span)
     assert np.all(warm["status"] == 0)
     assert (warm["accepted"] + warm["rejected"]).sum() <= (cold["accepted"] + cold["rejected"]).sum()
-    auto = direct(cloudy, oracle, entry, kind, u0, s, t_span, dt_in=None)
+    auto = run(cloudy, oracle, entry, kind, u0, s, t_span, dt_in=None)
     assert auto["dt"] is None
     for k in ("u", "t", "accepted", "rejected", "status"):
         assert bits_equal(auto[k], first[k]), k

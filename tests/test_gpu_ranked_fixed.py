@@ -35,10 +35,7 @@ import pytest
 
 import bench
 import test_ranked_fixed_host as R
-from test_gpu_box_sources import rel_err
-from test_gpu_parity import TOL_QUAD, _ssprk33_host, _tsit5_host, assert_close_scaled, dev
-from test_gpu_tsit5_adaptive import sentinel_planes
-from test_gpu_tsit5_saveat import SENTINEL32, bits_equal, blank_bits
+from gpu_support import TOL_QUAD, _ssprk33_host, _tsit5_host, assert_close_scaled, bits_equal, blank, dev, is_blank, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -52,12 +49,6 @@ N = R.N
 def device_plan(cloudy, plan, dtype=0, vel=False):
     wl = bench.make_workload(R.PLANS[plan], 1)
     return wl["coal_data"].plan(wl["dist_types"], dtype=dtype, **({"vel": R.VEL} if vel else {}))
-
-
-def blank(planes, ld, dtype):
-    if dtype == np.float64:
-        return sentinel_planes(planes, ld)
-    return np.full((planes, ld), SENTINEL32, dtype=np.uint32).view(np.float32)
 
 
 def run(cloudy, entry, plan, u0, s):
@@ -89,7 +80,7 @@ def run(cloudy, entry, plan, u0, s):
     assert rc == 0, (rc, L.cloudy_last_error().decode())
     got = [o.to_numpy() for o in outs]
     res = dict(out=[g[:, :n] for g in got], pad=[g[:, n:] for g in got], u_in=u_in.to_numpy(), buf=buf)
-    assert all(np.all(blank_bits(q)) for q in res["pad"]), "the padding columns were written"
+    assert all(np.all(is_blank(q)) for q in res["pad"]), "the padding columns were written"
     assert bits_equal(res["u_in"], res["buf"]), "the input changed"
     return res
 
@@ -149,7 +140,7 @@ def test_parity_at_1025(gpu_cloudy, oracle, entry, plan):
         assert np.all(np.abs(cs - wcs) <= TOL_QUAD * np.maximum(scale, 1e-300))
         assert np.allclose(sf, wsf, rtol=1e-11, atol=0)
     else:
-        want, ok = R.stepping_reference(plan, entry)   # (box: test_gpu_box_sources.oracle_reference)
+        want, ok = R.stepping_reference(plan, entry)   # (box: gpu_support.oracle_reference)
         assert ok.sum() >= 0.9 * N, ok.sum()
         err = rel_err(out, want, u0, ok)
         bound = max(1e3 * TOL_QUAD, 1e-9)
@@ -248,14 +239,14 @@ def run_columns(cloudy, entry, u0, ncol):
     ld = n + 15
     buf = np.full((planes, ld), 7.0)
     buf[:, :n] = u0
-    u_in, out, work = dev(cloudy, buf), dev(cloudy, sentinel_planes(planes, ld)), dev(cloudy, sentinel_planes(planes, ld))
+    u_in, out, work = dev(cloudy, buf), dev(cloudy, blank(planes, ld)), dev(cloudy, blank(planes, ld))
     if entry == "steps":
         rc = L.cloudy_rainshaft_ssprk33_steps(p.handle, R.NZ, ncol, ld, u_in.ptr, out.ptr, R.DZ, R.COL_DT, R.COL_STEPS, None)
     else:
         rc = L.cloudy_rainshaft_rhs(p.handle, R.NZ, ncol, ld, u_in.ptr, R.DZ, work.ptr, out.ptr, None)
     assert rc == 0, (rc, L.cloudy_last_error().decode())
     got = [out.to_numpy()] + ([work.to_numpy()] if entry == "rhs" else [])
-    assert all(np.all(blank_bits(g[:, n:])) for g in got) and bits_equal(u_in.to_numpy(), buf)
+    assert all(np.all(is_blank(g[:, n:])) for g in got) and bits_equal(u_in.to_numpy(), buf)
     return [g[:, :n] for g in got]
 
 
@@ -320,7 +311,7 @@ def test_plane_sums_are_exact(gpu_cloudy, n, dtype):
     ld = n + 5
     buf = np.full((R.SUM_PLANES, ld), 1e30, dtype=dtype)
     buf[:, :n] = R.sum_planes(n)
-    x, sums = dev(cloudy, buf), dev(cloudy, sentinel_planes(R.SUM_PLANES, 1))
+    x, sums = dev(cloudy, buf), dev(cloudy, blank(R.SUM_PLANES, 1))
     cloudy._lib.check(cloudy.lib().cloudy_moment_sums(p.handle, n, ld, R.SUM_PLANES, x.ptr, sums.ptr, None))
     got = sums.to_numpy().reshape(-1)
     assert np.isfinite(got).all() and np.all(got == np.floor(got))

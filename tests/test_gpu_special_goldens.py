@@ -19,7 +19,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_parity import EPS, INF, TOL_QUAD, dev
+from gpu_support import EPS, INF, TOL_QUAD, dev
 
 pytestmark = pytest.mark.gpu
 

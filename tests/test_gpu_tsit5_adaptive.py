@@ -4,7 +4,6 @@ single-mode Golovin box, and the fixed-step tableau (_tsit5_host) at a fine step
 
 Run with `-m gpu`.  Batch sizes: a single parcel, a partial wave beyond one wave, a partial workgroup beyond one workgroup
 (1, 65, 257).  The batches and t_span are picked on the oracle alone (test_tsit5_adaptive_host.py)."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -12,62 +11,9 @@ import pytest
 
 import bench
 import test_tsit5_adaptive_host as H
-from test_gpu_parity import INF, _tsit5_host, dev, make_case
-from tsit5_restated import default_opts
+from gpu_support import SENTINEL, SIZES, _tsit5_host, adaptive, dev, golovin_plan, same_counts, two_gamma_plan
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = np.float64(np.nan).view(np.uint64) | np.uint64(0x5EED)   # a NaN no arithmetic produces
-SIZES = (1, 65, 257)
-
-
-def sentinel_planes(planes, ld):
-    return np.full((planes, ld), SENTINEL, dtype=np.uint64).view(np.float64)
-
-
-@functools.lru_cache(maxsize=None)
-def golovin_plan(cloudy, oracle, dist):
-    par, op, _ = make_case(cloudy, oracle, [1 if dist == "gamma" else 0], H.GOLOVIN_KC, (INF,), bench.NORMS)
-    return par, op, par.coal_data.plan([1 if dist == "gamma" else 0])
-
-
-@functools.lru_cache(maxsize=None)
-def two_gamma_plan(cloudy, oracle, kind, dtype=0, specialize=0):
-    _, kc, thr, moving = H.two_gamma_case(oracle, kind)
-    par, op, _ = make_case(cloudy, oracle, [1, 1], kc, thr, bench.NORMS, moving=moving)
-    return par, op, par.coal_data.plan([1, 1], dtype=dtype, specialize=specialize)
-
-
-def adaptive(cloudy, plan, u0, t_span, reltol=1e-6, abstol=1e-9, dt=0.0, max_steps=10000, ld=None, dt_in="zeros", in_place=False,
-             expect=0):
-    """the C entry point itself on a batch u0 (planes, n) in buffers of leading dimension ld -> dict of numpy results"""
-    L = cloudy.lib()
-    planes, n = u0.shape
-    ld = n if ld is None else ld
-    buf = np.full((planes, ld), 7.0, dtype=u0.dtype)
-    buf[:, :n] = u0
-    u_in = dev(cloudy, buf)
-    if in_place:
-        u_out = u_in
-    else:
-        s = sentinel_planes(planes, ld)
-        u_out = dev(cloudy, s if u0.dtype == np.float64 else np.full((planes, ld), np.nan, dtype=np.float32))
-    dt_d = None if dt_in is None else dev(cloudy, (np.zeros(ld) if isinstance(dt_in, str) else np.pad(dt_in, (0, ld - n)))[None, :])
-    t_d = dev(cloudy, sentinel_planes(1, ld))
-    info = cloudy.DeviceArray.zeros(3, ld, np.int32)
-    opts = default_opts(cloudy, reltol=reltol, abstol=abstol, dt_init=dt, max_steps=max_steps)
-    rc = L.cloudy_tsit5_adaptive(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), None if dt_d is None else dt_d.ptr,
-                                 t_d.ptr, info.ptr, None)
-    assert rc == expect, (rc, L.cloudy_last_error().decode())
-    out = u_out.to_numpy()
-    counts = info.to_numpy()
-    res = dict(u=out[:, :n], pad=out[:, n:], u_in=u_in.to_numpy(), buf=buf, t=t_d.to_numpy()[0, :n], accepted=counts[0, :n],
-               rejected=counts[1, :n], status=counts[2, :n], dt=None if dt_d is None else dt_d.to_numpy()[0, :n])
-    return res
-
-
-def same_counts(got, ref):
-    return (got["accepted"] == ref["accepted"]) & (got["rejected"] == ref["rejected"])
 
 
 # ---- 1. closed form
@@ -230,7 +176,7 @@ def test_warm_start_and_in_place(gpu_cloudy, oracle):
     for k in ("u", "t", "accepted", "rejected", "status"):
         assert np.array_equal(auto[k].view(np.uint8), first[k].view(np.uint8)), k
     # opts.dt_init reaches the kernel: a first step of t_span / 1000 costs more attempts than the automatic one
-    small = adaptive(cloudy, plan, u0, H.GOLOVIN_T, dt=H.GOLOVIN_T / 1000, dt_in=None)
+    small = adaptive(cloudy, plan, u0, H.GOLOVIN_T, dt_init=H.GOLOVIN_T / 1000, dt_in=None)
     assert np.all(small["status"] == 0) and small["accepted"].min() >= 3
     # in place equals out of place bit for bit
     inplace = adaptive(cloudy, plan, u0, H.GOLOVIN_T, in_place=True)

@@ -6,7 +6,6 @@ move a bit of the integration.
 Run with `-m gpu`.  Batches, plans and t_span are those of tests/test_gpu_tsit5_adaptive.py (1, 65 and 257 parcels in buffers of
 leading dimension n + 15; thresholded plans at 65 parcels: their oracle is slow); the save times are the twelve of
 tsit5_restated.SAVE_FRACS."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -14,56 +13,13 @@ import pytest
 
 import test_tsit5_adaptive_host as H
 import test_tsit5_saveat_host as S
-from test_gpu_parity import dev
-from test_gpu_tsit5_adaptive import SENTINEL, SIZES, adaptive, golovin_plan, same_counts, sentinel_planes, two_gamma_plan
-from tsit5_restated import SAVE_FRACS, default_opts, save_times
+from gpu_support import SENTINEL, SIZES, adaptive, bits_equal, dev, golovin_plan, is_blank, same_counts, saveat, two_gamma_plan
+from tsit5_restated import SAVE_FRACS, save_times
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL32 = np.uint32(0x7FC05EED)   # a float NaN no arithmetic produces
 KEYS = ("u", "t", "dt", "accepted", "rejected", "status")
 CASES = (("allinf", 257), ("fixed", 65), ("moving", 65))
-
-
-def saveat(cloudy, plan, u0, t_span, times, reltol=1e-6, abstol=1e-9, max_steps=10000, ld=None, in_place=False, expect=0):
-    """the C entry point itself on a batch u0 (planes, n) in buffers of leading dimension ld -> the dict of
-    test_gpu_tsit5_adaptive.adaptive + saved (n_save, planes, n), saved_pad (the columns n .. ld of every snapshot plane) and
-    saved_bits (the whole snapshot buffer as unsigned integers)"""
-    L = cloudy.lib()
-    planes, n = u0.shape
-    ld = n if ld is None else ld
-    f64 = u0.dtype == np.float64
-    blank = (lambda p: sentinel_planes(p, ld)) if f64 else (lambda p: np.full((p, ld), SENTINEL32, dtype=np.uint32).view(np.float32))
-    buf = np.full((planes, ld), 7.0, dtype=u0.dtype)
-    buf[:, :n] = u0
-    u_in = dev(cloudy, buf)
-    u_out = u_in if in_place else dev(cloudy, blank(planes))
-    dt_d = dev(cloudy, np.zeros(ld)[None, :])
-    t_d = dev(cloudy, sentinel_planes(1, ld))
-    info = cloudy.DeviceArray.zeros(3, ld, np.int32)
-    n_save = len(times)
-    snap = dev(cloudy, blank(max(n_save, 1) * planes))
-    arr = (C.c_double * max(n_save, 1))(*times)
-    opts = default_opts(cloudy, reltol=reltol, abstol=abstol, max_steps=max_steps)
-    rc = L.cloudy_tsit5_adaptive_saveat(plan.handle, n, ld, u_in.ptr, u_out.ptr, t_span, C.byref(opts), dt_d.ptr, t_d.ptr, info.ptr, None,
-                                        n_save, arr, snap.ptr)
-    assert rc == expect, (rc, L.cloudy_last_error().decode())
-    out, counts, sv = u_out.to_numpy(), info.to_numpy(), snap.to_numpy()
-    bits = sv.view(np.uint64 if f64 else np.uint32)
-    sv = sv.reshape(max(n_save, 1), planes, ld)[:n_save]
-    return dict(u=out[:, :n], pad=out[:, n:], u_in=u_in.to_numpy(), buf=buf, t=t_d.to_numpy()[0, :n], accepted=counts[0, :n],
-                rejected=counts[1, :n], status=counts[2, :n], dt=dt_d.to_numpy()[0, :n], saved=sv[:, :, :n], saved_pad=sv[:, :, n:],
-                saved_bits=bits)
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def blank_bits(x):
-    """elementwise: still the sentinel of its width (x: fp64 / float planes, or their bits)"""
-    return x.view(np.uint64) == SENTINEL if x.dtype.itemsize == 8 else x.view(np.uint32) == SENTINEL32
 
 
 @functools.lru_cache(maxsize=None)
@@ -101,7 +57,7 @@ def test_golovin_closed_form_at_the_save_times(gpu_cloudy, oracle, dist, reltol,
     assert np.isfinite(got["saved"]).all()
     assert np.all(err <= 2 * ref_err + 1e-12), (err, ref_err)
     assert bits_equal(got["saved"][0], u0) and bits_equal(got["saved"][-1], got["u"])
-    assert np.all(blank_bits(got["saved_pad"]))
+    assert np.all(is_blank(got["saved_pad"]))
 
 
 # ---- 2. saving does not disturb the integration
@@ -121,7 +77,7 @@ def test_saving_does_not_disturb_the_integration(gpu_cloudy, oracle, kind, n):
     for k in KEYS:
         assert bits_equal(none[k], base[k]), k
         assert bits_equal(inplace[k], base[k]), k
-    assert np.all(blank_bits(none["saved_bits"]))          # (nothing to save: the buffer is not touched)
+    assert np.all(is_blank(none["saved_bits"]))          # (nothing to save: the buffer is not touched)
     assert bits_equal(inplace["saved"], got["saved"])
 
 
@@ -134,7 +90,7 @@ def test_end_points_padding_and_input(gpu_cloudy, oracle, kind, n):
     assert got["saved"].shape == (len(SAVE_FRACS), 6, n) and np.isfinite(got["saved"]).all()
     assert bits_equal(got["saved"][-1], got["u"])
     assert bits_equal(got["saved"][0], u0)
-    assert got["saved_pad"].shape[2] == 15 and np.all(blank_bits(got["saved_pad"])) and np.all(blank_bits(got["pad"]))
+    assert got["saved_pad"].shape[2] == 15 and np.all(is_blank(got["saved_pad"])) and np.all(is_blank(got["pad"]))
     assert bits_equal(got["u_in"], got["buf"])
 
 
@@ -177,7 +133,7 @@ def test_budget_leaves_nan_beyond_the_time_reached(gpu_cloudy, oracle):
     assert beyond[:, slow].any() and (~beyond[:, slow]).any() and not beyond[:, ~slow].any()
     nan, fin = np.isnan(got["saved"]), np.isfinite(got["saved"])
     assert np.all(nan.all(axis=1) == beyond) and np.all(fin.all(axis=1) == ~beyond)
-    assert np.all(blank_bits(got["saved_pad"]))
+    assert np.all(is_blank(got["saved_pad"]))
 
 
 # ---- 6. batch independence
@@ -223,7 +179,7 @@ def test_float_planes(gpu_cloudy, oracle, kind):
     print(f"float planes, {kind}: max relative difference over the snapshots {err.max():.2e}")
     assert err.max() <= 2.0 ** -24, err.max()
     assert bits_equal(got["saved"][0], u32) and bits_equal(got["saved"][-1], got["u"])
-    assert np.all(blank_bits(got["saved_pad"]))
+    assert np.all(is_blank(got["saved_pad"]))
 
 
 # ---- 8. refusals
@@ -240,8 +196,8 @@ def test_refusals_name_the_alternative_and_leave_every_output_alone(gpu_cloudy, 
         got = saveat(cloudy, plan, batch, 1e-3, save_times(1e-3), expect=E.EUNSUPPORTED)
         msg = L.cloudy_last_error().decode()
         assert "cloudy_tsit5_steps" in msg, (what, msg)
-        assert np.all(blank_bits(got["saved_bits"])), what
-        assert np.all(blank_bits(got["u"])), what
+        assert np.all(is_blank(got["saved_bits"])), what
+        assert np.all(is_blank(got["u"])), what
         assert not got["accepted"].any() and np.all(got["t"].view(np.uint64) == SENTINEL)
 
 

@@ -136,7 +136,7 @@ def h5_fine(family):
     """-> (the parcels of the H5 batch that take the h / 5 rejection, their end state by the fixed-step tableau at H5_FINE_STEPS
     steps on the oracle's right-hand side), once per session"""
     from oracle import cloudy_oracle
-    from test_gpu_parity import _tsit5_host
+    from gpu_support import _tsit5_host
 
     idx = np.flatnonzero(h5_reference(family)[1])
     u0, s, _ = batch(family, H5["kind"], H5["n"])

@@ -110,8 +110,7 @@ def oracle_rhs(oracle, plan, stepper, s):
 def stepping_reference(plan, stepper):
     """the scheme of `stepper` driven by the oracle's right-hand side on the clean batch, once per session -> (end state, regular and resolved)"""
     from oracle import cloudy_oracle as oracle
-    from test_gpu_box_sources import oracle_reference
-    from test_gpu_parity import _ssprk33_host, _tsit5_host
+    from gpu_support import _ssprk33_host, _tsit5_host, oracle_reference
 
     u0, s, _ = batch(plan)
     with np.errstate(all="ignore"):
@@ -143,7 +142,7 @@ def resolved(oracle, plan, stepper, u0, s, want):
     Where it moves by more, the oracle stepping is no reference at the 1e-9 the device is held to: parcel 417 of the `moving`
     batch keeps its first mode within 10 % under Tsit5 -- regular by the criterion above -- while its second and third modes
     leave the stability region (moments of -3e24 .. 3e39 from 1e-17 .. 1e-3), and its oracle end state moves by 8e-3."""
-    from test_gpu_parity import _ssprk33_host, _tsit5_host
+    from gpu_support import _ssprk33_host, _tsit5_host
 
     host = _tsit5_host if stepper == "tsit5" else _ssprk33_host
     ref = np.maximum(np.abs(u0) + np.abs(want), 1e-300)
