@@ -170,3 +170,71 @@ def get_standard_N_q(plan, mom, size_cutoff=1e-6, out=None, stream=None):
         raise ValueError("out must have the same leading dimension as mom")
     _lib.check(_lib.lib().cloudy_standard_N_q(plan.handle, n, ld, ptr, float(size_cutoff), as_device(o)[0], stream))
     return o
+
+
+def _moments_call(plan, mom, q, x_threshold, per_mode, out, stream):
+    import ctypes as C
+
+    ptr, planes, n, ld = as_device(mom)
+    if planes != plan.nmom:
+        raise TypeError(f"moment: expected {plan.nmom} moment planes, got {planes}")
+    orders = np.atleast_1d(np.asarray(q, dtype=np.float64)).ravel()
+    n_out = (plan.N if per_mode else 1) * orders.size
+    o = out if out is not None else DeviceArray(n_out, ld, plane_dtype(plan))
+    optr, oplanes, _, old = as_device(o)
+    if old != ld or oplanes < n_out:
+        raise ValueError(f"out must hold {n_out} planes of the leading dimension of mom")
+    arr = (C.c_double * max(orders.size, 1))(*orders)
+    _lib.check(_lib.lib().cloudy_moments(plan.handle, n, ld, ptr, int(orders.size), arr, float(x_threshold), int(bool(per_mode)), optr,
+                                         stream))
+    return o
+
+
+def moment(plan, mom, q, per_mode=True, out=None, stream=None):
+    """moment(dist, q) (ParticleDistributions.jl:177-218) of every mode of every parcel at the real order(s) q (a scalar or a
+    sequence of up to 8 values in [0, 16]), batched on the GPU: mom (nmom, n) device, physical units -> device array of
+    N * len(q) planes, plane m * len(q) + j = mode m, order j (per_mode=False: len(q) planes, the sum over the modes); physical
+    units, the plan's plane type."""
+    return _moments_call(plan, mom, q, float("inf"), per_mode, out, stream)
+
+
+def partial_moment(plan, mom, q, x_threshold, per_mode=True, out=None, stream=None):
+    """partial_moment(dist, q, x_threshold) (ParticleDistributions.jl:226-285): the moments of `moment` up to the physical mass
+    x_threshold (+Inf: the full moments); the same planes."""
+    return _moments_call(plan, mom, q, x_threshold, per_mode, out, stream)
+
+
+def _density_call(plan, mom, x, kind, per_mode, out, stream):
+    ptr, planes, n, ld = as_device(mom)
+    if planes != plan.nmom:
+        raise TypeError(f"density: expected {plan.nmom} moment planes, got {planes}")
+    if isinstance(x, DeviceArray):
+        if x.dtype != np.float64:
+            raise TypeError("the grid must be float64")
+        grid, n_x = x, x.shape[0] * x.shape[1]
+    else:   # host values: uploaded
+        xs = np.atleast_1d(np.asarray(x, dtype=np.float64)).ravel()
+        grid, n_x = DeviceArray.from_numpy(xs.reshape(1, -1)), xs.size
+    n_out = n_x * (plan.N if per_mode else 1)
+    o = out if out is not None else DeviceArray(n_out, ld, plane_dtype(plan))
+    optr, oplanes, _, old = as_device(o)
+    if old != ld or oplanes < n_out:
+        raise ValueError(f"out must hold {n_out} planes of the leading dimension of mom")
+    _lib.check(_lib.lib().cloudy_density(plan.handle, n, ld, ptr, kind, n_x, grid.ptr, int(bool(per_mode)), optr, stream))
+    if grid is not x:   # (the launch is asynchronous: the uploaded grid lives until the kernel has read it)
+        _lib.check(_lib.lib().cloudy_stream_synchronize(stream))
+    return o
+
+
+def density(plan, mom, x, per_mode=True, out=None, stream=None):
+    """density(dist, x) (ParticleDistributions.jl:323-355, 395-405) of every mode of every parcel on the grid x of physical
+    masses (a scalar, a sequence, or a float64 DeviceArray; up to 1024 points), batched on the GPU: mom (nmom, n) device, physical
+    units -> device array of len(x) * N planes, plane j * N + m = grid point j, mode m (per_mode=False: len(x) planes, the sum over
+    the modes).  A negative or NaN grid value gives NaN in the planes of that point."""
+    return _density_call(plan, mom, x, _lib.DENSITY, per_mode, out, stream)
+
+
+def normed_density(plan, mom, x, out=None, stream=None):
+    """normed_density(dist, x) (ParticleDistributions.jl:363-388, 407-416): the densities of `density` per unit number
+    concentration, per mode (plans with a Monodisperse mode have none, as in the reference)."""
+    return _density_call(plan, mom, x, _lib.NORMED_DENSITY, True, out, stream)

@@ -19,6 +19,7 @@ from .KernelTensors import CoalescenceTensor, check_symmetry, get_normalized_ker
 from .ParticleDistributions import (ExponentialPrimitiveParticleDistribution, GammaPrimitiveParticleDistribution,
                                     LognormalPrimitiveParticleDistribution, MonodispersePrimitiveParticleDistribution,
                                     compute_thresholds, get_moments, get_standard_N_q, nparams, pack_params, update_dist_from_moments,
+                                    moment, partial_moment, density, normed_density,
                                     check_moment_consistency, closure_stats, CLOSURE_STATS_FIELDS)
 from .Coalescence import (CoalescenceData, NumericalPlan, Plan, get_coal_ints, get_finite_2d_integrals,
                           kernel_func_code, numerical_plan, QUAD_CONVERGED, QUAD_FIXED, F64, F32, F32_FAST,

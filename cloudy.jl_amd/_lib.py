@@ -14,6 +14,8 @@ MAX_MODES, MAX_P, MAX_VEL = 8, 8, 4
 OK, EINVAL, ENOTSYMMETRIC, EHIP, ENOMEM, EUNSUPPORTED, ENODEVICE, ECOMM = 0, -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
 SRC_COAL, SRC_COND = 1, 2  # CLOUDY_SRC_*: the sources of cloudy_box_ssprk33_steps and cloudy_box_tsit5_adaptive
+MAX_ORDERS, MAX_GRID = 8, 1024  # CLOUDY_MAX_ORDERS, CLOUDY_MAX_GRID: the orders of one cloudy_moments call, the grid of one cloudy_density call
+DENSITY, NORMED_DENSITY = 0, 1  # CLOUDY_DENSITY, CLOUDY_NORMED_DENSITY
 
 
 class CloudyError(RuntimeError):
@@ -103,6 +105,8 @@ SYMBOLS = {
     "cloudy_sedimentation_flux": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
     "cloudy_cond_evap": (_i, [_vp, _sz, _sz, _vp, _vp, C.c_double, C.c_double, _vp, _vp]),
     "cloudy_standard_N_q": (_i, [_vp, _sz, _sz, _vp, C.c_double, _vp, _vp]),
+    "cloudy_moments": (_i, [_vp, _sz, _sz, _vp, _i, _dp, C.c_double, _i, _vp, _vp]),
+    "cloudy_density": (_i, [_vp, _sz, _sz, _vp, _i, _sz, _vp, _i, _vp, _vp]),
     "cloudy_rainshaft_sources": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "cloudy_rainshaft_rhs": (_i, [_vp, _sz, _sz, _sz, _vp, C.c_double, _vp, _vp, _vp]),
     "cloudy_rainshaft_ssprk33_steps": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp]),

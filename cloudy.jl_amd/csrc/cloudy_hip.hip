@@ -26,6 +26,7 @@
 #include "box_sources.hpp"
 #include "parcel.hpp"
 #include "adaptive.hpp"
+#include "spectra.hpp"
 #include "reduce_kernels.hpp"
 
 using namespace cloudy;
@@ -353,6 +354,8 @@ JitUnit serving_unit(const cloudy_plan *plan, const LaunchReq &r) {
     case OP_TSIT5_ADAPTIVE: return JIT_ADAPTIVE;
     case OP_BOX_TSIT5_ADAPTIVE: return JIT_BOX_ADAPTIVE;
     case OP_PARCEL_TSIT5_ADAPTIVE: return JIT_PARCEL_ADAPTIVE;
+    case OP_MOMENTS:
+    case OP_DENSITY: return JIT_SPECTRA;
     case OP_RAINSHAFT_SSPRK33: return h.mode == MODE_MOVING ? JIT_UNITS : pick_rainshaft(plan, r.nz, r.n / r.nz, false);
     case OP_RAINSHAFT_TSIT5_ADAPTIVE: return pick_column_adaptive(plan, r.nz, r.n / r.nz, (r.sources & SRC_COND) != 0, r.n_save > 0);
     case OP_RAINSHAFT_COND_SSPRK33:
@@ -382,6 +385,7 @@ int jit_position(const HostPlan &h, JitUnit u, const LaunchReq &r) {
     case JIT_ADAPTIVE: return saveat ? ADAPTIVE_SAVEAT : ADAPTIVE_PLAIN;
     case JIT_BOX_ADAPTIVE: return (coal ? BOXAD_COALCOND : BOXAD_COND) + saveat;
     case JIT_PARCEL_ADAPTIVE: return (coal ? PARAD_COALCOND : PARAD_COND) + saveat;
+    case JIT_SPECTRA: return r.op == OP_DENSITY ? SPECTRA_GRID : SPECTRA_MOMENTS;
     case JIT_PARCEL: return r.op == OP_PARCEL_RHS ? (coal ? PARCEL_RHS_COAL : PARCEL_RHS) : (coal ? PARCEL_COALCOND : PARCEL_COND);
     case JIT_DIAG:
         return r.op == OP_UPDATE_DIST ? DIAG_UPDATE_DIST : r.op == OP_FINITE_2D ? DIAG_FINITE_2D : r.op == OP_SEDI ? DIAG_SEDI_FLUX
@@ -465,6 +469,7 @@ hipError_t launch_jit(const cloudy_plan *plan, JitUnit u, const LaunchReq &r) {
         case A_NQ_CUTOFF: args[i] = &nq_cutoff; break;
         case A_NQ_N0: args[i] = &nq_n0; break;
         case A_NQ_M0: args[i] = &nq_m0; break;
+        case A_SPECTRA: args[i] = const_cast<void *>(r.spectra); break;   // (by value: the pointer to them)
         }
     const size_t per_wg = k.per_lane ? (size_t)k.block * k.per_lane : (size_t)k.block / r.nz * r.nz;
     hipError_t e = hipModuleLaunchKernel(k.fn, (unsigned)((n + per_wg - 1) / per_wg), 1, 1, (unsigned)k.block, 1, 1, 0, r.stream, args, nullptr);
@@ -620,6 +625,10 @@ int launch(const cloudy_plan *plan, const LaunchReq &r) {
         return refuse_without_unit(plan, JIT_PARCEL_ADAPTIVE, "cloudy_parcel_tsit5_adaptive runs the kernel compiled for the plan (hiprtc) "
                                                               "and has no ahead-of-time instance: step such a parcel stage by stage with "
                                                               "cloudy_cond_evap (and cloudy_coal_rhs) and cloudy_parcel_thermo_host");
+    if (r.op == OP_MOMENTS || r.op == OP_DENSITY)
+        return refuse_without_unit(plan, JIT_SPECTRA, "cloudy_moments and cloudy_density run the kernels compiled for the plan (hiprtc) and "
+                                                      "have no ahead-of-time instance: evaluate on the host from "
+                                                      "cloudy_update_dist_from_moments");
     if (r.op == OP_RAINSHAFT_TSIT5_ADAPTIVE) {
         const int bs = jit_column_adaptive_part(plan->h, r.nz, r.n / r.nz);
         return refuse_without_unit(plan, jit_column_unit(r.n_save > 0 ? COLF_DENSE : COLF_ADAPTIVE, bs),
@@ -1545,6 +1554,72 @@ int cloudy_standard_N_q(const cloudy_plan *plan, size_t n, size_t ld, const void
     if (!(size_cutoff > 0)) return fail(CLOUDY_EINVAL, "size_cutoff must be positive");
     LaunchReq r(OP_NQ, n, ld, mom_dev, nq_dev, stream);
     r.s_scalar = size_cutoff;
+    return run(plan, r);
+}
+
+// what cloudy_moments and cloudy_density check of their batch before the plan (check_batch repeats it behind the plan's check)
+static int check_spectra_batch(size_t n, size_t ld, const void *mom_dev, const void *out_dev) {
+    if (ld < n) return fail(CLOUDY_EINVAL, "ld (%zu) must be >= n_parcels (%zu)", ld, n);
+    if (n > 0 && (!mom_dev || !out_dev)) return fail(CLOUDY_EINVAL, "device buffer is NULL");
+    return CLOUDY_OK;
+}
+
+int cloudy_moments(const cloudy_plan *plan, size_t n, size_t ld, const void *mom_dev, int n_orders, const double *orders,
+                   double x_threshold, int per_mode, void *out_dev, void *stream) {
+    if (n_orders < 1 || n_orders > CLOUDY_MAX_ORDERS)
+        return fail(CLOUDY_EINVAL, "n_orders (%d) must be in [1, CLOUDY_MAX_ORDERS] (%d)", n_orders, CLOUDY_MAX_ORDERS);
+    if (!orders) return fail(CLOUDY_EINVAL, "orders is NULL");
+    for (int j = 0; j < n_orders; ++j)
+        if (!std::isfinite(orders[j]) || orders[j] < 0.0 || orders[j] > 16.0)
+            return fail(CLOUDY_EINVAL, "orders[%d] (%g) must be finite and within [0, 16]", j, orders[j]);
+    if (!(x_threshold > 0.0)) return fail(CLOUDY_EINVAL, "x_threshold (%g) must be positive (+Inf: the full moment)", x_threshold);
+    if (per_mode != 0 && per_mode != 1) return fail(CLOUDY_EINVAL, "per_mode (%d) must be 0 or 1", per_mode);
+    int rc = check_spectra_batch(n, ld, mom_dev, out_dev);
+    if (rc || (rc = check_batch(plan, n, ld, mom_dev, out_dev))) return rc;   // (the plane types cloudy_standard_N_q serves: all)
+    static_assert(kMaxOrders == CLOUDY_MAX_ORDERS, "MomentArgs holds CLOUDY_MAX_ORDERS orders");
+    const HostPlan &h = plan->h;
+    MomentArgs a = {};
+    a.n_orders = n_orders;
+    a.partial = std::isinf(x_threshold) ? 0 : 1;
+    a.per_mode = per_mode;
+    a.x_t = a.partial ? x_threshold / h.norms[1] : 0.0;
+    a.ln_x_t = a.partial ? std::log(a.x_t) : 0.0;
+    for (int j = 0; j < n_orders; ++j) {
+        a.q[j] = orders[j];
+        a.scale[j] = h.norms[0] * std::pow(h.norms[1], orders[j]);
+    }
+    LaunchReq r(OP_MOMENTS, n, ld, mom_dev, out_dev, stream);
+    r.spectra = &a;
+    return run(plan, r);
+}
+
+int cloudy_density(const cloudy_plan *plan, size_t n, size_t ld, const void *mom_dev, int kind, size_t n_x, const double *x_dev,
+                   int per_mode, void *out_dev, void *stream) {
+    if (kind != CLOUDY_DENSITY && kind != CLOUDY_NORMED_DENSITY)
+        return fail(CLOUDY_EINVAL, "kind (%d) must be CLOUDY_DENSITY or CLOUDY_NORMED_DENSITY", kind);
+    if (n_x < 1 || n_x > CLOUDY_MAX_GRID) return fail(CLOUDY_EINVAL, "n_x (%zu) must be in [1, CLOUDY_MAX_GRID] (%d)", n_x, CLOUDY_MAX_GRID);
+    if (!x_dev) return fail(CLOUDY_EINVAL, "x_dev is NULL");
+    if (per_mode != 0 && per_mode != 1) return fail(CLOUDY_EINVAL, "per_mode (%d) must be 0 or 1", per_mode);
+    if (kind == CLOUDY_NORMED_DENSITY && !per_mode)
+        return fail(CLOUDY_EINVAL, "per_mode must be 1 for CLOUDY_NORMED_DENSITY: normed densities of several modes do not add to one");
+    int rc = check_spectra_batch(n, ld, mom_dev, out_dev);
+    if (rc || (rc = check_batch(plan, n, ld, mom_dev, out_dev))) return rc;   // (the plane types cloudy_standard_N_q serves: all)
+    static_assert(kMaxGrid == CLOUDY_MAX_GRID && SPECTRA_DENSITY == CLOUDY_DENSITY && SPECTRA_NORMED_DENSITY == CLOUDY_NORMED_DENSITY,
+                  "spectra.hpp restates the header's constants");
+    const HostPlan &h = plan->h;
+    if (kind == CLOUDY_NORMED_DENSITY)
+        for (int i = 0; i < h.N; ++i)
+            if (h.dist_type[i] == CLOUDY_DIST_MONODISPERSE)
+                return fail(CLOUDY_EINVAL, "no method normed_density_func for a Monodisperse distribution (ParticleDistributions.jl:363-388)");
+    DensityArgs a = {};
+    a.n_x = (int32_t)n_x;
+    a.kind = kind;
+    a.per_mode = per_mode;
+    a.m0 = h.norms[1];
+    a.scale = (kind == CLOUDY_DENSITY ? h.norms[0] : 1.0) / h.norms[1];
+    LaunchReq r(OP_DENSITY, n, ld, mom_dev, out_dev, stream);
+    r.spectra = &a;
+    r.s_dev = x_dev;
     return run(plan, r);
 }
 

@@ -59,7 +59,9 @@ enum Op {
     OP_TSIT5_ADAPTIVE = 16 /* per-parcel adaptive Tsit5 (cloudy_tsit5_adaptive, cloudy_tsit5_adaptive_saveat, adaptive.hpp) */,
     OP_BOX_TSIT5_ADAPTIVE = 17 /* the same with the condensation source (cloudy_box_tsit5_adaptive, adaptive_box.hpp) */,
     OP_PARCEL_TSIT5_ADAPTIVE = 18 /* the same on the adiabatic parcel (cloudy_parcel_tsit5_adaptive, adaptive_thermo.hpp) */,
-    OP_RAINSHAFT_TSIT5_ADAPTIVE = 19 /* per-column adaptive Tsit5 of the rainshaft columns (cloudy_rainshaft_tsit5_adaptive[_saveat], adaptive_column.hpp) */
+    OP_RAINSHAFT_TSIT5_ADAPTIVE = 19 /* per-column adaptive Tsit5 of the rainshaft columns (cloudy_rainshaft_tsit5_adaptive[_saveat], adaptive_column.hpp) */,
+    OP_MOMENTS = 20 /* moments of every mode at real orders, up to a cutoff or not (cloudy_moments, spectra.hpp) */,
+    OP_DENSITY = 21 /* densities of every mode on a grid of masses (cloudy_density) */
 };
 
 struct LaunchReq {
@@ -79,6 +81,7 @@ struct LaunchReq {
     const double *s_dev = nullptr;      // OP_COND, OP_BOX_*, OP_RAINSHAFT_COND_* (optional per-parcel supersaturation)
     int sources = 0;                    // OP_BOX_*, OP_PARCEL_*: CLOUDY_SRC_* bits
     const void *parcel = nullptr;       // OP_PARCEL_*: the ParcelParams (parcel.hpp); coef = coef0, s_scalar / s_dev = w / w_dev
+    const void *spectra = nullptr;      // OP_MOMENTS: the MomentArgs; OP_DENSITY: the DensityArgs (spectra.hpp), its grid in s_dev
     const void *adaptive = nullptr;     // OP_*TSIT5_ADAPTIVE: the AdaptiveOpts (adaptive.hpp) ...
     double *dt_dev = nullptr, *t_dev = nullptr;   // ... and its optional per-parcel planes: next dt (in/out), time reached,
     int32_t *info_dev = nullptr;                  // accepted / rejected / status ([3][ld]); OP_RAINSHAFT_TSIT5_ADAPTIVE: per column ([3][n_columns])

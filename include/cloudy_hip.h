@@ -33,6 +33,10 @@
  *   cloudy_rainshaft_ssprk33_steps <- solve(ODEProblem(make_rainshaft_rhs(...), m, tspan, p), SSPRK33(), dt = p.dt),
  *                                    test/examples/Analytical/rainshaft_gamma_mixture.jl:59-60
  *   cloudy_standard_N_q           <- get_standard_N_q(pdists, size_cutoff)  ParticleDistributions.jl:634-687
+ *   cloudy_moments                <- moment(dist, q) / partial_moment(dist, q, x_threshold) at real q, every mode
+ *                                    ParticleDistributions.jl:177-218, 226-285
+ *   cloudy_density                <- density(dist, x) / normed_density(dist, x) on a grid of masses, every mode
+ *                                    ParticleDistributions.jl:323-416
  *   cloudy_cond_evap              <- rhs_condensation!(dmom, mom, p, s) / get_cond_evap
  *                                    test/examples/utils/box_model_helpers.jl:55-67, src/Sources/Condensation.jl:22-37
  *   cloudy_ssprk33_steps          <- solve(ODEProblem(rhs, m0, tspan, p), SSPRK33(), dt = p.dt) of the drivers,
@@ -552,6 +556,44 @@ int cloudy_cond_evap(const cloudy_plan *plan, size_t n_parcels, size_t ld, const
  * (N_liq, N_rai, M_liq, M_rai) in physical units; size_cutoff in physical mass units (the examples pass 1e-6 kg). */
 int cloudy_standard_N_q(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *mom_dev, double size_cutoff,
                         void *nq_dev, void *stream);
+
+/* Real-order moments and size spectra of every mode of every parcel, one launch each: what a host model evaluates around a
+ * microphysics step (effective radius from M_2/3 and M_1, reflectivity from M_2, fall speed from M_1+1/6, their rain-only forms
+ * with a cutoff, the spectra the reference's drivers plot, test/examples/utils/plotting_helpers.jl:104).
+ * mom_dev as for cloudy_standard_N_q: the plan's planes, physical units, the plan's plane type; outputs in the plan's plane type
+ * and in physical units.  Both calls serve tensor plans and NumericalCoalStyle plans of up to CLOUDY_MAX_MODES modes and every
+ * plane type, and run kernels compiled for the plan with hiprtc (no ahead-of-time instance: CLOUDY_EUNSUPPORTED where plan-time
+ * compilation is off or failed).  Arguments that need no plan are checked first (CLOUDY_EINVAL, the message names the argument),
+ * then the plan; a refused call writes nothing. */
+#define CLOUDY_MAX_ORDERS 8
+#define CLOUDY_MAX_GRID 1024
+enum { CLOUDY_DENSITY = 0, CLOUDY_NORMED_DENSITY = 1 };
+
+/* moment(dist, q) (ParticleDistributions.jl:177-218), or, with a finite x_threshold, partial_moment(dist, q, x_threshold)
+ * (:226-285), of every mode of every parcel at n_orders real orders (1 .. CLOUDY_MAX_ORDERS host values, each finite and within
+ * [0, 16]).  x_threshold: physical mass, positive; +Inf: the full moment (no incomplete gamma function is evaluated).
+ * out_dev: M * n_orders planes of leading dimension ld, M = n_modes if per_mode (1), else 1 (0); plane m * n_orders + j holds
+ * mode m, order j; with per_mode = 0 plane j is the sum over the modes in mode order, formed in fp64 from the per-mode values.
+ * On the (n, theta, k) of the closure inversion, times n0 m0^q:
+ *   Gamma / Exponential (k = 1)  n theta^q Gamma(q + k) / Gamma(k)        up to x_t: times P(q + k, x_t / theta)
+ *   Monodisperse                 n theta^q                                 x_t < theta ? 0 : the full moment
+ *   Lognormal                    n exp(q mu + q^2 sigma^2 / 2)             times Phi((ln x_t - mu - q sigma^2) / sigma)
+ * (the Lognormal partial moment in closed form, as cloudy_standard_N_q: the reference integrates with quadgk, :255-269).  A
+ * fallback mode (0, 1, 1) gives 0 at every order.  cloudy_standard_N_q is orders (0, 1) at one cutoff, summed over the modes. */
+int cloudy_moments(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *mom_dev, int n_orders, const double *orders,
+                   double x_threshold, int per_mode, void *out_dev, void *stream);
+
+/* density(dist, x) (kind = CLOUDY_DENSITY) or normed_density(dist, x) (CLOUDY_NORMED_DENSITY) (ParticleDistributions.jl:323-416)
+ * of every mode of every parcel on a grid of n_x masses (1 .. CLOUDY_MAX_GRID device doubles, physical mass): n0 / m0 (1 / m0) times
+ * the normalised (normed) density at x / m0.  out_dev: n_x * M planes, M as above; plane j * M + m holds grid point j, mode m;
+ * per_mode = 0 sums the densities of the modes (CLOUDY_NORMED_DENSITY takes per_mode = 1 only).  The formulas are the reference's
+ * (:323-388), the Monodisperse density its pulse of half width theta / 10; a plan with a Monodisperse mode has no normed density
+ * (CLOUDY_EINVAL, as the reference has no method).  A negative or NaN grid value gives a quiet NaN in every plane of that grid
+ * point and nowhere else: the batch form of error("Density can only be evaluated at nonnegative values.").  At x = 0 the value is
+ * the one the reference's expressions give: Inf (Gamma, k < 1), n / theta (Exponential; Gamma, k = 1), 0 (Gamma, k > 1;
+ * Monodisperse; a fallback Gamma or Exponential mode), NaN (Lognormal). */
+int cloudy_density(const cloudy_plan *plan, size_t n_parcels, size_t ld, const void *mom_dev, int kind, size_t n_x,
+                   const double *x_dev, int per_mode, void *out_dev, void *stream);
 
 /* coalescence source and sedimentation flux of each cell in one fused pass
  * (negative moments clamped to zero, empty cells skipped) */

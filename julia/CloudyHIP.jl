@@ -748,6 +748,47 @@ function rainshaft_cond_rhs!(dm, flux, m, plan::Plan, nz, dz, xi, s; stream = no
     return dm
 end
 
+# ---- diagnostics around a step: real-order moments and size spectra of every mode, one launch each ---------------------------
+const MAX_ORDERS, MAX_GRID = 8, 1024   # CLOUDY_MAX_ORDERS, CLOUDY_MAX_GRID
+
+"""
+    moments!(out, m, plan, q; x_threshold = Inf, per_mode = true, stream = nothing, sync = true)
+
+`moment(dist, q)` -- with a finite `x_threshold` `partial_moment(dist, q, x_threshold)` -- of every mode of every parcel of the device
+array `m` (n_parcels, nmom; physical units) at the real orders `q` (a number or up to $MAX_ORDERS of them, each in [0, 16]), in one
+launch (`cloudy_moments`).  `out` (n_parcels, M * length(q)), M = the number of modes (`per_mode`) or 1 (their sum): column
+`(mode - 1) * length(q) + j` holds order `q[j]` of `mode`, in physical units.
+"""
+function moments!(out, m, plan::Plan, q; x_threshold = Inf, per_mode::Bool = true, stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(m, plan.nmom)
+    orders = Float64[x for x in q]
+    stride(out, 2) == ld || error("out must have the leading dimension of m")
+    st = stream === nothing ? current_stream() : stream
+    check(ccall((:cloudy_moments, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cdouble, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
+                plan.handle, n, ld, pointer(m), length(orders), orders, x_threshold, per_mode ? 1 : 0, pointer(out), st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return out
+end
+
+"""
+    density!(out, m, plan, x; normed = false, per_mode = true, stream = nothing, sync = true)
+
+`density(dist, x)` (`normed`: `normed_density(dist, x)`) of every mode of every parcel of `m` on the grid `x`, a DEVICE vector of up
+to $MAX_GRID physical masses, in one launch (`cloudy_density`).  `out` (n_parcels, length(x) * M): column `(j - 1) * M + mode` holds
+grid point `x[j]` of `mode`; `per_mode = false` (densities only) sums the modes.  A negative or NaN `x[j]` gives NaN in its columns.
+"""
+function density!(out, m, plan::Plan, x; normed::Bool = false, per_mode::Bool = true, stream = nothing, sync::Bool = true)
+    n, ld = batch_shape(m, plan.nmom)
+    stride(out, 2) == ld || error("out must have the leading dimension of m")
+    st = stream === nothing ? current_stream() : stream
+    check(ccall((:cloudy_density, lib), Cint,
+                (Ptr{Cvoid}, Csize_t, Csize_t, Ptr{Cvoid}, Cint, Csize_t, Ptr{Cdouble}, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
+                plan.handle, n, ld, pointer(m), normed ? 1 : 0, length(x), Ptr{Cdouble}(pointer(x)), per_mode ? 1 : 0, pointer(out), st))
+    sync && check(ccall((:cloudy_stream_synchronize, lib), Cint, (Ptr{Cvoid},), st))
+    return out
+end
+
 # ---- multi-GPU: the conservation diagnostic summed over ranks (moments_sum, plotting_helpers.jl:240-252) ------------
 # One Julia process per GPU (MPI.jl / Distributed.jl own the processes): rank 0 draws the id, the host broadcasts its
 # 128 bytes, every rank forms the communicator; the all-reduce itself is RCCL inside the library.

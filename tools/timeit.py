@@ -43,6 +43,11 @@ every experiment switch of the library is an environment variable, so an A/B run
   python tools/timeit.py saveat [--parcels P] [--t-span T] [--reltol R]
         cloudy_tsit5_adaptive_saveat on the batch of `adaptive`: cloudy_tsit5_adaptive itself, then the new entry point with n_save =
         0, 1 and 16 equidistant save times (the last at t_span), and the algorithmic snapshot traffic per parcel
+  python tools/timeit.py spectra [--parcels P]
+        cloudy_moments on the cfg3a batch with 1 and 8 orders, full and up to a cutoff of 1e-9 kg, and cloudy_density at 16 and 100
+        grid points (on as many parcels as keep its output within the bytes of the 8-order call), each beside a fill
+        (cloudy_memset) of as many output planes in the same run: the store floor of the call (the library exports no
+        device-to-device copy; the reads of a call are the plan's 6 moment planes)
   python tools/timeit.py host [--parcels P]
         cloudy_coal_rhs_host on cfg3a: the PCIe-inclusive rate (host arrays staged through the device)
 
@@ -350,6 +355,39 @@ def cmd_saveat(a, pkg, L):
           f"{2 * plan.nmom * 8} B)", flush=True)
 
 
+def cmd_spectra(a, pkg, L):
+    """ms per call of cloudy_moments (1 and 8 orders, full and partial) and cloudy_density (16 and 100 grid points), per mode, on the
+    cfg3a batch, each beside a fill of as many output planes"""
+    n = a.parcels or 10_000_000
+    wl = bench.make_workload("cfg3a", 1)
+    plan = wl["coal_data"].plan(wl["dist_types"])
+    mom = bench.synth_moments(2, n, 7)
+    u0 = pkg.DeviceArray.from_numpy(mom)
+    all_orders = (0.0, 0.25, 2.0 / 3.0, 1.0, 7.0 / 6.0, 2.0, 3.5, 6.0)
+    budget = plan.N * len(all_orders) * n   # output elements of the largest moments call: the density calls stay within them
+
+    def report(what, planes, m, call):
+        out = pkg.DeviceArray(planes, m)
+        ms = bench._sustained_ms(pkg, lambda: pkg._lib.check(call(out)), min_reps=3)
+        fill = bench._sustained_ms(pkg, lambda: pkg._lib.check(L.cloudy_memset(out.ptr, 0, out.nbytes, None)), min_reps=3)
+        out.free()
+        print(f"cfg3a, {m} parcels: {what}: {ms:.3f} ms, fill of {planes} planes {fill:.3f} ms ({ms / fill:.2f} x), "
+              f"{planes * 8} B stored + {plan.nmom * 8} B read per parcel", flush=True)
+
+    for n_orders in (1, 8):
+        arr = (C.c_double * n_orders)(*all_orders[-n_orders:])
+        for x_t in (float("inf"), 1e-9):
+            report(f"cloudy_moments, {n_orders} order(s), {'full' if np.isinf(x_t) else 'up to 1e-9 kg'}", plan.N * n_orders, n,
+                   lambda out: L.cloudy_moments(plan.handle, n, n, u0.ptr, n_orders, arr, x_t, 1, out.ptr, None))
+    for n_x in (16, 100):
+        m = min(n, budget // (n_x * plan.N))
+        grid = pkg.DeviceArray.from_numpy(np.logspace(-14, -5, n_x).reshape(1, -1))
+        um = pkg.DeviceArray.from_numpy(mom[:, :m])   # (one leading dimension for the moments and the densities: m)
+        report(f"cloudy_density, {n_x} grid points", n_x * plan.N, m,
+               lambda out: L.cloudy_density(plan.handle, m, m, um.ptr, 0, n_x, grid.ptr, 1, out.ptr, None))
+        um.free()
+
+
 def cmd_boxadaptive(a, pkg, L):
     """ms per call on the batch of cmd_adaptive: cloudy_tsit5_adaptive, and cloudy_box_tsit5_adaptive with COAL | COND, COND alone and
     COAL | COND with 16 save times (a supersaturation per parcel, U(-0.02, 0.05)); the active-lane fraction of each from its info planes"""
@@ -627,13 +665,15 @@ def main():
     pa.add_argument("--parcels", type=int, default=0)
     pa.add_argument("--t-span", type=float, default=20.0)
     pa.add_argument("--reltol", type=float, default=1e-6)
+    sp = sub.add_parser("spectra")
+    sp.add_argument("--parcels", type=int, default=0)
     hh = sub.add_parser("host")
     hh.add_argument("--parcels", type=int, default=0)
     a = ap.parse_args()
     pkg = load_package()
     {"kernels": cmd_kernels, "conv": cmd_conv, "columns": cmd_columns, "colcond": cmd_colcond, "coladaptive": cmd_coladaptive, "integrators": cmd_integrators, "box": cmd_box, "parcel": cmd_parcel, "adaptive": cmd_adaptive,
      "saveat": cmd_saveat, "boxadaptive": cmd_boxadaptive, "parceladaptive": cmd_parceladaptive,
-     "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
+     "spectra": cmd_spectra, "host": cmd_host}[a.cmd](a, pkg, pkg.lib())
 
 
 if __name__ == "__main__":
